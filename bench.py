@@ -9,12 +9,16 @@ parameters broadcast once, then ONE RCCL all-reduce of the layer's flat gradient
 DistributedDataParallel instead),
 clips sharded over ranks (weak scaling).
 
-Prints ONE JSON line (rank 0).  Besides the contract's fields it carries
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and reports them (`value`,
+`ms_per_step`).  With --full the line also carries what takes runs of its own:
   roofline     -- the CFM attention forward kernel, timed live with HIP events on the launch stream
                   (per-stage events inside libcffm_hip.so), against the HBM roofline; MFMA fraction alongside
   kernels      -- per-stage ms/step breakdown of the timed region (same events)
+  head_step / gtc_step / cfg4_step -- the whole-head step, the CFFM++ prototype layer and the 512x512 layer
   cpu_baseline -- the CPU oracle (a port of the reference algorithm, validated against the reference) timed
-                  on this box's host cores on a bounded sample of the same workload.
+                  on this box's host cores on a bounded sample of the same workload
+  and the run-time checks (parameters finite, ranks in sync, the exposed wait of the gradient exchange).
+--dump-outputs DIR writes what the last timed step handed its caller (see dump_outputs) as .npy files.
 """
 import argparse
 import ctypes as C
@@ -206,6 +210,58 @@ def dw_stream_alone(lib, dev, b, n=30):
         torch.cuda.synchronize(dev)
         out[name] = 1e3 * e0.elapsed_time(e1) / n
     return out
+
+
+def workload(dev, b, rank=0):
+    """The timed step's layer (seeded weights), input clips and upstream gradient on `dev`: the same for every run with the same
+    batch and rank.  -> (layer, x [b,4,256,60,60], gy [b,4,256,60,60])"""
+    import vss_cffm_amd as V
+    torch.manual_seed(0)
+    layer = V.BasicLayer3d3(dim=256, depth=DEPTH, num_heads=8, window_size=7, expand_size=3, pool_method='fc',
+                            focal_level=2, focal_window=5, focal_l_clips=[1, 2, 3], focal_kernel_clips=[7, 5, 3])
+    with torch.no_grad():  # "trained-like" synthetic weights (SURVEY.md 8d): sharper softmax than default init
+        for n, p in layer.named_parameters():
+            if n.endswith('attn.qkv.weight'):
+                p.normal_(0, 0.08)
+            elif 'relative_position_bias_table' in n:
+                p.normal_(0, 0.5)
+    layer.to(dev)
+    gen = torch.Generator(device='cpu').manual_seed(1000 + rank)
+    x = (torch.randn(b, T, 256, GRID, GRID, generator=gen) * 1.5).to(dev)
+    # upstream gradient of the layer output [B,4,256,H,W]: the head consumes only the new target frame
+    # (cffm_head.py:145 `_c_further[:,-1]`), so frames 0..2 receive zeros; fixed synthetic values on the target frame
+    gy = torch.zeros(b, T, 256, GRID, GRID)
+    gy[:, -1] = torch.randn(b, 256, GRID, GRID, generator=gen) / (b * 256 * GRID * GRID)
+    return layer, x, gy.to(dev)
+
+
+DUMP_BUDGET_BYTES = 60_000_000     # --dump-outputs writes at most this much (float32)
+
+
+def dump_outputs(dirname, y, grads, params, moments):
+    """--dump-outputs: what the last timed step handed its caller -- the layer output `y`, the gradient of every parameter
+    (`grad.<name>`), every parameter after the AdamW update (`param.<name>`; at base rate 0 the seeded values, see main) and the
+    AdamW moments the update wrote (`exp_avg.<name>`, `exp_avg_sq.<name>`: they integrate every step's gradients) -- as float32
+    .npy files (57 MB at B = 2).
+    (`y` is [B,4,256,H,W]; the N > 1 graph form computes and hands back the target frame only, [B,256,H,W].)
+    An output that would not fit the budget is written as `y_sample`: a fixed sample of its elements (flat indices drawn
+    with seed 0, ascending), the same for every run with the same arguments."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    rest = {'grad.' + n: g for n, g in grads.items() if g is not None}
+    rest.update(('param.' + n, p) for n, p in params.items())
+    for n, st in moments.items():
+        rest.update((k + '.' + n, st[k]) for k in ('exp_avg', 'exp_avg_sq'))
+    room = max(0, (DUMP_BUDGET_BYTES - 4 * sum(t.numel() for t in rest.values())) // 4)
+    arrays = {}
+    if y.numel() <= room:
+        arrays['y'] = y
+    else:
+        idx = torch.randperm(y.numel(), generator=torch.Generator().manual_seed(0))[:room].sort().values
+        arrays['y_sample'] = y.detach().reshape(-1).cpu()[idx]
+    arrays.update(rest)
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), t.detach().float().cpu().numpy())
 
 
 def launch_ranks(n):
@@ -522,6 +578,10 @@ def main():
     ap.add_argument('--no-head-step', action='store_true', help='skip the whole-head training step reported as `head_step`')
     ap.add_argument('--no-gtc-step', action='store_true', help='skip the CFFM++ prototype-layer step (BASELINE config 5) reported as `gtc_step`')
     ap.add_argument('--no-cfg4-step', action='store_true', help='skip the 512x512 (64 x 64 token grid) step (BASELINE config 4) reported as `cfg4_step`')
+    ap.add_argument('--full', action='store_true', help='also measure and check everything besides the headline: per-stage and roofline '
+                    'timings, the head / CFFM++ / 512x512 steps, the CPU baseline, parameter and rank checks (the --no-* options trim it)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write what the last one computed (layer output, '
+                    'gradients, updated parameters) as float32 DIR/<name>.npy')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -566,16 +626,8 @@ def main():
     from vss_cffm_amd import _lib
     lib = _lib.get()  # raises without the HIP library: no fallback
 
-    torch.manual_seed(0)
-    layer = V.BasicLayer3d3(dim=256, depth=DEPTH, num_heads=8, window_size=7, expand_size=3, pool_method='fc',
-                            focal_level=2, focal_window=5, focal_l_clips=[1, 2, 3], focal_kernel_clips=[7, 5, 3])
-    with torch.no_grad():  # "trained-like" synthetic weights: sharper softmax than default init
-        for n, p in layer.named_parameters():
-            if n.endswith('attn.qkv.weight'):
-                p.normal_(0, 0.08)
-            elif 'relative_position_bias_table' in n:
-                p.normal_(0, 0.5)
-    layer.to(dev)
+    b = args.batch
+    layer, x, gy = workload(dev, b, rank)
     model = layer
     if multi:
         if args.ddp:   # torch's reducer: 52 per-parameter hooks and bucket copies per step
@@ -588,19 +640,19 @@ def main():
     params_list = list(layer.parameters())
     groups = V.optim.paramwise_groups((('decode_head.decoder_focal.' + n, p) for n, p in layer.named_parameters()), base_lr=6e-5, base_wd=0.01)
     opt = V.optim.AdamW(groups, lr=6e-5, betas=(0.9, 0.999), weight_decay=0.01)
-    gen = torch.Generator(device='cpu').manual_seed(1000 + rank)
-    b = args.batch
-    x = (torch.randn(b, T, 256, GRID, GRID, generator=gen) * 1.5).to(dev)
-    # upstream gradient of the layer output [B,4,256,H,W]: the head consumes only the new target frame
-    # (cffm_head.py:145 `_c_further[:,-1]`), so frames 0..2 receive zeros; fixed synthetic values on the target frame
-    gy = torch.zeros(b, T, 256, GRID, GRID)
-    gy[:, -1] = torch.randn(b, 256, GRID, GRID, generator=gen) / (b * 256 * GRID * GRID)
-    gy = gy.to(dev)
+
+    def moments():         # parameter name -> the AdamW state the update launch reads and writes (exp_avg, exp_avg_sq)
+        return {n: opt.state[p] for n, p in layer.named_parameters() if 'exp_avg' in opt.state[p]}
+
+    last_y = []            # --dump-outputs: the latest step's output
+    graph_out = {}         # --dump-outputs: the captured step's output and gradient tensors (every replay rewrites them in place)
 
     def fwd_bwd():
         opt.zero_grad(set_to_none=True)
         y = model(x)
         y.backward(gy)
+        if args.dump_outputs:
+            last_y[:] = [y.detach()]
 
     # N > 1 (default): the gradient exchange is overlapped with the backward, block by block -- block 1's slice of the flat
     # gradient buffer is all-reduced (asynchronously, on RCCL's stream) while block 0's backward kernels run
@@ -613,12 +665,13 @@ def main():
             reducer.finish()
         opt.step()
 
-    # Learning rate: the untimed spin-up / capture / calibration steps run with lr = 0 (same kernels, parameters untouched --
-    # with the fixed synthetic upstream gradient a thousand full-rate steps at the head's 6e-4 walk the weights until they
-    # overflow); from the first warm-up step on, the reference's schedule (local_configs/cffm/B1/cffm.b1.480x480.vspw2.160k.py:
-    # 41-45: poly, power 1, linear warm-up over 1500 iterations from ratio 1e-6) is evaluated on the device from the
-    # optimizer's step count (AdamW.set_poly_schedule), so replayed graphs follow it with no host involvement.
-    base_lrs = [g_['lr'] for g_ in opt.param_groups]
+    # Learning rate: every step of the run -- spin-up, capture, calibration, warm-up and timed -- runs with base rate 0: the same
+    # kernels and traffic, parameters untouched.  The synthetic upstream gradient is fixed, so the objective has no minimum and
+    # Adam moves every weight by ~lr per step in the same direction: at the head's 6e-4 a few thousand steps walk the weights
+    # until activations and the f16 attention operands overflow, and the step's outputs stop being finite.  From the first
+    # warm-up step on, the reference's schedule (local_configs/cffm/B1/cffm.b1.480x480.vspw2.160k.py:41-45: poly, power 1,
+    # linear warm-up over 1500 iterations from ratio 1e-6) is still evaluated on the device from the optimizer's step count
+    # (AdamW.set_poly_schedule), as in training, so the AdamW launch does the same work; it scales the base rate of 0.
     for g_ in opt.param_groups:
         g_['lr'] = 0.0
 
@@ -630,7 +683,7 @@ def main():
         eager_step()
     torch.cuda.synchronize(dev)
 
-    stage_timing = not args.no_stage_timing
+    stage_timing = args.full and not args.no_stage_timing
     nst = lib.cffm_profile_stage_count()
     names = [lib.cffm_profile_stage_name(i).decode() for i in range(nst)]
     ms_buf, n_buf = (C.c_float * nst)(), (C.c_int * nst)()
@@ -667,6 +720,8 @@ def main():
                     ga = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(ga):
                         eager_step()
+                    if args.dump_outputs:
+                        graph_out.update(y=last_y[0], grads={n: p.grad for n, p in layer.named_parameters()})
                     return ga.replay
                 # N > 1: the layer's pieces over static buffers (vss_cffm_amd.ops.LayerPieces: the same library calls as the
                 # autograd path, driven directly so that the backward can be cut between blocks):
@@ -676,6 +731,8 @@ def main():
                 lp = V.ops.LayerPieces(x, DEPTH, [p.detach() for p in ordered])
                 for p_, g_ in zip(ordered, lp.grads):
                     p_.grad = g_
+                if args.dump_outputs:
+                    graph_out.update(y=lp.y, grads={n: p.grad for n, p in layer.named_parameters()})
                 gy_last = gy[:, -1]
                 # Gradient exchange at N > 1 (CFFM_BENCH_EXCHANGE):
                 #   'whole' (default since round 5): the whole backward as ONE library call, then ONE all-reduce of the flat gradient buffer.
@@ -813,8 +870,6 @@ def main():
             step, use_graph, graph_events = eager_step, False, False
             graph_note = 'replay slower than eager launches on this box'
     torch.cuda.synchronize(dev)      # nothing in flight reads the optimizer's pinned mirror while it is rewritten
-    for g_, base in zip(opt.param_groups, base_lrs):
-        g_['lr'] = base
     opt.refresh_hyper()
     opt.set_poly_schedule(max_iters=160000, power=1.0, min_lr=0.0, warmup_iters=1500, warmup_ratio=1e-6)
     for _ in range(args.warmup):
@@ -837,6 +892,11 @@ def main():
         step()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:    # before anything below runs another step
+        if use_graph:
+            dump_outputs(args.dump_outputs, graph_out['y'], graph_out['grads'], dict(layer.named_parameters()), moments())
+        else:
+            dump_outputs(args.dump_outputs, last_y[0], {n: p.grad for n, p in layer.named_parameters()}, dict(layer.named_parameters()), moments())
     attn_ms, attn_n, all_ms, all_n, bsteps = 0.0, 0, None, None, min(args.steps, 20)
     ai = names.index('cfm_attn_fwd')
     if stage_timing:
@@ -914,7 +974,7 @@ def main():
         lib.cffm_profile_collect(ms_buf, n_buf)
         all_ms, all_n = list(ms_buf), list(n_buf)
     collective = None
-    if multi and coll_info.get('probe') is not None:
+    if args.full and multi and coll_info.get('probe') is not None:
         # how long the compute stream WAITS for the gradient exchange (the part of the all-reduces the backward does not cover): event
         # pairs around the reducer's finish() in the three-graph form, a few steps after the timed region (whatever form `value` was
         # measured in -- inside the one-graph form the wait is a graph edge and cannot be bracketed from the host)
@@ -934,27 +994,34 @@ def main():
         if world > 1:
             collective['ring_estimate_us_last_call'] = round(2 * (world - 1) * (last_bytes / world / 153e9 * 1e6 + 2.5), 1)
             collective['ring_estimate_note'] = 'arithmetic, not a measurement: 2 (N - 1) ring steps of bytes / N at ~153 GB/s per xGMI link + ~2.5 us per step, for the %d bytes of the last all-reduce of a step' % last_bytes
-    with torch.no_grad():
-        params_finite = bool(all(torch.isfinite(p).all().item() for p in params_list))
-    ranks_in_sync = None
-    if multi and not args.ddp:
-        # data parallel correctness at run time: every rank started from rank 0's parameters and applied the same averaged
-        # gradients, so the parameters must still be bit-identical everywhere (the inputs differ per rank)
+    params_finite, moments_finite, ranks_in_sync = None, None, None
+    # (at base rate 0 the parameters keep their seeded values; the AdamW moments integrate every step's exchanged gradients,
+    #  so the checks below look at both)
+    state = [t for st in moments().values() for t in (st['exp_avg'], st['exp_avg_sq'])]
+    if args.full:
         with torch.no_grad():
-            cs = torch.stack([p.detach().double().sum() for p in params_list] + [p.detach().double().abs().sum() for p in params_list])
+            params_finite = bool(all(torch.isfinite(p).all().item() for p in params_list))
+            moments_finite = bool(state) and bool(all(torch.isfinite(t).all().item() for t in state))
+    if args.full and multi and not args.ddp:
+        # data parallel correctness at run time: every rank started from rank 0's parameters and fed the same averaged gradients
+        # to AdamW, so the parameters and the moments must still be bit-identical everywhere (the inputs differ per rank: a broken,
+        # skipped or misplaced exchange leaves different gradients, hence different moments, on the ranks)
+        with torch.no_grad():
+            ts = params_list + state
+            cs = torch.stack([t.detach().double().sum() for t in ts] + [t.detach().double().abs().sum() for t in ts])
         lo, hi = cs.clone(), cs.clone()
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         ranks_in_sync = bool(torch.equal(lo, hi))
         if not ranks_in_sync and rank == 0:
-            sys.stderr.write('bench.py: the ranks\' parameters have diverged -- the gradient exchange is broken\n')
+            sys.stderr.write('bench.py: the ranks\' parameters or AdamW moments have diverged -- the gradient exchange is broken\n')
     if multi:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     # the whole-head training step (context number): every rank runs it -- SyncBatchNorm and the gradient exchange are collectives
     hs_all = None
-    if not args.no_head_step:
+    if args.full and not args.no_head_step:
         if reducer is not None:
             reducer.remove()
         try:
@@ -963,13 +1030,13 @@ def main():
             hs_all = {'error': '%s: %s' % (type(e).__name__, str(e).splitlines()[0] if str(e) else '')}
 
     gs = None
-    if rank == 0 and not args.no_gtc_step:
+    if rank == 0 and args.full and not args.no_gtc_step:
         try:
             gs = gtc_step(dev, b)
         except Exception as e:   # noqa: BLE001  (context only: never costs the headline)
             gs = {'error': '%s: %s' % (type(e).__name__, str(e).splitlines()[0] if str(e) else '')}
     c4 = None
-    if rank == 0 and not args.no_cfg4_step:
+    if rank == 0 and args.full and not args.no_cfg4_step:
         try:
             c4 = cfg4_step(dev)
         except Exception as e:   # noqa: BLE001  (context only: never costs the headline)
@@ -1055,7 +1122,7 @@ def main():
             'data_note': ('every step consumes the SAME resident synthetic clip batch (29.5 MB at B = 2) and upstream gradient: they stay in the 256 MB MALL '
                           'between steps, so a step does not pay the first-touch HBM read a fresh batch would (~7 us at ~4 TB/s, ~1 % of the step)'),
             'config': {'workload': 'CFFM-B1 480x480 T=4: hot path on [B,4,256,60,60] fp32, depth 2, fwd+bwd+AdamW',
-                       'clips_per_gpu': b, 'global_batch': world * b, 'parallelism': 'dp%d' % world, 'spinup_steps': args.spinup_steps, 'hip_graph': use_graph, 'hip_graph_calibration': graph_cal, 'ranks_in_sync': ranks_in_sync, 'params_finite': params_finite, 'hip_graph_note': graph_note if not use_graph else ('one graph per step' if not multi else (nonlocal_note[-1] if nonlocal_note else coll_info.get('form'))),
+                       'clips_per_gpu': b, 'global_batch': world * b, 'parallelism': 'dp%d' % world, 'spinup_steps': args.spinup_steps, 'hip_graph': use_graph, 'hip_graph_calibration': graph_cal, 'ranks_in_sync': ranks_in_sync, 'params_finite': params_finite, 'moments_finite': moments_finite, 'hip_graph_note': graph_note if not use_graph else ('one graph per step' if not multi else (nonlocal_note[-1] if nonlocal_note else coll_info.get('form'))),
                        'grad_allreduce': ('RCCL (torch DDP)' if args.ddp else ('RCCL, one asynchronous all-reduce per block of the flat gradient buffer, overlapped with the backward of the next block' if coll_info.get('blockwise') else 'RCCL, ONE all-reduce of the flat gradient buffer (6.8 MB) behind the backward; CFFM_BENCH_EXCHANGE=blockwise selects the per-block overlapped form')) if multi else 'none'},
             'roofline': roof, 'roofline_kernels': rk, 'head_step': hs, 'gtc_step': gs, 'cfg4_step': c4,
             'rccl': {'world': world, 'backend': (dist.get_backend() if multi else None)}, 'collective': collective,
@@ -1064,10 +1131,12 @@ def main():
                                   'measured <= 1.1e-3 (f16 operands of dS/dP in the attention backward), gated at 1.5e-3 -- looser than the contract\'s 1e-3, which is worded on outputs; '
                                   'justified by the 30-step training-trajectory test against the oracle (DESIGN 3g)'},
             'kernels': stages,
-            'kernels_note': 'per-stage HIP-event times from a separate instrumented pass of %d steps after the timed region '
-                            '(event records on every launch slow the step by ~25 %%, so they are kept out of `value`)' % bsteps,
+            'kernels_note': ('per-stage HIP-event times from a separate instrumented pass of %d steps after the timed region '
+                             '(event records on every launch slow the step by ~25 %%, so they are kept out of `value`)' % bsteps) if stage_timing else
+                            'no per-stage pass: run with --full (and without --no-stage-timing) for it',
+            'full': args.full,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out['cpu_baseline'] = cpu_baseline()
         elif world == 1:
             out['cpu_baseline'] = None

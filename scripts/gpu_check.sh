@@ -1,10 +1,10 @@
 #!/bin/bash
 # One GPU-box visit: smoke, parity tests, a short bench and a rocprofv3 kernel trace of it.
-# Everything lands in gpurun_out/ (merged back by gpurun).
+# Everything lands in $OUT/.
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
-mkdir -p gpurun_out
-OUT=gpurun_out
+export OUT=${OUT:-out}   # results directory, relative to the repository root
+mkdir -p $OUT
 rocminfo 2>/dev/null | grep -E "Marketing Name|gfx" | head -4 > $OUT/device.txt
 echo "== smoke" ; timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 ; echo "smoke rc=$?" ; tail -3 $OUT/smoke.log
 echo "== pytest -m gpu" ; timeout 1500 python -m pytest tests -m gpu -q -s -x --no-header -p no:cacheprovider > $OUT/pytest_gpu.log 2>&1 ; echo "pytest rc=$?" ; tail -25 $OUT/pytest_gpu.log

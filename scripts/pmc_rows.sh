@@ -3,15 +3,16 @@
 # group (kernel-trace only), over scripts/segloss_bench.py and scripts/segfuse_bench.py.
 cd "$(dirname "$0")/.." && R=$PWD
 export TMPDIR=/tmp
-mkdir -p gpurun_out/pmc
+export OUT=${OUT:-out}   # results directory, relative to the repository root
+mkdir -p $OUT/pmc
 i=0
 for grp in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY" "SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"; do
   i=$((i+1))
   for s in segloss segfuse; do
-    (cd /tmp && rm -rf /tmp/sqr_${s}_$i && timeout 600 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d /tmp/sqr_${s}_$i -o p -- python $R/scripts/${s}_bench.py > $R/gpurun_out/pmc/sqr_${s}_$i.log 2>&1)
+    (cd /tmp && rm -rf /tmp/sqr_${s}_$i && timeout 600 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d /tmp/sqr_${s}_$i -o p -- python $R/scripts/${s}_bench.py > $R/$OUT/pmc/sqr_${s}_$i.log 2>&1)
   done
 done
-python - <<'PY' | tee gpurun_out/pmc/sq_rows_summary.txt
+python - <<'PY' | tee $OUT/pmc/sq_rows_summary.txt
 import csv, glob, re, collections
 acc = collections.defaultdict(lambda: collections.defaultdict(lambda: [0, 0.0]))
 for f in glob.glob('/tmp/sqr_*/**/*counter_collection.csv', recursive=True):

@@ -1,7 +1,8 @@
 #!/bin/bash
 # the N > 1 paths of bench.py on a one-GPU box: self-launched 2 ranks sharing cuda:0 over gloo (graph pieces + eager), and
 # RCCL itself with a single rank (CFFM_BENCH_FORCE_DIST) for the graph-pieces default, eager blockwise overlap and torch DDP
-cd "$(dirname "$0")/.."; export TMPDIR=/tmp; mkdir -p gpurun_out
+export OUT=${OUT:-out}   # results directory, relative to the repository root
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp; mkdir -p $OUT
 show() { python - "$1" <<'PY'
 import json,sys
 try:
@@ -12,10 +13,10 @@ except Exception as e:
 PY
 }
 echo "== python bench.py --gpus 2 (self-launch; gloo, both ranks on cuda:0)"
-CFFM_BENCH_BACKEND=gloo CFFM_BENCH_ONE_DEVICE=1 timeout 900 python bench.py --gpus 2 --steps 10 --warmup 3 --spinup-steps 20 --no-stage-timing > gpurun_out/d2.log 2> gpurun_out/d2.err; echo rc=$?; tail -c 500 gpurun_out/d2.err; show gpurun_out/d2.log
+CFFM_BENCH_BACKEND=gloo CFFM_BENCH_ONE_DEVICE=1 timeout 900 python bench.py --full --gpus 2 --steps 10 --warmup 3 --spinup-steps 20 --no-stage-timing > $OUT/d2.log 2> $OUT/d2.err; echo rc=$?; tail -c 500 $OUT/d2.err; show $OUT/d2.log
 echo "== same, --eager"
-CFFM_BENCH_BACKEND=gloo CFFM_BENCH_ONE_DEVICE=1 timeout 900 python bench.py --gpus 2 --steps 10 --warmup 3 --spinup-steps 20 --no-stage-timing --eager > gpurun_out/d2e.log 2> gpurun_out/d2e.err; echo rc=$?; tail -c 300 gpurun_out/d2e.err; show gpurun_out/d2e.log
+CFFM_BENCH_BACKEND=gloo CFFM_BENCH_ONE_DEVICE=1 timeout 900 python bench.py --full --gpus 2 --steps 10 --warmup 3 --spinup-steps 20 --no-stage-timing --eager > $OUT/d2e.log 2> $OUT/d2e.err; echo rc=$?; tail -c 300 $OUT/d2e.err; show $OUT/d2e.log
 for v in "" "--eager" "--ddp"; do
   echo "== RCCL, single rank, $v"
-  CFFM_BENCH_FORCE_DIST=1 timeout 400 python bench.py --no-cpu-baseline --no-head-step $v > gpurun_out/dr.log 2> gpurun_out/dr.err; echo "rc=$?"; tail -c 300 gpurun_out/dr.err; show gpurun_out/dr.log
+  CFFM_BENCH_FORCE_DIST=1 timeout 400 python bench.py --full --no-cpu-baseline --no-head-step $v > $OUT/dr.log 2> $OUT/dr.err; echo "rc=$?"; tail -c 300 $OUT/dr.err; show $OUT/dr.log
 done

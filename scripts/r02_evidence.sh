@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round-2 evidence in one GPU-box visit; everything lands in gpurun_out/ with r02_ names (copied into profiles/ afterwards):
+# Round-2 evidence in one GPU-box visit; everything lands in $OUT/ with r02_ names (copied into profiles/ afterwards):
 #   r02_bench.json / .err          the default bench line
 #   r02_bench_kernel_stats.csv     rocprofv3 --kernel-trace --stats of the bench command (no cpu baseline / head step legs)
 #   r02_pmc_FETCH_SIZE.csv, r02_pmc_WRITE_SIZE.csv, r02_pmc_attn_fwd.json   HBM traffic (separate --pmc passes)
@@ -7,19 +7,20 @@
 #   r02_stage_kernel_stats.txt     per-kernel durations of one clip-block step (scripts/kstats.sh)
 #   r02_head_step.txt              torch-profiler attribution of the whole-head step
 #   r02_segloss_kernel_stats.csv, r02_segloss_pmc_sq.txt   the fused resize + cross entropy kernels
-cd "$(dirname "$0")/.." && R=$PWD; export TMPDIR=/tmp; mkdir -p gpurun_out/pmc
+export OUT=${OUT:-out}   # results directory, relative to the repository root
+cd "$(dirname "$0")/.." && R=$PWD; export TMPDIR=/tmp; mkdir -p $OUT/pmc
 bash scripts/r02_bench_profile.sh 2>&1 | tail -40
-bash scripts/pmc_attn.sh > gpurun_out/r02_pmc_hbm.txt 2>&1
-cp gpurun_out/pmc/FETCH_SIZE.summary.csv gpurun_out/r02_pmc_FETCH_SIZE.csv; cp gpurun_out/pmc/WRITE_SIZE.summary.csv gpurun_out/r02_pmc_WRITE_SIZE.csv
+bash scripts/pmc_attn.sh > $OUT/r02_pmc_hbm.txt 2>&1
+cp $OUT/pmc/FETCH_SIZE.summary.csv $OUT/r02_pmc_FETCH_SIZE.csv; cp $OUT/pmc/WRITE_SIZE.summary.csv $OUT/r02_pmc_WRITE_SIZE.csv
 python - <<'PY'
-import csv, json
+import csv, json, os
 def load(p):      # kernel names contain commas: the two numeric columns are the last two fields
     out = {}
     for line in list(open(p))[1:]:
         name, n, avg = line.rstrip().rsplit(',', 2)
         out[name] = float(avg)
     return out
-f, w = load('gpurun_out/r02_pmc_FETCH_SIZE.csv'), load('gpurun_out/r02_pmc_WRITE_SIZE.csv')
+f, w = load(os.path.join(os.environ['OUT'], 'r02_pmc_FETCH_SIZE.csv')), load(os.path.join(os.environ['OUT'], 'r02_pmc_WRITE_SIZE.csv'))
 k = [n for n in f if 'k_cfm_attn_fwd' in n][0]
 cal = 'k_copy_batched'
 out = {'kernel': 'k_cfm_attn_fwd', 'batch_clips': 2, 'FETCH_SIZE_KB_per_launch': f[k], 'WRITE_SIZE_KB_per_launch': w.get(k, 0.0),
@@ -29,10 +30,10 @@ out = {'kernel': 'k_cfm_attn_fwd', 'batch_clips': 2, 'FETCH_SIZE_KB_per_launch':
                        'lse = 7.52 MB); the attention kernel gathers 64-byte (token, head) slices of the f16 q/k/v rows (unique data 15.9 MB), for which the raw counter '
                        'already matches, so the raw value is reported as traffic and the x2 value as an upper bound') % (f.get(cal, 0) / 1024, w.get(cal, 0) / 1024),
        'source': 'rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes), scripts/pmc_attn.sh; profiles/r02_pmc_*.csv'}
-json.dump(out, open('gpurun_out/r02_pmc_attn_fwd.json', 'w'), indent=1)
+json.dump(out, open(os.path.join(os.environ['OUT'], 'r02_pmc_attn_fwd.json'), 'w'), indent=1)
 print(json.dumps(out)[:300])
 PY
-bash scripts/pmc_sq.sh "attn|dkv_gather|ln_pool|gemm|bias" > /dev/null 2>&1; cp gpurun_out/pmc/sq_summary.txt gpurun_out/r02_pmc_sq.txt
-bash scripts/kstats.sh "" "." > gpurun_out/r02_stage_kernel_stats.txt 2>&1
-bash scripts/r02_head_profile.sh > gpurun_out/r02_head_step.txt 2>&1; head -12 gpurun_out/r02_head_step.txt
-bash scripts/r02_segloss_pmc.sh > /dev/null 2>&1; grep upce gpurun_out/r02_segloss_kernel_stats.csv | cut -c1-160
+bash scripts/pmc_sq.sh "attn|dkv_gather|ln_pool|gemm|bias" > /dev/null 2>&1; cp $OUT/pmc/sq_summary.txt $OUT/r02_pmc_sq.txt
+bash scripts/kstats.sh "" "." > $OUT/r02_stage_kernel_stats.txt 2>&1
+bash scripts/r02_head_profile.sh > $OUT/r02_head_step.txt 2>&1; head -12 $OUT/r02_head_step.txt
+bash scripts/r02_segloss_pmc.sh > /dev/null 2>&1; grep upce $OUT/r02_segloss_kernel_stats.csv | cut -c1-160

@@ -1,8 +1,9 @@
 #!/bin/bash
 # Where the time between kernels goes: rocprofv3 kernel trace of the bench command, idle / overlapped time per replayed step
-cd "$(dirname "$0")/.." && R=$PWD; export TMPDIR=/tmp; mkdir -p gpurun_out
+export OUT=${OUT:-out}   # results directory, relative to the repository root
+cd "$(dirname "$0")/.." && R=$PWD; export TMPDIR=/tmp; mkdir -p $OUT
 (cd /tmp && rm -rf /tmp/gt && rocprofv3 --kernel-trace --output-format csv -d /tmp/gt -o x -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-head-step --spinup-steps 50 ${BENCH_EXTRA} > /dev/null 2>&1)
-python - <<'PY' | tee gpurun_out/r02_gap_trace.txt
+python - <<'PY' | tee $OUT/r02_gap_trace.txt
 import csv, glob
 f = glob.glob('/tmp/gt/**/*kernel_trace.csv', recursive=True)[0]
 rows = [(int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name'].split('(')[0][:40], r.get('Queue_Id', ''), r.get('Stream_Id', '')) for r in csv.DictReader(open(f))]

@@ -1,6 +1,7 @@
 #!/bin/bash
 # the whole-head training step: GPU tests of the fused row path + torch-profiler kernel attribution of the step
-cd "$(dirname "$0")/.."; export TMPDIR=/tmp; mkdir -p gpurun_out
+export OUT=${OUT:-out}   # results directory, relative to the repository root
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp; mkdir -p $OUT
 timeout 900 python -m pytest tests/test_headfuse.py tests/test_boundary.py tests/test_data.py tests/test_segfuse.py tests/test_segloss.py -m gpu -x -q --no-header -p no:cacheprovider 2>&1 | tail -3
 HEAD_STEP_ONLY=hip,hip python scripts/head_step_bench.py 2>/dev/null | tail -1
 python - <<'PY'

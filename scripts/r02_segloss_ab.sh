@@ -1,6 +1,7 @@
 #!/bin/bash
 # segloss backward: block form (default) against the round-1 gather form; tests, op time and per-kernel time
-cd "$(dirname "$0")/.."; export TMPDIR=/tmp; mkdir -p gpurun_out; R=$(pwd)
+export OUT=${OUT:-out}   # results directory, relative to the repository root
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp; mkdir -p $OUT; R=$(pwd)
 timeout 600 python -m pytest tests/test_segloss.py tests/test_segfuse.py -m gpu -x -q --no-header -p no:cacheprovider 2>&1 | tail -3
 for f in block gather; do
   echo "== CFFM_UPCE_BWD=$f"; CFFM_UPCE_BWD=$f timeout 300 python scripts/segloss_bench.py 2>/dev/null | tail -1

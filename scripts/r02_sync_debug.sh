@@ -11,5 +11,5 @@ PY
 }
 for v in "--graph" "--eager" ""; do
 echo "== 2 ranks gloo one device $v"
-CFFM_BENCH_BACKEND=gloo CFFM_BENCH_ONE_DEVICE=1 timeout 900 python bench.py --gpus 2 --steps 10 --warmup 3 --spinup-steps 20 --no-stage-timing $v > /tmp/d.log 2> /tmp/d.err; echo rc=$?; grep -v "Gloo\|socket\|amdgpu" /tmp/d.err | tail -3; show /tmp/d.log
+CFFM_BENCH_BACKEND=gloo CFFM_BENCH_ONE_DEVICE=1 timeout 900 python bench.py --full --gpus 2 --steps 10 --warmup 3 --spinup-steps 20 --no-stage-timing $v > /tmp/d.log 2> /tmp/d.err; echo rc=$?; grep -v "Gloo\|socket\|amdgpu" /tmp/d.err | tail -3; show /tmp/d.log
 done

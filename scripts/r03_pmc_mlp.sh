@@ -1,6 +1,7 @@
 #!/bin/bash
 # L2 hit rate of the fused MLP kernels with and without their global stores (PNL_ABLATE=4 build): does the store stream evict the weights?
-cd "$(dirname "$0")/.." && R=$PWD; export TMPDIR=/tmp; mkdir -p gpurun_out
+export OUT=${OUT:-out}   # results directory, relative to the repository root
+cd "$(dirname "$0")/.." && R=$PWD; export TMPDIR=/tmp; mkdir -p $OUT
 for a in 0 4; do
   for pmc in "TCC_HIT_sum TCC_MISS_sum" "TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum"; do
     (cd /tmp && rm -rf /tmp/pm && rocprofv3 --kernel-trace --pmc $pmc --output-format csv -d /tmp/pm -o x -- $R/build/r03_mlp_abl$a > /dev/null 2>&1)

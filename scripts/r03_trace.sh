@@ -1,12 +1,13 @@
 #!/bin/bash
 # rocprofv3 kernel trace (per-dispatch start / end timestamps) of a short bench run: per-kernel stats + a timeline of ONE step
 # (which kernels overlap, where the gaps are).  usage: scripts/r03_trace.sh <tag> [extra bench args]
-cd "$(dirname "$0")/.." && R=$PWD; export TMPDIR=/tmp; mkdir -p gpurun_out
+export OUT=${OUT:-out}   # results directory, relative to the repository root
+cd "$(dirname "$0")/.." && R=$PWD; export TMPDIR=/tmp; mkdir -p $OUT
 TAG=${1:-x}; shift
-(cd /tmp && rm -rf /tmp/bp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/bp -o x -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-head-step --no-stage-timing --spinup-steps 50 "$@" > $R/gpurun_out/r03_trace_$TAG.json 2>/dev/null)
-cp $(find /tmp/bp -name '*kernel_stats.csv' | head -1) gpurun_out/r03_kernel_stats_$TAG.csv
+(cd /tmp && rm -rf /tmp/bp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/bp -o x -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-head-step --no-stage-timing --spinup-steps 50 "$@" > $R/$OUT/r03_trace_$TAG.json 2>/dev/null)
+cp $(find /tmp/bp -name '*kernel_stats.csv' | head -1) $OUT/r03_kernel_stats_$TAG.csv
 python - $TAG <<'PY'
-import csv, sys, glob, json
+import csv, sys, glob, json, os
 tag = sys.argv[1]
 f = glob.glob('/tmp/bp/**/*kernel_trace.csv', recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
@@ -14,7 +15,7 @@ rows.sort(key=lambda r: int(r['Start_Timestamp']))
 # the last 6 steps: a step starts at each k_param_prep
 idx = [i for i, r in enumerate(rows) if r['Kernel_Name'].startswith('k_param_prep') or r['Kernel_Name'].startswith('k_transpose_prep')]
 try:
-    j = json.loads(open('gpurun_out/r03_trace_%s.json' % tag).read().strip().splitlines()[-1])
+    j = json.loads(open(os.path.join(os.environ['OUT'], 'r03_trace_%s.json') % tag).read().strip().splitlines()[-1])
     print('bench under rocprof: %.4f ms/step' % j['ms_per_step'])
 except Exception as e:
     print('bench line unreadable', e)
@@ -34,10 +35,10 @@ if len(idx) > 8:
             cur_e = max(cur_e, e)
     u += cur_e - cur_s
     print('one step: %d kernels, span %.1f us, sum of kernel times %.1f us, union busy %.1f us (gaps %.1f us)' % (len(step), span / 1e3, busy / 1e3, u / 1e3, (span - u) / 1e3))
-    with open('gpurun_out/r03_timeline_%s.txt' % tag, 'w') as o:
+    with open(os.path.join(os.environ['OUT'], 'r03_timeline_%s.txt') % tag, 'w') as o:
         for r in step:
             o.write('%9.1f %8.1f  q%-3s %s\n' % ((int(r['Start_Timestamp']) - t0) / 1e3, (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3, r.get('Queue_Id', '?'), r['Kernel_Name'][:70]))
-st = list(csv.DictReader(open('gpurun_out/r03_kernel_stats_%s.csv' % tag)))
+st = list(csv.DictReader(open(os.path.join(os.environ['OUT'], 'r03_kernel_stats_%s.csv') % tag)))
 tot = sum(float(r['TotalDurationNs']) for r in st)
 nstep = max(1, len(idx))
 print('kernel time per step (all streams): %.1f us over %d steps' % (tot / 1e3 / nstep, nstep))
@@ -46,7 +47,7 @@ for r in st[:26]:
 PY
 python - <<'PY'
 # per-launch durations of the kernels that run once per block, in launch order (block 0 / block 1 alternate in the forward)
-import csv, glob
+import csv, glob, os
 f = glob.glob('/tmp/bp/**/*kernel_trace.csv', recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
 rows.sort(key=lambda r: int(r['Start_Timestamp']))

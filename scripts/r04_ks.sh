@@ -1,6 +1,7 @@
 #!/bin/bash
 # Round-4: the key-split attention backward: stage tests, stage timing under rocprofv3 (experiments build: group count, ablation builds)
-cd "$(dirname "$0")/.." && R=$PWD; export TMPDIR=/tmp; mkdir -p gpurun_out
+export OUT=${OUT:-out}   # results directory, relative to the repository root
+cd "$(dirname "$0")/.." && R=$PWD; export TMPDIR=/tmp; mkdir -p $OUT
 T=${1:-a}
 run() { # label, env...
   (cd /tmp && rm -rf /tmp/bp && env "${@:2}" rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/bp -o x -- timeout 300 python $R/scripts/r04_attn_bwd_bench.py $LIB 2>&1 | grep "attn_bwd stage")
@@ -19,4 +20,4 @@ LIB=$R/build/libcffm_exp.so
 run g27 CFFM_BWD_GROUPS=27
 for ng in 32; do run g$ng CFFM_BWD_GROUPS=$ng; done
 for l in $R/build/libcffm_ks_abl*.so; do [ -f $l ] && LIB=$l && run $(basename $l) ; done
-} 2>&1 | grep -v "^$\|amdgpu.ids" | tee gpurun_out/r04_ks_${T}.txt
+} 2>&1 | grep -v "^$\|amdgpu.ids" | tee $OUT/r04_ks_${T}.txt

@@ -1,14 +1,15 @@
 #!/bin/bash
 # CFFM++ prototype layer (BASELINE config 5): GPU parity tests of the fused block + its timing (bench.py gtc_step) + rocprofv3 kernel stats.
-cd "$(dirname "$0")/.." && R=$PWD; export TMPDIR=/tmp; mkdir -p gpurun_out
+export OUT=${OUT:-out}   # results directory, relative to the repository root
+cd "$(dirname "$0")/.." && R=$PWD; export TMPDIR=/tmp; mkdir -p $OUT
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_boundary.py -x -q -m gpu -k "gtc or cffmpp or headpp or config5" 2>&1 | tail -5
-python - <<'PY' > gpurun_out/r05_gtc_step.json
+python - <<'PY' > $OUT/r05_gtc_step.json
 import json, sys, torch
 sys.path.insert(0, '.')
 import bench
 print(json.dumps(bench.gtc_step(torch.device('cuda:0'), 2), indent=1))
 PY
-cat gpurun_out/r05_gtc_step.json
+cat $OUT/r05_gtc_step.json
 cat > /tmp/gtc_prof.py <<'PY'
 import sys, torch
 sys.path.insert(0, sys.argv[1])
@@ -23,5 +24,5 @@ for k in (8, 100):
 torch.cuda.synchronize()
 PY
 (cd /tmp && rm -rf /tmp/gp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/gp -o x -- python /tmp/gtc_prof.py $R > /dev/null 2>&1)
-cp $(find /tmp/gp -name '*kernel_stats.csv' | head -1) gpurun_out/r05_gtc_kernel_stats.csv; head -25 gpurun_out/r05_gtc_kernel_stats.csv | cut -c1-150
-python scripts/r05_gtc_unfused_record.py 2>&1 | tee gpurun_out/r05_gtc_fused_vs_unfused.txt
+cp $(find /tmp/gp -name '*kernel_stats.csv' | head -1) $OUT/r05_gtc_kernel_stats.csv; head -25 $OUT/r05_gtc_kernel_stats.csv | cut -c1-150
+python scripts/r05_gtc_unfused_record.py 2>&1 | tee $OUT/r05_gtc_fused_vs_unfused.txt

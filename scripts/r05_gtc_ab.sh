@@ -1,10 +1,11 @@
 #!/bin/bash
 # A/B of library builds on the CFFM++ prototype block: usage scripts/r05_gtc_ab.sh <tag> lib1.so lib2.so ...   (two alternations; bench.py gtc_step)
-cd "$(dirname "$0")/.." && R=$PWD; mkdir -p gpurun_out
+export OUT=${OUT:-out}   # results directory, relative to the repository root
+cd "$(dirname "$0")/.." && R=$PWD; mkdir -p $OUT
 T=$1; shift
 for rep in 1 2; do
 for l in "$@"; do
-  CFFM_LIB=$l python - <<PY | tee -a gpurun_out/r05_gtc_ab_$T.txt
+  CFFM_LIB=$l python - <<PY | tee -a $OUT/r05_gtc_ab_$T.txt
 import os, sys, torch
 sys.path.insert(0, '.')
 from vss_cffm_amd import _lib

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round-6 evidence in one GPU-box visit; everything lands in gpurun_out/ with r06_ names (copied into profiles/ afterwards):
+# Round-6 evidence in one GPU-box visit; everything lands in $OUT/ with r06_ names (copied into profiles/ afterwards):
 #   r06_bench.json / .err          the default bench line
 #   r06_bench_kernel_stats.csv     rocprofv3 --kernel-trace --stats of the bench command (no cpu baseline / head step legs)
 #   r06_timeline_graph.txt         one replayed step: start / duration / hardware queue of every kernel (scripts/r06_trace.sh)
@@ -11,31 +11,32 @@
 #   r06_head_timeline.txt          one replayed whole-head step (scripts/r06_head_trace.sh)
 #   r06_gpu_suite.txt              tail of pytest -m gpu
 
-cd "$(dirname "$0")/.." && R=$PWD; export TMPDIR=/tmp; mkdir -p gpurun_out/pmc
-python bench.py --steps 20 --warmup 5 > gpurun_out/r06_bench.json 2> gpurun_out/r06_bench.err; tail -2 gpurun_out/r06_bench.err
-(cd /tmp && rm -rf /tmp/bp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/bp -o x -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-head-step --no-gtc-step --no-cfg4-step --spinup-steps 100 > $R/gpurun_out/r06_bench_prof.json 2>/dev/null)
-cp $(find /tmp/bp -name '*kernel_stats.csv' | head -1) gpurun_out/r06_bench_kernel_stats.csv
+export OUT=${OUT:-out}   # results directory, relative to the repository root
+cd "$(dirname "$0")/.." && R=$PWD; export TMPDIR=/tmp; mkdir -p $OUT/pmc
+python bench.py --full --steps 20 --warmup 5 > $OUT/r06_bench.json 2> $OUT/r06_bench.err; tail -2 $OUT/r06_bench.err
+(cd /tmp && rm -rf /tmp/bp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/bp -o x -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-head-step --no-gtc-step --no-cfg4-step --spinup-steps 100 > $R/$OUT/r06_bench_prof.json 2>/dev/null)
+cp $(find /tmp/bp -name '*kernel_stats.csv' | head -1) $OUT/r06_bench_kernel_stats.csv
 python - <<'PY'
-import csv, json
-j = json.loads(open('gpurun_out/r06_bench.json').read().strip().splitlines()[-1])
+import csv, json, os
+j = json.loads(open(os.path.join(os.environ['OUT'], 'r06_bench.json')).read().strip().splitlines()[-1])
 print('bench:', j['value'], j['ms_per_step'], 'graph', j['config']['hip_graph'], j['config']['hip_graph_calibration'], 'roofline', j['roofline']['frac'], j['roofline']['avg_launch_us'], j['roofline'].get('back_to_back_us'), 'head', j['head_step'] and j['head_step'].get('ms_per_step'), 'cpu', j['cpu_baseline'] and j['cpu_baseline']['value'])
-rows = list(csv.DictReader(open('gpurun_out/r06_bench_kernel_stats.csv')))
+rows = list(csv.DictReader(open(os.path.join(os.environ['OUT'], 'r06_bench_kernel_stats.csv'))))
 tot = sum(float(r['TotalDurationNs']) for r in rows)
 for r in rows[:30]:
     print('%-64s %6s calls %8.1f us avg %5.1f %%' % (r['Name'][:64], r['Calls'], float(r['AverageNs']) / 1e3, 100 * float(r['TotalDurationNs']) / tot))
 PY
-bash scripts/r06_trace.sh graph --graph | head -3; cp gpurun_out/r06_timeline_graph.txt gpurun_out/r06_timeline_graph_evidence.txt
-bash scripts/pmc_attn.sh > gpurun_out/r06_pmc_hbm.txt 2>&1
-cp gpurun_out/pmc/FETCH_SIZE.summary.csv gpurun_out/r06_pmc_FETCH_SIZE.csv; cp gpurun_out/pmc/WRITE_SIZE.summary.csv gpurun_out/r06_pmc_WRITE_SIZE.csv
+bash scripts/r06_trace.sh graph --graph | head -3; cp $OUT/r06_timeline_graph.txt $OUT/r06_timeline_graph_evidence.txt
+bash scripts/pmc_attn.sh > $OUT/r06_pmc_hbm.txt 2>&1
+cp $OUT/pmc/FETCH_SIZE.summary.csv $OUT/r06_pmc_FETCH_SIZE.csv; cp $OUT/pmc/WRITE_SIZE.summary.csv $OUT/r06_pmc_WRITE_SIZE.csv
 python - <<'PY'
-import json
+import json, os
 def load(p):      # kernel names contain commas: the two numeric columns are the last two fields
     out = {}
     for line in list(open(p))[1:]:
         name, n, avg = line.rstrip().rsplit(',', 2)
         out[name] = float(avg)
     return out
-f, w = load('gpurun_out/r06_pmc_FETCH_SIZE.csv'), load('gpurun_out/r06_pmc_WRITE_SIZE.csv')
+f, w = load(os.path.join(os.environ['OUT'], 'r06_pmc_FETCH_SIZE.csv')), load(os.path.join(os.environ['OUT'], 'r06_pmc_WRITE_SIZE.csv'))
 k = [n for n in f if 'k_cfm_attn_fwd' in n][0]
 cal = [n for n in f if 'k_mlp_fwd' in n]
 calnote = ''
@@ -49,12 +50,12 @@ out = {'kernel': 'k_cfm_attn_fwd', 'batch_clips': 2, 'FETCH_SIZE_KB_per_launch':
                        'of the f16 q/k/v rows (unique data 15.9 MB), for which the raw FETCH counter already matches (MI355X_MICROARCH.md halves FETCH_SIZE only for wide '
                        'streaming reads), so the raw value is reported as traffic and the x2 value as an upper bound'),
        'source': 'rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes), scripts/pmc_attn.sh; profiles/r06_pmc_*.csv'}
-json.dump(out, open('gpurun_out/r06_pmc_attn_fwd.json', 'w'), indent=1)
+json.dump(out, open(os.path.join(os.environ['OUT'], 'r06_pmc_attn_fwd.json'), 'w'), indent=1)
 print(json.dumps(out)[:300])
 PY
-bash scripts/r06_pmc_table.sh > /dev/null 2>&1; head -8 gpurun_out/r06_pmc_sq.txt
-bash scripts/kstats.sh "" "." > gpurun_out/r06_stage_kernel_stats.txt 2>&1
-bash scripts/r02_head_profile.sh > gpurun_out/r06_head_step.txt 2>&1; head -12 gpurun_out/r06_head_step.txt
-bash scripts/r06_gtc.sh > gpurun_out/r06_gtc_all.txt 2>&1; grep -A3 "K=100" gpurun_out/r06_gtc_step.json | head -5
-bash scripts/r06_head_trace.sh final 2>&1 | tail -2; cp gpurun_out/r06_head_timeline_final.txt gpurun_out/r06_head_timeline.txt
-timeout 1800 python -m pytest tests -q -m gpu 2>&1 | tail -4 > gpurun_out/r06_gpu_suite.txt; cat gpurun_out/r06_gpu_suite.txt
+bash scripts/r06_pmc_table.sh > /dev/null 2>&1; head -8 $OUT/r06_pmc_sq.txt
+bash scripts/kstats.sh "" "." > $OUT/r06_stage_kernel_stats.txt 2>&1
+bash scripts/r02_head_profile.sh > $OUT/r06_head_step.txt 2>&1; head -12 $OUT/r06_head_step.txt
+bash scripts/r06_gtc.sh > $OUT/r06_gtc_all.txt 2>&1; grep -A3 "K=100" $OUT/r06_gtc_step.json | head -5
+bash scripts/r06_head_trace.sh final 2>&1 | tail -2; cp $OUT/r06_head_timeline_final.txt $OUT/r06_head_timeline.txt
+timeout 1800 python -m pytest tests -q -m gpu 2>&1 | tail -4 > $OUT/r06_gpu_suite.txt; cat $OUT/r06_gpu_suite.txt

@@ -1,10 +1,11 @@
 #!/bin/bash
 # rocprofv3 kernel trace of the whole-head training step replayed from one HIP graph: timeline of ONE replay (start, duration, queue).
 # usage: scripts/r06_head_trace.sh <tag>
-cd "$(dirname "$0")/.." && R=$PWD; export TMPDIR=/tmp; mkdir -p gpurun_out
+export OUT=${OUT:-out}   # results directory, relative to the repository root
+cd "$(dirname "$0")/.." && R=$PWD; export TMPDIR=/tmp; mkdir -p $OUT
 TAG=${1:-x}
 cat > /tmp/head_trace.py <<'PY'
-import sys, torch
+import sys, torch, os
 sys.path.insert(0, sys.argv[1])
 import bench
 dev = torch.device('cuda:0')
@@ -14,10 +15,10 @@ orig_sync = torch.cuda.synchronize
 out = bench.head_step(dev, 2, steps=6)
 print(out)
 PY
-(cd /tmp && rm -rf /tmp/hp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/hp -o x -- python /tmp/head_trace.py $R > $R/gpurun_out/r06_head_trace_$TAG.log 2>&1)
-tail -2 gpurun_out/r06_head_trace_$TAG.log | cut -c1-400
+(cd /tmp && rm -rf /tmp/hp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/hp -o x -- python /tmp/head_trace.py $R > $R/$OUT/r06_head_trace_$TAG.log 2>&1)
+tail -2 $OUT/r06_head_trace_$TAG.log | cut -c1-400
 python - $TAG <<'PY'
-import csv, sys, glob
+import csv, sys, glob, os
 tag = sys.argv[1]
 f = glob.glob('/tmp/hp/**/*kernel_trace.csv', recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
@@ -51,7 +52,7 @@ if per:
             ce = max(ce, e)
     u += ce - cs
     print('one replay: %d kernels, span %.1f us, sum of kernel times %.1f us, union busy %.1f us (gaps %.1f us)' % (len(step), span / 1e3, busy / 1e3, u / 1e3, (span - u) / 1e3))
-    with open('gpurun_out/r06_head_timeline_%s.txt' % tag, 'w') as o:
+    with open(os.path.join(os.environ['OUT'], 'r06_head_timeline_%s.txt') % tag, 'w') as o:
         for r in step:
             o.write('%9.1f %8.1f  q%-3s %s\n' % ((int(r['Start_Timestamp']) - t0) / 1e3, (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3, r.get('Queue_Id', '?'), r['Kernel_Name'][:90]))
 PY

@@ -1,17 +1,18 @@
 #!/bin/bash
 # Per-SIMD utilisation of every hot kernel: SQ_ACTIVE_INST_* are quad-cycles summed over waves
 # (MI355X_MICROARCH.md), so busy fraction of a pipe = counter x 4 / (1024 SIMDs x kernel duration x clock).  Durations: rocprofv3
-# kernel trace of the same driver (scripts/stage_times.py, eager launches, B = 2).  Output: gpurun_out/r06_pmc_sq.txt
-cd "$(dirname "$0")/.." && R=$PWD; export TMPDIR=/tmp; mkdir -p gpurun_out/pmc
+# kernel trace of the same driver (scripts/stage_times.py, eager launches, B = 2).  Output: $OUT/r06_pmc_sq.txt
+export OUT=${OUT:-out}   # results directory, relative to the repository root
+cd "$(dirname "$0")/.." && R=$PWD; export TMPDIR=/tmp; mkdir -p $OUT/pmc
 bash scripts/pmc_sq.sh "attn|dkv_gather|ln_pool|gemm|mlp|panel|dw_dma" > /dev/null 2>&1
 (cd /tmp && rm -rf /tmp/sq_dur && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/sq_dur -o p -- python $R/scripts/stage_times.py --steps 5 > /dev/null 2>&1)
-python - <<'PY' | tee gpurun_out/r06_pmc_sq.txt
-import csv, glob, re
+python - <<'PY' | tee $OUT/r06_pmc_sq.txt
+import csv, glob, re, os
 dur = {}
 for r in csv.DictReader(open(glob.glob('/tmp/sq_dur/**/*kernel_stats.csv', recursive=True)[0])):
     dur[r['Name'].split('(')[0][:48]] = float(r['AverageNs']) * 1e-9
 cur, vals = None, {}
-for line in open('gpurun_out/pmc/sq_summary.txt'):
+for line in open(os.path.join(os.environ['OUT'], 'pmc/sq_summary.txt')):
     if not line.startswith('   '):
         cur = line.strip(); vals[cur] = {}
     else:
@@ -32,4 +33,4 @@ for k, d in vals.items():
         d.get('SQ_WAIT_ANY', 0) / max(d.get('SQ_WAVE_CYCLES', 1), 1), d.get('SQ_LDS_BANK_CONFLICT', 0) / max(d.get('SQ_LDS_IDX_ACTIVE', 1), 1)))
     print('%-44s         | MFMA pipe busy %.2f-%.2f' % ('', d.get('SQ_VALU_MFMA_BUSY_CYCLES', 0) / (1024 * t * 2.4e9), d.get('SQ_VALU_MFMA_BUSY_CYCLES', 0) / (1024 * t * 2.1e9)))
 PY
-cp gpurun_out/pmc/sq_summary.txt gpurun_out/r06_pmc_sq_raw.txt
+cp $OUT/pmc/sq_summary.txt $OUT/r06_pmc_sq_raw.txt
