@@ -6,12 +6,12 @@
  *
  *   cffm_layer_forward / _backward   <->  BasicLayer3d3.forward            cffm_transformer.py:917-927
  *   cffm_block_forward / _backward   <->  CffmTransformerBlock3d3.forward  cffm_transformer.py:709-832
- *   cffm_ln_pool_fwd / _bwd          <->  CFFA: norm1 + pad + pool_layers / pool_layers_clips
+ *   cffm_ln_pool_fwd                 <->  CFFA: norm1 + pad + pool_layers / pool_layers_clips
  *                                                                           cffm_transformer.py:716-805
- *   cffm_bias_assemble / _scatter    <->  relative-position bias gathers    cffm_transformer.py:536-587
+ *   cffm_bias_assemble               <->  relative-position bias gathers    cffm_transformer.py:536-587
  *   cffm_attn_fwd / _bwd             <->  WindowAttention3d3.forward (CFM)  cffm_transformer.py:364-606
  *   cffm_linear_*                    <->  nn.Linear (qkv :374, proj :602, Mlp :10-26)
- *   cffm_residual_ln, cffm_bias_gelu, cffm_residual_out  <->  residual/norm2/Mlp glue  :823-824
+ *   cffm_mlp_fwd / _bwd              <->  proj + residual + norm2 + Mlp + residual  :602, :823-824
  *   cffm_gtc_*                       <->  BasicLayer_cluster / WindowAttention_cluster (CFFM++)
  *                                                         pvt/swin_transformer_2d.py:1103-1148, :208-262
  *
@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CFFM_ABI_VERSION 10
+#define CFFM_ABI_VERSION 11
 
 typedef struct cffm_geom {
     int B, H0, W0;      /* clips, unpadded 1/8-scale grid                                   */
@@ -106,7 +106,6 @@ int cffm_profile_collect_graph(float* ms /*[stage_count]*/, int* calls /*[stage_
 /* dst[n][c][r] = src[n][r][c] for n < batch (element strides src_bs / dst_bs between batches) */
 int cffm_transpose(const float* src, float* dst, int batch, int rows, int cols, long src_bs, long dst_bs, void* stream);
 int cffm_pool_matrix(const float* const pool_w[4], float* M /*[15*49]*/, void* stream);
-int cffm_pool_matrix_bwd(const float* dM, float* const dpool_w[4], void* stream);
 /* Process-wide: tells the library that EVERY gradient tensor handed to the block / layer backward sits in a slice of a flat buffer
  * padded to a multiple of 4 floats (vss_cffm_amd.ops lays them out so; a data-parallel exchange all-reduces that buffer whole), and
  * asks it to zero the padding itself: the backward of the pooling Linears -- owners of the only tensors whose length is not a multiple
@@ -116,11 +115,6 @@ void cffm_grad_slices_padded(int yes);
 int cffm_ln_pool_fwd(const cffm_geom* g, const float* x_ref, long ref_bs, const float* x_tgt, long tgt_bs,
                      const float* gamma, const float* beta, const float* M, const float* const pool_b[4],
                      float* zall, float* mean, float* rstd, void* stream);
-int cffm_ln_pool_bwd(const cffm_geom* g, const float* x_ref, long ref_bs, const float* x_tgt, long tgt_bs,
-                     const float* gamma, const float* beta, const float* M, const float* mean, const float* rstd,
-                     const float* dzall, const float* dres /* [B*HW,256] added to the target-frame grad, may be NULL */,
-                     float* dx_ref, long dref_bs, int accum_ref, float* dx_tgt, long dtgt_bs,
-                     float* dgamma, float* dbeta, float* dM, float* const dpool_b[4], void* stream);
 /* the dense additive bias [8 heads][64 queries][304 keys] (cffm_transformer.py:536-587 gathers it from six tables) in two
  * layouts, each may be NULL: bias = query-major fp32 [8,64,304] (checks); biasH = what cffm_attn_fwd / cffm_attn_bwd read: f16
  * B-operand fragments [8 heads][4 waves][10 key-tile pairs][64 lanes][8], entry (h, wave, p, lane = 16 g + j, e) = bias(h, query
@@ -128,7 +122,6 @@ int cffm_ln_pool_bwd(const cffm_geom* g, const float* x_ref, long ref_bs, const 
  * (S^T tile t = K Q^T + Sel_(t & 1) * B) from one contiguous 1 KiB load per (wave, tile pair).  (8*4*10*512 halfs = 320 KB; ABI 6:
  * tile pairs, ABI <= 5 kept one tile per fragment.) */
 int cffm_bias_assemble(const float* own, const float* ring, const float* const pool[4], float* bias, void* biasH, void* stream);
-int cffm_bias_scatter(const float* dbiasT, float* down, float* dring, float* const dpool[4], void* stream);
 /* qkv16 [B*RC,768] f16 = zall w^T + b with the q third times 32^-0.5 (cffm_linear_qkv_fwd) */
 int cffm_linear_qkv_fwd(const float* zall, const float* w /*[768,256]*/, const float* b /*[768]*/, void* qkv16, long M,
                         void* stream);
@@ -153,12 +146,6 @@ int cffm_linear_bwd_weight(const float* dy, const float* x, float* dw, long M, i
 /* n <= 4 independent weight gradients (dw_i[N_i,K_i] = dy_i[M_i,N_i]^T x_i[M_i,K_i]) in one launch: the four Linear layers of a
  * block (qkv / proj / fc1 / fc2 .weight.grad, cffm_transformer.py:374, :381, :18-19), none of which feeds the backward chain */
 typedef struct { const float* dy; const float* x; float* dw; long M; int N; int K; } cffm_wgrad;
-/* Weight gradient with both operands in split-4 storage (16 bytes = {bf16 hi x4 | bf16 lo x4} of four consecutive floats of a row: what the
- * block's producers write for GEMM-only tensors): tiles go global -> LDS by DMA, no staging arithmetic (csrc/dw_kernels.h).  N, K multiples
- * of 128.  cffm_split4 makes such a copy of a plain fp32 array (n floats, n % 4 == 0). */
-int cffm_split4(const float* src, float* dst, long n, void* stream);
-int cffm_linear_bwd_weight_split(const float* dy_s, const float* x_s, float* dw, long M, int N, int K, void* stream);
-int cffm_linear_bwd_weight_split_group(const cffm_wgrad* problems, int n /* <= 3 */, void* stream);   /* one launch, one common k-slice length */
 int cffm_linear_bwd_weight_group(const cffm_wgrad* problems /* host */, int n, void* stream);
 /* ABI 9: weight gradient with both operands in "T-frag" storage (csrc/dws_kernels.h): MFMA fragments along the contraction -- unit (ks, jt, h)
  * = 64 lanes x 16 B at 16-byte word ((ks * C/16 + jt) * 2 + h) * 64, lane (l15, g) holding x[32 ks + 8 g + e][16 jt + l15], e = 0..7, as bf16
@@ -174,11 +161,6 @@ int cffm_dw_stream(int on);
 int cffm_tfrag_pack(const float* x, float* dst, long R, int C /* % 16 == 0 */, void* stream);
 int cffm_linear_bwd_weight_tfrag(const float* dy_t, const float* x_t, float* dw, long M, int N, int K, void* stream);
 int cffm_linear_bwd_weight_tfrag_group(const cffm_wgrad* problems /* host; dy / x in T-frag storage */, int n /* <= 4 */, void* stream);
-/* fused Mlp halves: hraw = x w^T (raw, kept for backward), act = gelu(hraw + b)  |  out = res + x w^T + b */
-int cffm_linear_gelu_fwd(const float* x, const float* w, const float* b, float* hraw, float* act, long M, int N, int K,
-                         void* stream);
-int cffm_linear_residual_fwd(const float* x, const float* w, const float* b, const float* res, float* out, long M, int N,
-                             int K, void* stream);
 /* ---- fused row-panel stages (round 3): one launch per direction for everything between the attention output and the block
  * output -- proj (cffm_transformer.py:602), residual (:823), norm2 + Mlp (fc1, exact GELU, fc2: :10-26) + residual (:824).
  * Weights are passed in MFMA-fragment order (cffm_panel_pack_weight: form 0 = forward y = x W^T, form 1 = input gradient
@@ -189,41 +171,15 @@ int cffm_linear_residual_fwd(const float* x, const float* w, const float* b, con
  *   backward: dh = (dout W2) * gelu'(hraw + b1); dx1 = dout + LN'(dh W1); dao = dx1 Wp; dg2, dbe2, db1, db2 = colsum(dout),
  *             dbp = colsum(dx1) (every one fully written)                                                                   */
 int cffm_panel_pack_weight(const float* w, int N, int K, int form, float* w_frag, void* stream);
-long cffm_mlp_records(long NP);
 int cffm_mlp_fwd(const float* ao, const float* xt, long xt_bs, int rows_per_batch, const float* wp_f, const float* w1_f,
                  const float* w2_f, const float* bp, const float* b1, const float* b2, const float* g2, const float* be2,
                  float* x1, float* z2s, float* mean2, float* rstd2, float* hraw, float* acts, float* x2, long NP, void* stream);
 int cffm_mlp_bwd(const float* dout, const float* hraw, const float* b1, const float* x1, const float* mean2,
                  const float* rstd2, const float* g2, const float* w2_n, const float* w1_n, const float* wp_n, float* dhs,
                  float* dx1, float* dao, float* dg2, float* dbe2, float* db1, float* db2, float* dbp, long NP, void* stream);
-/* ABI 9: the same two kernels also leaving T-frag copies (cffm_tfrag_floats(NP, 256 | 1024) floats; see cffm_linear_bwd_weight_tfrag) of the
- * operands of the block's weight gradients: ao, z2, act (forward), dout, dh, dx1 (backward).  Every split-4 / T-frag output may be NULL. */
-int cffm_mlp_fwd_tfrag(const float* ao, const float* xt, long xt_bs, int rows_per_batch, const float* wp_f, const float* w1_f,
-                       const float* w2_f, const float* bp, const float* b1, const float* b2, const float* g2, const float* be2,
-                       float* x1, float* z2s, float* mean2, float* rstd2, float* hraw, float* acts, float* x2, float* ao_t, float* z2_t,
-                       float* act_t, long NP, void* stream);
-int cffm_mlp_bwd_tfrag(const float* dout, const float* hraw, const float* b1, const float* x1, const float* mean2,
-                       const float* rstd2, const float* g2, const float* w2_n, const float* w1_n, const float* wp_n, float* dhs,
-                       float* dx1, float* dao, float* dg2, float* dbe2, float* db1, float* db2, float* dbp, float* dout_t, float* dh_t,
-                       float* dx1_t, long NP, void* stream);
 int cffm_colsum(const float* a, long rows, int cols /* multiple of 4 */, float* out /* overwritten */, void* stream);
-int cffm_residual_ln(const float* xt, long xt_bs, int rows_per_batch, const float* yraw, const float* bproj,
-                     const float* gamma, const float* beta, float* x1, float* z2, float* mean, float* rstd,
-                     long nrows, void* stream);
-/* dx1 = (dres or 0) + LNbwd(dz2); dgamma/dbeta are overwritten (zero_grads != 0) or accumulated into; the column
- * sums of dres and of dx1 (the bias gradients of the Linear layers on either side) come for free: pass NULL to skip */
-int cffm_ln_bwd_residual(const float* x1, const float* mean, const float* rstd, const float* gamma, const float* dz2,
-                         const float* dres /* may be NULL */, float* dx1, float* dgamma, float* dbeta, long nrows,
-                         int zero_grads, float* dres_colsum /* [256] or NULL */, float* dx1_colsum /* [256] or NULL */,
-                         void* stream);
-int cffm_bias_gelu(const float* hraw, const float* b1, float* act, long rows, int cols, void* stream);
-int cffm_gelu_bwd(const float* hraw, const float* b1, float* dact_inout, long rows, int cols /* 1024 */,
-                  float* db1 /* [1024] column sums of the result, or NULL */, void* stream);
-int cffm_residual_out(const float* x1, const float* oraw, const float* b2, float* out, long rows, void* stream);
 
 /* ---- CFFM++ global temporal context (WindowAttention_cluster, pvt/swin_transformer_2d.py:208-262) ---- */
-int cffm_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* z, float* mean, float* rstd,
-                       long nrows, void* stream);
 /* q_raw [B*T,256] = LN(x) Wq^T without bias, kv_raw [B*K,512] = LN(centers) Wkv^T without bias; softmax over the K
  * prototypes per (token, head); o [B*T,256]; lse [B*T,8].  K <= 128: on the matrix pipe (three-pass bf16 split of every product: the
  * 1e-4 tolerance of the fp32 form is kept), the head's Kc / Vc packed once per call as MFMA fragments; above: fp32 on the VALU.  The
@@ -408,21 +364,11 @@ int cffm_rows_resize_bwd(const float* ddst, long ddst_map_stride, float* dsrc, l
  * (v - mean) * (1/std) in float32, padding of the bottom / right to Ho x Wo with pad_val (image, after normalisation) and
  * seg_pad_val (labels); out_img [T,3,Ho,Wo] float32, out_lab [T,1,Ho,Wo] int64.  The random draws stay on the host
  * (vss_cffm_amd/data.py draws them in the reference's order). */
-int cffm_clip_format(const unsigned char* frames, const unsigned char* labels, float* out_img, long long* out_lab, int T, int H, int W,
-                     int y1, int x1, int ch, int cw, int flip, int Ho, int Wo, const float mean[3], const float std[3], int to_rgb,
-                     float pad_val, int seg_pad_val, int reduce_zero_label, void* stream);
-/* the same with PhotoMetricDistortion_clips' brightness / contrast (mmseg/datasets/pipelines/transforms.py:2028-2150, convert() :2057)
- * between flip and normalisation, per frame: brightness_beta[t] / contrast_alpha[t] (HOST arrays of T floats, or NULL) -- NaN = branch
- * not taken for that frame; v = u8(clip(v + beta)), then v = u8(clip(v * alpha)) in float32 as numpy does.  (No saturation / hue:
- * cffm_clip_format_hsv.) */
-int cffm_clip_format_photo(const unsigned char* frames, const unsigned char* labels, float* out_img, long long* out_lab, int T, int H,
-                           int W, int y1, int x1, int ch, int cw, int flip, int Ho, int Wo, const float mean[3], const float std[3],
-                           int to_rgb, float pad_val, int seg_pad_val, int reduce_zero_label, const float* brightness_beta,
-                           const float* contrast_alpha, void* stream);
-/* ABI 8: the whole of PhotoMetricDistortion_clips.__call__ (transforms.py:2112-2139) per frame: brightness, contrast when
+/* The whole of PhotoMetricDistortion_clips.__call__ (mmseg/datasets/pipelines/transforms.py:2028-2150, ABI 8) between flip and
+ * normalisation, per frame: brightness (v = u8(clip(v + beta)), convert() :2057, in float32 as numpy does), contrast when
  * contrast_first[t] (the reference's mode == 1), saturation (:2082-2091: S of mmcv.bgr2hsv = cv2 COLOR_BGR2HSV scaled by saturation[t],
  * convert()-style, back through COLOR_HSV2BGR), hue (:2093-2102: H + hue_shift[t] mod 180, its own round trip), contrast when
- * !contrast_first[t].  HOST arrays of T entries or NULL; NaN = branch not taken; hue_shift holds integers.  The two colour conversions
+ * !contrast_first[t] (v = u8(clip(v * alpha))).  HOST arrays of T entries or NULL; NaN = branch not taken; hue_shift holds integers.  The two colour conversions
  * restate OpenCV's 8-bit arithmetic (color_hsv.cpp RGB2HSV_b: integer with the 12-bit division tables, hue range 180; HSV2RGB_b: float32
  * through HSV2RGB_native, * 255, cvRound) -- OpenCV is not available where this library is built or tested, so that restatement is checked
  * against oracle/cv_oracle.py only (parity unpinned). */
@@ -444,21 +390,6 @@ int cffm_clip_resize(const unsigned char* frames, const unsigned char* labels, i
  * consecutive elements of one tensor.  Decoupled weight decay, bias-corrected moments, exactly torch.optim.AdamW
  * (amsgrad off): p *= 1 - lr*wd; m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps). */
 #define CFFM_ADAMW_CHUNK 2048
-typedef struct {
-    float* p;           /* parameter values (updated in place) */
-    const float* g;     /* gradient */
-    float* m;           /* first moment (updated) */
-    float* v;           /* second moment (updated) */
-    long n;             /* 1..CFFM_ADAMW_CHUNK elements */
-} cffm_adamw_chunk;
-int cffm_adamw_step(const cffm_adamw_chunk* chunks /* device */, int nchunks, double lr, double beta1, double beta2, double eps,
-                    double weight_decay, int step /* t >= 1 */, void* stream);
-/* The same update with the step count kept ON THE DEVICE (state: 4 floats, zero-initialised by the caller: [0] = t, advanced
- * by the call, [1], [2] = the bias-correction factors derived from it), so a training step captured in a HIP graph replays
- * with the right t.  grad_base != NULL: every chunk's `g` is a byte offset from grad_base instead of a pointer (all the
- * gradients of the layer live in one buffer; its address may change between steps, the table does not). */
-int cffm_adamw_step_dev(const cffm_adamw_chunk* chunks /* device */, int nchunks, const float* grad_base, double lr, double beta1,
-                        double beta2, double eps, double weight_decay, float* state /* device [4] */, void* stream);
 /* Every parameter group of the optimizer in ONE launch (the reference's paramwise_cfg -- `head` lr_mult 10, `norm` /
  * `pos_block` decay_mult 0: local_configs/cffm/B1/cffm.b1.480x480.vspw2.160k.py:35-39 -- makes several): a chunk names the
  * ROW of the hyper-parameter tables it is updated with.  Device tables, `nrows` rows each:
@@ -474,7 +405,8 @@ int cffm_adamw_step_dev(const cffm_adamw_chunk* chunks /* device */, int nchunks
  *                              (the caller must order mirror writes against replays in flight; kind 1 needs no writes)
  *   state  [nrows][4] float : t, lr_t/(1-b1^t), 1/sqrt(1-b2^t), 1-lr_t*wd -- t advanced by the call (zero-initialise, or seed
  *                              with the step count of a resumed run)
- * grad_base as in cffm_adamw_step_dev. */
+ * grad_base != NULL: every chunk's `g` is a byte offset from grad_base instead of a pointer (all the gradients of the layer live in one
+ * buffer; its address may change between steps, the table does not). */
 #define CFFM_ADAMW_TICKETS 65
 typedef struct {
     float* p;

@@ -10,7 +10,7 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libcffm_hip.so')
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 vp, ci, cl, cd, cf = C.c_void_p, C.c_int, C.c_long, C.c_double, C.c_float
 
@@ -67,12 +67,9 @@ SIGNATURES = {
     'cffm_profile_collect_graph': (ci, [vp, vp, ci]),
     'cffm_transpose': (ci, [vp, vp, ci, ci, ci, cl, cl, vp]),
     'cffm_pool_matrix': (ci, [P4, vp, vp]),
-    'cffm_pool_matrix_bwd': (ci, [vp, P4, vp]),
     'cffm_grad_slices_padded': (None, [ci]),
     'cffm_ln_pool_fwd': (ci, [GP, vp, cl, vp, cl, vp, vp, vp, P4, vp, vp, vp, vp]),
-    'cffm_ln_pool_bwd': (ci, [GP, vp, cl, vp, cl, vp, vp, vp, vp, vp, vp, vp, vp, cl, ci, vp, cl, vp, vp, vp, P4, vp]),
     'cffm_bias_assemble': (ci, [vp, vp, P4, vp, vp, vp]),
-    'cffm_bias_scatter': (ci, [vp, vp, vp, P4, vp]),
     'cffm_linear_qkv_fwd': (ci, [vp, vp, vp, vp, cl, vp]),
     'cffm_attn_fwd': (ci, [GP, vp, vp, vp, vp, vp, vp, vp]),
     'cffm_attn_bwd': (ci, [GP, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -81,29 +78,15 @@ SIGNATURES = {
     'cffm_linear_bwd_input': (ci, [vp, vp, vp, cl, ci, ci, vp]),
     'cffm_linear_bwd_weight': (ci, [vp, vp, vp, cl, ci, ci, vp]),
     'cffm_linear_bwd_weight_group': (ci, [vp, ci, vp]),
-    'cffm_split4': (ci, [vp, vp, cl, vp]),
-    'cffm_linear_bwd_weight_split': (ci, [vp, vp, vp, cl, ci, ci, vp]),
-    'cffm_linear_bwd_weight_split_group': (ci, [vp, ci, vp]),
     'cffm_tfrag_floats': (cl, [cl, ci]),
     'cffm_dw_stream': (ci, [ci]),
     'cffm_tfrag_pack': (ci, [vp, vp, cl, ci, vp]),
     'cffm_linear_bwd_weight_tfrag': (ci, [vp, vp, vp, cl, ci, ci, vp]),
     'cffm_linear_bwd_weight_tfrag_group': (ci, [vp, ci, vp]),
-    'cffm_linear_gelu_fwd': (ci, [vp, vp, vp, vp, vp, cl, ci, ci, vp]),
-    'cffm_linear_residual_fwd': (ci, [vp, vp, vp, vp, vp, cl, ci, ci, vp]),
     'cffm_colsum': (ci, [vp, cl, ci, vp, vp]),
     'cffm_panel_pack_weight': (ci, [vp, ci, ci, ci, vp, vp]),
-    'cffm_mlp_records': (cl, [cl]),
     'cffm_mlp_fwd': (ci, [vp, vp, cl, ci] + [vp] * 15 + [cl, vp]),
     'cffm_mlp_bwd': (ci, [vp] * 18 + [cl, vp]),
-    'cffm_mlp_fwd_tfrag': (ci, [vp, vp, cl, ci] + [vp] * 18 + [cl, vp]),
-    'cffm_mlp_bwd_tfrag': (ci, [vp] * 21 + [cl, vp]),
-    'cffm_residual_ln': (ci, [vp, cl, ci, vp, vp, vp, vp, vp, vp, vp, vp, cl, vp]),
-    'cffm_ln_bwd_residual': (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, cl, ci, vp, vp, vp]),
-    'cffm_layernorm_fwd': (ci, [vp, vp, vp, vp, vp, vp, cl, vp]),
-    'cffm_bias_gelu': (ci, [vp, vp, vp, cl, ci, vp]),
-    'cffm_gelu_bwd': (ci, [vp, vp, vp, cl, ci, vp, vp]),
-    'cffm_residual_out': (ci, [vp, vp, vp, vp, cl, vp]),
     'cffm_block_forward': (ci, [GP, BP, vp, cl, vp, cl, vp, vp, vp, vp, vp]),
     'cffm_block_backward': (ci, [GP, BP, BP, vp, cl, vp, cl, vp, vp, vp, vp, vp, vp, vp, cl, ci, vp, cl, vp, vp]),
     'cffm_layer_forward': (ci, [GP, ci, BP, vp, vp, vp, vp, vp, vp, vp]),
@@ -132,8 +115,6 @@ SIGNATURES = {
     'cffm_bn_finalize_bwd': (ci, [vp, cl, cd, vp, vp, ci, vp, vp]),
     'cffm_rows_resize_fwd': (ci, [vp, cl, vp, cl, ci, ci, ci, ci, ci, ci, vp]),
     'cffm_rows_resize_bwd': (ci, [vp, cl, vp, cl, ci, ci, ci, ci, ci, ci, vp]),
-    'cffm_clip_format': (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.c_float * 3, C.c_float * 3, ci, C.c_float, ci, ci, vp]),
-    'cffm_clip_format_photo': (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.c_float * 3, C.c_float * 3, ci, C.c_float, ci, ci, vp, vp, vp]),
     'cffm_clip_format_hsv': (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.c_float * 3, C.c_float * 3, ci, C.c_float, ci, ci, vp, vp, vp, vp, vp, vp]),
     'cffm_clip_resize': (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, vp]),
     'cffm_upce_blocks': (cl, [ci, ci, ci]),
@@ -142,8 +123,6 @@ SIGNATURES = {
     'cffm_upce_maps_finalize': (ci, [vp, ci, cl, vp, vp, vp, vp]),
     'cffm_upce_maps_fwd': (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cl, cl, ci, ci, vp]),
     'cffm_upce_maps_bwd': (ci, [vp, vp, vp, vp, vp, vp, C.c_float, vp, ci, ci, ci, ci, ci, ci, ci, ci, cl, cl, ci, ci, vp]),
-    'cffm_adamw_step': (ci, [vp, ci, cd, cd, cd, cd, cd, ci, vp]),
-    'cffm_adamw_step_dev': (ci, [vp, ci, vp, cd, cd, cd, cd, cd, vp, vp]),
     'cffm_adamw_step_rows': (ci, [vp, ci, vp, vp, vp, vp, ci, vp, vp, vp]),
 }
 

@@ -73,13 +73,6 @@ __global__ void __launch_bounds__(256) k_transpose(const float* __restrict__ src
     transpose_body(src, dst, rows, cols, src_bs, dst_bs, addend, add_mod, add_skip, copy_dst, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
-// dst[z][0..n4) = src[z][0..n4) (16-byte units, batch strides in floats): the pass-through frames of the layer output
-__global__ void __launch_bounds__(256) k_copy_batched(const float* __restrict__ src, float* __restrict__ dst, long n4, long src_bs, long dst_bs) {
-    const f32x4* s = (const f32x4*)(src + (long)blockIdx.y * src_bs);
-    f32x4* d = (f32x4*)(dst + (long)blockIdx.y * dst_bs);
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) d[i] = s[i];
-}
-
 // --------------------------------------------------------------------------- pooling matrix
 // Cell g of a window is a fixed linear functional of the window's 49 LayerNormed pixels
 // (SURVEY.md A.6 "window-locality"): g=0 target pool, g=1 frame t-9 (7x7 pool), g=2..5 frame t-6
@@ -101,7 +94,7 @@ __device__ __forceinline__ void cell_geom(int g, int& grp, int& u, int& v, int& 
 }
 
 struct PoolW { const float* w[4]; };  // pool_layers.0, pool_layers_clips.{0,1,2} weights
-struct PoolWG { float* w[4]; float* b[4]; };   // b: the four pool-bias gradients, or NULL (see k_pool_matrix_bwd: padding of flat gradient buffers)
+struct PoolWG { float* w[4]; float* b[4]; };   // b: the four pool-bias gradients, or NULL (see pool_matrix_bwd_body: padding of flat gradient buffers)
 
 // entry (cell g, window pixel i) of the pooling matrix
 __device__ __forceinline__ float pool_matrix_entry(const PoolW& pw, int g, int i) {
@@ -153,8 +146,7 @@ __device__ __forceinline__ void pool_matrix_bwd_body(const float* __restrict__ d
         for (int q = 0; q < 4; ++q) gw.b[q][1 + i] = 0.f;
     }
 }
-__global__ void __launch_bounds__(64) k_pool_matrix_bwd(const float* __restrict__ dM, PoolWG gw) { pool_matrix_bwd_body(dM, gw, blockIdx.x); }
-// the same for up to PMB_MAXD blocks in one launch (grid (111, n)): the end of a layer backward
+// up to PMB_MAXD blocks in one launch (grid (111, n)): the end of a layer backward
 #define PMB_MAXD 4
 struct PoolWGN { const float* dM[PMB_MAXD]; PoolWG gw[PMB_MAXD]; };
 __global__ void __launch_bounds__(64) k_pool_matrix_bwd_n(PoolWGN a) { pool_matrix_bwd_body(a.dM[blockIdx.y], a.gw[blockIdx.y], blockIdx.x); }
@@ -462,7 +454,7 @@ __device__ __forceinline__ void ln_pool_bwd_ref_frame(const Geo& G, const RefRow
         // resized rows wsg u .. wsg u + wsg - 1, a resized row r taps pixel rows r and r + 1 (bil_tap), so pixel row iy reaches the cells
         // u = r / wsg of r in {iy - 1, iy} ^ [0, 5]: one or two per dimension -- on average 1.65 of the 9 cells of frame t-3 and 1.3 of
         // the 4 of frame t-6.  Everywhere else M[c][i] is an exact zero: no share in dz, and the dM entry is one that the pooling-matrix
-        // backward multiplies by a zero tap (k_pool_matrix_bwd) -- it stays 0.  (Round 5, second form: all NC cells per pixel cost
+        // backward multiplies by a zero tap (k_pool_matrix_bwd_n) -- it stays 0.  (Round 5, second form: all NC cells per pixel cost
         // 14 dot products + wave reductions per block and pixel triple, 48 us for the launch.)
         constexpr int NCD = NC == 9 ? 3 : (NC == 4 ? 2 : 1), WSG = NC == 9 ? 2 : (NC == 4 ? 3 : 7);
         const int iy = i / 7, ix = i % 7;

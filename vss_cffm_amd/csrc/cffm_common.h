@@ -7,16 +7,7 @@
 #endif
 #include <stdint.h>
 
-// Tuning switches (launch shapes, stream forks, rejected forms kept for A/B runs) are read from the environment only in
-// -DCFFM_EXPERIMENTS builds (scripts/): the product library is built without it, and there every switch IS its default -- what
-// bench.py and the -m gpu tests run is the only configuration libcffm_hip.so has.  (The one exception is documented where it is read:
-// CFFM_DW_GROUP, the two legitimate forms of the weight-gradient groups, both covered by tests.)
 #include <stdlib.h>
-#ifdef CFFM_EXPERIMENTS
-static inline const char* cffm_tune(const char* name) { return getenv(name); }
-#else
-static inline const char* cffm_tune(const char*) { return nullptr; }
-#endif
 
 // ---- fixed problem constants of the reference head (cffm_head.py:74-95) ------------------------
 #define CFFM_C 256         // embed_dim of every CFFM config
@@ -53,12 +44,8 @@ typedef f16 f16x8 __attribute__((ext_vector_type(8)));
     emu::launch(dim3 grid, dim3 block, (shmem), [=]() { kernel(__VA_ARGS__); })
 #else
 #define CFFM_DYN_SMEM(name) extern __shared__ __attribute__((aligned(16))) char name[]
-#ifdef CFFM_NULL_LAUNCH   // profiling builds only: no kernel is launched (host-side cost of a step without the device work)
-#define CFFM_LAUNCH(kernel, grid, block, shmem, stream, ...) (void)0
-#else
 #define CFFM_LAUNCH(kernel, grid, block, shmem, stream, ...) \
     hipLaunchKernelGGL(kernel, dim3 grid, dim3 block, (shmem), (stream), __VA_ARGS__)
-#endif
 #endif
 
 // ---- wave (64 lanes) reductions ------------------------------------------------------------------

@@ -14,16 +14,6 @@
 
 #include "../../include/cffm_hip.h"
 
-// A boolean / integer tuning switch: a constant in the product build, an environment variable in -DCFFM_EXPERIMENTS builds (see
-// cffm_tune in cffm_common.h).  The alternative legs these switches select are dead code the compiler removes from libcffm_hip.so.
-#ifdef CFFM_EXPERIMENTS
-#define CFFM_SWITCH(fn, env, dflt) static int fn() { static int v = -(1 << 30); if (v == -(1 << 30)) { const char* e = getenv(env); v = e ? atoi(e) : (dflt); } return v; }
-#define constexpr_or_not
-#else
-#define CFFM_SWITCH(fn, env, dflt) static constexpr int fn() { return (dflt); }
-#define constexpr_or_not constexpr
-#endif
-
 static thread_local char g_err[512] = "";
 
 static int fail(int code, const char* fmt, ...) {
@@ -358,14 +348,13 @@ static float* lib_scratch3(size_t nfloats) {
 // back to back) that truly overlap with the chain's kernels; the GEMMs need the whole chip and overlap only partly.
 // All of it is issued on a library-owned second stream, forked from / joined to the caller's stream with events:
 // launched eagerly the two streams overlap on the device; captured into a HIP graph (bench.py) the fork becomes a parallel
-// branch of the graph.  CFFM_SIDE_STREAM=0 keeps everything on the caller's stream (A/B measurement, debugging).
+// branch of the graph.  cffm_side_streams(0) keeps everything on the caller's stream (per-kernel timing).
 struct SideStream {
     bool on = false;
-    int ns = 1;                 // side streams in use (CFFM_SIDE_STREAMS = 1 | 2 | 4): with two, branches 0 / 2 (the GEMM-sized work) and
-                                // 1 / 3 (the small kernels) do not queue behind each other
+    int ns = 1;                 // side streams in use: 1 launched eagerly, 4 under stream capture and for the caller's branches
 #ifndef CFFM_EMU
     hipStream_t st[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t fork[4] = {nullptr, nullptr, nullptr, nullptr}, join[2] = {nullptr, nullptr}, order = nullptr, tail_order = nullptr, cs_order = nullptr;
+    hipEvent_t fork[4] = {nullptr, nullptr, nullptr, nullptr}, join[2] = {nullptr, nullptr}, order = nullptr, tail_order = nullptr;
     // deferred join of a block backward (layer_backward_impl): what the NEXT block has to wait for
     hipEvent_t dw_done[2] = {nullptr, nullptr}, bias_done[2] = {nullptr, nullptr}, tail_done[2] = {nullptr, nullptr}, join_all[4] = {nullptr, nullptr, nullptr, nullptr};
     bool bias_pending[2] = {false, false}, dw_pending[2] = {false, false}, tail_pending[2] = {false, false};
@@ -403,25 +392,16 @@ static int stream_is_capturing(hipStream_t st) {
 // `main`: the caller's stream.  Launched eagerly ONE side stream measured best (0.877 vs 0.929 ms per step with two); under stream
 // capture more (two: 0.882-0.895 vs 0.902-0.906 replayed: branches that do not queue behind each other give the graph executor more
 // to run side by side; FOUR -- every branch of a block backward on its own stream -- another 0.8 %: 0.8894 vs 0.8963 as means of five
-// alternating runs).  CFFM_SIDE_STREAMS=1|2|4 forces a count.
+// alternating runs).
 static bool side_init(hipStream_t main) {
-    static int state = -1, forced_ns = 0;
+    static int state = -1;
     if (state < 0) {
         state = 0;
 #ifndef CFFM_EMU
-        const char* e = cffm_tune("CFFM_SIDE_STREAM");
-        const char* n = cffm_tune("CFFM_SIDE_STREAMS");
-        forced_ns = !n ? 0 : (n[0] == '1' ? 1 : (n[0] == '4' ? 4 : 2));
-        // CFFM_SIDE_PRIO=low: the side streams get the lowest stream priority (parameter-gradient work yields to the chain's kernels
-        // when both have workgroups ready)
-        int lo = 0, hi = 0;
-        const char* pr = cffm_tune("CFFM_SIDE_PRIO");
-        const bool low = pr && pr[0] == 'l' && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess;
-        auto mk = [&](hipStream_t* st_) { return (low ? hipStreamCreateWithPriority(st_, hipStreamNonBlocking, lo) : hipStreamCreateWithFlags(st_, hipStreamNonBlocking)) == hipSuccess; };
-        if (!(e && e[0] == '0') && mk(&g_side.st[0]) && mk(&g_side.st[1]) && mk(&g_side.st[2]) && mk(&g_side.st[3])) {
+        auto mk = [](hipStream_t* st_) { return hipStreamCreateWithFlags(st_, hipStreamNonBlocking) == hipSuccess; };
+        if (mk(&g_side.st[0]) && mk(&g_side.st[1]) && mk(&g_side.st[2]) && mk(&g_side.st[3])) {
             bool ok = hipEventCreateWithFlags(&g_side.order, hipEventDisableTiming) == hipSuccess &&
-                      hipEventCreateWithFlags(&g_side.tail_order, hipEventDisableTiming) == hipSuccess &&
-                      hipEventCreateWithFlags(&g_side.cs_order, hipEventDisableTiming) == hipSuccess;
+                      hipEventCreateWithFlags(&g_side.tail_order, hipEventDisableTiming) == hipSuccess;
             for (int i = 0; i < 4; ++i) ok = ok && hipEventCreateWithFlags(&g_side.fork[i], hipEventDisableTiming) == hipSuccess;
             for (int i = 0; i < 2; ++i) ok = ok && hipEventCreateWithFlags(&g_side.join[i], hipEventDisableTiming) == hipSuccess;
             for (int i = 0; i < 2; ++i) ok = ok && hipEventCreateWithFlags(&g_side.tail_done[i], hipEventDisableTiming) == hipSuccess;
@@ -434,31 +414,30 @@ static bool side_init(hipStream_t main) {
 #endif
     }
     g_side.on = state == 1 && !g_side_off;
-    g_side.ns = forced_ns ? forced_ns : (stream_is_capturing(main) ? 4 : 1);
+    g_side.ns = stream_is_capturing(main) ? 4 : 1;
     return g_side.on;
 }
 // the stream branch `i` (0 / 1) of the side work runs on, ordered after everything issued on `main` so far
-// How the four weight-gradient GEMMs of a block backward are issued.  `one`: ONE grouped launch late in the block (59 us of GEMM +
-// sum); `split`: two groups of two, each forked to the side stream as early as its operands allow (2 x 53 us, but off the chain
-// sooner).  Launched eagerly the side stream really runs beside the chain and `split` wins (0.886 vs 0.911 ms per step); a replayed
-// HIP graph executes its branches almost serially, so there the cheaper `one` wins (0.927 vs 0.950).  Default: by whether the
-// caller's stream is being captured; CFFM_DW_GROUP=one|split forces a form.
-// How the side work of a block backward is attached to the chain (bit mask; default 38 = 2 | 4 | 32, the rest for A/B measurements).
-// Under stream capture the graph executor (ROCm 7.2) gives a node's FIRST-captured dependant the node's own stream and every further
-// dependant the next of its (four) streams, depth first -- so whatever is launched first behind a fork stays on the chain's stream,
-// and side branches that reach the same stream number run one after the other in topological order.  The chain must therefore be
-// launched first at every fork and must never wait for a side branch inside the step:
-//   bit 0  the dK/dV gather is launched before the bias-tile sum of the attention backward
-//   bit 1  the q|k|v input-gradient GEMM is launched before the column sum / weight-gradient group
-//   bit 2  the bias-tile sum + scatter get no branch of their own: they follow the weight-gradient group on its stream
-//   bit 5  the record reductions + pooling-matrix backward are launched only after the NEXT chain kernel (tail_flush)
-// Measured (B = 2, depth 2, replayed graph, same box): 0 -> 0.830-0.833 ms per step, 4 -> 0.808-0.810, 38 (with the two scratch sets
+// How the side work of a block backward is attached to the chain.  Under stream capture the graph executor (ROCm 7.2) gives a node's
+// FIRST-captured dependant the node's own stream and every further dependant the next of its (four) streams, depth first -- so whatever
+// is launched first behind a fork stays on the chain's stream, and side branches that reach the same stream number run one after the
+// other in topological order.  The chain must therefore be launched first at every fork and must never wait for a side branch inside
+// the step.  block_backward_impl
+//   launches the q|k|v input-gradient GEMM before the weight-gradient group,
+//   gives the bias-tile sum + scatter no branch of their own: they follow the weight-gradient group on its stream,
+//   launches the record reductions + pooling-matrix backward only after the NEXT chain kernel (tail_flush).
+// Measured as a bit mask of forms (bits 1 / 2 / 5: the three choices above; bit 0: the dK/dV gather launched before a forked bias-tile
+// sum) on B = 2, depth 2, replayed graph, same box: 0 -> 0.830-0.833 ms per step, 4 -> 0.808-0.810, 38 (with the two scratch sets
 // of scratch_layout, so that no block waits for the previous block's weight gradients) -> 0.798-0.811 against 0.821-0.848 for 4;
 // 35 (the bias-tile sum early again, now that every side branch lands on the same graph stream in launch order: it runs in the idle
 // stretch beside the gather instead of behind the weight gradients on the step's tail) -> 0.773-0.785 against 0.783-0.786 for 38; with
 // the last block's tail on the caller's stream and the L2 warm-up of the fused kernels 38 is ahead again (one fork less on the chain:
 // a node with a dependant on another stream costs its same-stream successor ~5 us): 0.724-0.728 against 0.732-0.737 for 35.
-CFFM_SWITCH(fork_order, "CFFM_FORK_ORDER", 38)
+// How the four weight-gradient GEMMs of a block backward are issued.  `one`: ONE grouped launch late in the block (59 us of GEMM +
+// sum); `split`: two groups of two, each forked to the side stream as early as its operands allow (2 x 53 us, but off the chain
+// sooner).  Launched eagerly the side stream really runs beside the chain and `split` wins (0.886 vs 0.911 ms per step); a replayed
+// HIP graph executes its branches almost serially, so there the cheaper `one` wins (0.927 vs 0.950).  Default: by whether the
+// caller's stream is being captured; CFFM_DW_GROUP=one|split forces a form.
 static int dw_one_group(hipStream_t st) {
     static int forced = -2;
     if (forced == -2) { const char* e = getenv("CFFM_DW_GROUP"); forced = !e ? -1 : (e[0] == 's' ? 0 : 1); }
@@ -483,7 +462,7 @@ static void side_fork_mark(hipStream_t main, int i) {
 }
 static hipStream_t side_fork_take(hipStream_t main, int i) {
 #ifndef CFFM_EMU
-    const int idx = g_side.ns >= 4 ? (i & 3) : (g_side.ns > 1 ? (i & 1) : 0);
+    const int idx = g_side.ns >= 4 ? (i & 3) : 0;
     hipStream_t s = g_side.st[idx];
     if (g_side.on && hipStreamWaitEvent(s, g_side.fork[i], 0) == hipSuccess) {
         g_side.used |= 1u << idx;
@@ -496,7 +475,7 @@ static hipStream_t side_fork_take(hipStream_t main, int i) {
 }
 static hipStream_t side_fork(hipStream_t main, int i) {
 #ifndef CFFM_EMU
-    const int idx = g_side.ns >= 4 ? (i & 3) : (g_side.ns > 1 ? (i & 1) : 0);
+    const int idx = g_side.ns >= 4 ? (i & 3) : 0;
     hipStream_t s = g_side.st[idx];
     if (g_side.on && hipEventRecord(g_side.fork[i], main) == hipSuccess && hipStreamWaitEvent(s, g_side.fork[i], 0) == hipSuccess) {
         g_side.used |= 1u << idx;
@@ -759,15 +738,6 @@ int cffm_pool_matrix(const float* const pool_w[4], float* M, void* stream) {
 
 static thread_local int g_grad_pads = 0;   // per calling thread (autograd runs one backward thread per device: ADVICE r4)
 void cffm_grad_slices_padded(int yes) { g_grad_pads = yes ? 1 : 0; }
-static int pool_matrix_bwd_impl(const float* dM, float* const dpool_w[4], float* const dpool_b[4], void* stream) {
-    PROF(ST_POOLMAT);
-    PoolWG gw;
-    for (int i = 0; i < 4; ++i) { gw.w[i] = dpool_w[i]; gw.b[i] = dpool_b ? dpool_b[i] : nullptr; }
-    CFFM_LAUNCH(k_pool_matrix_bwd, (111), (64), 0, (hipStream_t)stream, dM, gw);
-    CHECK_LAUNCH("pool_matrix_bwd");
-    return 0;
-}
-int cffm_pool_matrix_bwd(const float* dM, float* const dpool_w[4], void* stream) { return pool_matrix_bwd_impl(dM, dpool_w, nullptr, stream); }
 
 // `split`: the rows a GEMM is the only reader of are written in split-4 storage (cffm_common.h); the public stage
 // functions always write plain fp32, the block orchestration asks for split-4 when the hand-written GEMMs are in use
@@ -859,29 +829,6 @@ static void cffa_jobs(RedJobs& J, const float* rec, long rows, float* dgamma, fl
     job_add(J, rec + rows * LNP_RSTRIDE + 2 * CFFM_C, (int)rows, LNP_RSTRIDE, LNP_TAIL_REF, c, st);
 }
 
-int cffm_ln_pool_bwd(const cffm_geom* g, const float* x_ref, long ref_bs, const float* x_tgt, long tgt_bs,
-                     const float* gamma, const float* beta, const float* M, const float* mean, const float* rstd,
-                     const float* dzall, const float* dres, float* dx_ref, long dref_bs, int accum_ref,
-                     float* dx_tgt, long dtgt_bs, float* dgamma, float* dbeta, float* dM, float* const dpool_b[4],
-                     void* stream) {
-    REQUIRE(g && x_ref && x_tgt && gamma && beta && M && mean && rstd && dzall && dx_ref && dx_tgt && dgamma && dbeta && dM && dpool_b, "ln_pool_bwd: null");
-    hipStream_t st = (hipStream_t)stream;
-    const long rows = cffa_rows(g);
-    float* rec = red_scratch((size_t)2 * rows * LNP_RSTRIDE, st);
-    REQUIRE(rec, "ln_pool_bwd: scratch allocation failed");
-    TRY(ln_pool_bwd_tgt(g, x_tgt, tgt_bs, gamma, beta, M, mean, rstd, dzall, dres, dx_tgt, dtgt_bs, rec, stream));
-    CffaRefBlocks Bk;
-    Bk.n = 1;
-    for (int d = 0; d < RB_MAXD; ++d) { Bk.gamma[d] = gamma; Bk.beta[d] = beta; Bk.M[d] = M; Bk.dzall[d] = dzall; Bk.rec[d] = rec + rows * LNP_RSTRIDE; }
-    TRY(ln_pool_bwd_ref(g, x_ref, ref_bs, Bk, mean, rstd, dx_ref, dref_bs, accum_ref, stream));
-    RedJobs J;
-    J.njob = 0;
-    cffa_jobs(J, rec, rows, dgamma, dbeta, dM, dpool_b, st);
-    redq_launch(J, st);
-    CHECK_LAUNCH("ln_pool_bwd");
-    return 0;
-}
-
 // Library-owned state of the CFFA backward, one SLOT per block of the layer: the block's token-row gradient dzall (written by the q|k|v
 // input-gradient GEMM, its pooled-cell rows are read again by the reference pass at the end of the range), the records of its target
 // and reference workgroups, its pooling-matrix gradient.
@@ -971,7 +918,7 @@ int cffm_bias_assemble(const float* own, const float* ring, const float* const p
     return 0;
 }
 
-int cffm_bias_scatter(const float* dbiasT, float* down, float* dring, float* const dpool[4], void* stream) {
+static int cffm_bias_scatter(const float* dbiasT, float* down, float* dring, float* const dpool[4], void* stream) {
     PROF(ST_BIAS_SCT);
     BiasTablesG t;
     t.own = down; t.ring = dring;
@@ -996,9 +943,7 @@ int cffm_attn_fwd(const cffm_geom* g, const void* qkv16, const int* key_src, con
 // window groups of the fused backward: 8 heads x groups <= one 12-wave workgroup per CU on 256 CUs, every group the same length
 static int attn_bwd_groups(const cffm_geom* g, int* per_group) {
     const int total = g->B * g->nW;
-    static int want = -1;   // tuning aid: CFFM_BWD_GROUPS
-    if (want < 0) { const char* e = cffm_tune("CFFM_BWD_GROUPS"); want = e ? atoi(e) : 32; if (want < 1) want = 32; }
-    int ng = total < want ? total : want;
+    const int ng = total < 32 ? total : 32;
     *per_group = (total + ng - 1) / ng;
     return (total + *per_group - 1) / *per_group;
 }
@@ -1086,38 +1031,6 @@ int cffm_linear_bwd_weight_group(const cffm_wgrad* problems, int n, void* stream
     return 0;
 }
 
-// plain fp32 -> split-4 storage (16 bytes = {bf16 hi x4 | bf16 lo x4} of four consecutive floats, cffm_common.h): what the operands of
-// cffm_linear_bwd_weight_split are stored as.  n: floats, a multiple of 4
-int cffm_split4(const float* src, float* dst, long n, void* stream) {
-    REQUIRE(src && dst && n >= 0 && n % 4 == 0, "split4: n must be a multiple of 4");
-    if (!n) return 0;
-    CFFM_LAUNCH(k_split4, (ew_grid(n / 4)), (256), 0, (hipStream_t)stream, src, dst, n / 4);
-    CHECK_LAUNCH("split4");
-    return 0;
-}
-// dw[N,K] = dy[M,N]^T x[M,K] with dy and x in split-4 storage: the LDS-DMA weight-gradient kernel of the block backward (dw_kernels.h) as
-// a stage.  N, K multiples of 128
-int cffm_linear_bwd_weight_split_group(const cffm_wgrad* problems, int n, void* stream) {
-    REQUIRE(problems && n >= 1 && n <= DWD_MAX, "linear_bwd_weight_split_group: 1..%d problems", DWD_MAX);
-    for (int i = 0; i < n; ++i)
-        REQUIRE(problems[i].dy && problems[i].x && problems[i].dw && problems[i].M >= 1 && problems[i].N % 128 == 0 && problems[i].K % 128 == 0 &&
-                problems[i].N >= 128 && problems[i].K >= 128, "linear_bwd_weight_split_group: N, K must be multiples of 128");
-    PROF(ST_GEMM);
-    int klen;
-    static int wgs = -1;      // tuning aid (experiment builds): CFFM_DWD_WGS
-    if (wgs < 0) { const char* e = cffm_tune("CFFM_DWD_WGS"); wgs = e ? atoi(e) : 480; if (wgs < 1) wgs = 480; }
-    const size_t need = dw_dma_partial_floats((const GemmTN*)problems, n, wgs, &klen);
-    float* part = need ? lib_scratch(need) : nullptr;
-    REQUIRE(!need || part, "linear_bwd_weight_split_group: scratch allocation failed");
-    REQUIRE(!dw_group_dma((const GemmTN*)problems, n, (hipStream_t)stream, part, wgs), "linear_bwd_weight_split_group: launch failed");
-    CHECK_LAUNCH("linear_bwd_weight_split_group");
-    return 0;
-}
-int cffm_linear_bwd_weight_split(const float* dy_s, const float* x_s, float* dw, long M, int N, int K, void* stream) {
-    const cffm_wgrad pr = {dy_s, x_s, dw, M, N, K};
-    return cffm_linear_bwd_weight_split_group(&pr, 1, stream);
-}
-
 // row-major fp32 x[R][C] -> T-frag storage (dws_kernels.h: MFMA fragments along the contraction, bf16 hi | lo, rows padded to a multiple of
 // 32 with zeros): what the operands of cffm_linear_bwd_weight_tfrag are stored as.  dst: cffm_tfrag_floats(R, C) floats.  A utility: inside
 // the block the row-panel kernels leave their operands in this order themselves.
@@ -1155,19 +1068,6 @@ int cffm_linear_qkv_fwd(const float* x, const float* w, const float* b, void* qk
     return gemm_nt_qkv16_split(x, w, b, (h16*)qkv16, M, 768, CFFM_C, (hipStream_t)stream) ? fail(-3, "linear_qkv_fwd: gemm failed") : 0;
 }
 
-// fused Mlp halves (one launch each)
-int cffm_linear_gelu_fwd(const float* x, const float* w, const float* b, float* hraw, float* act, long M, int N, int K, void* stream) {
-    PROF(ST_GEMM);
-    REQUIRE(N % 4 == 0, "linear_gelu_fwd: N %% 4");
-    return gemm_nt_gelu_split(x, w, b, hraw, act, M, N, K, (hipStream_t)stream) ? fail(-3, "linear_gelu_fwd: gemm failed") : 0;
-}
-int cffm_linear_residual_fwd(const float* x, const float* w, const float* b, const float* res, float* out, long M, int N, int K,
-                             void* stream) {
-    PROF(ST_GEMM);
-    REQUIRE(N % 4 == 0, "linear_residual_fwd: N %% 4");
-    return gemm_nt_residual_split(x, w, b, res, out, M, N, K, (hipStream_t)stream) ? fail(-3, "linear_residual_fwd: gemm failed") : 0;
-}
-
 int cffm_colsum(const float* a, long rows, int cols, float* out, void* stream) {
     ScratchFor pool(stream);
     PROF(ST_COLSUM);
@@ -1185,24 +1085,11 @@ int cffm_colsum(const float* a, long rows, int cols, float* out, void* stream) {
     return 0;
 }
 
-static int residual_ln_impl(const float* xt, long xt_bs, int rows_per_batch, const float* yraw, const float* bproj,
-                            const float* gamma, const float* beta, float* x1, float* z2, float* mean, float* rstd,
-                            long nrows, int split, void* stream) {
-    PROF(ST_RES_LN);
-    CFFM_LAUNCH(k_residual_ln, ((unsigned)((nrows + 3) / 4)), (256), 0, (hipStream_t)stream, xt, xt_bs, rows_per_batch, yraw, bproj,
-                gamma, beta, x1, z2, mean, rstd, nrows, split);
-    CHECK_LAUNCH("residual_ln");
-    return 0;
-}
-int cffm_residual_ln(const float* xt, long xt_bs, int rows_per_batch, const float* yraw, const float* bproj,
-                     const float* gamma, const float* beta, float* x1, float* z2, float* mean, float* rstd,
-                     long nrows, void* stream) {
-    return residual_ln_impl(xt, xt_bs, rows_per_batch, yraw, bproj, gamma, beta, x1, z2, mean, rstd, nrows, 0, stream);
-}
-
-int cffm_ln_bwd_residual(const float* x1, const float* mean, const float* rstd, const float* gamma, const float* dz2,
-                         const float* dres, float* dx1, float* dgamma, float* dbeta, long nrows, int zero_grads,
-                         float* dres_colsum, float* dx1_colsum, void* stream) {
+// dx1 = (dres or 0) + LNbwd(dz2); dgamma / dbeta overwritten (zero_grads != 0) or accumulated into; the column sums of dres and of dx1
+// (the bias gradients of the Linear layers on either side, or NULL) come for free
+static int cffm_ln_bwd_residual(const float* x1, const float* mean, const float* rstd, const float* gamma, const float* dz2,
+                                const float* dres, float* dx1, float* dgamma, float* dbeta, long nrows, int zero_grads,
+                                float* dres_colsum, float* dx1_colsum, void* stream) {
     PROF(ST_LN_BWD);
     hipStream_t st = (hipStream_t)stream;
     const int rpb = LNB_ROWS;
@@ -1222,74 +1109,7 @@ int cffm_ln_bwd_residual(const float* x1, const float* mean, const float* rstd, 
 }
 
 
-int cffm_bias_gelu(const float* hraw, const float* b1, float* act, long rows, int cols, void* stream) {
-    PROF(ST_GELU);
-    REQUIRE(cols % 4 == 0, "bias_gelu: cols %% 4");
-    const long n4 = rows * cols / 4;
-    CFFM_LAUNCH(k_bias_gelu, (ew_grid(n4)), (256), 0, (hipStream_t)stream, hraw, b1, act, n4, cols / 4);
-    CHECK_LAUNCH("bias_gelu");
-    return 0;
-}
-static int gelu_bwd_impl(const float* hraw, const float* b1, float* dact, long rows, int cols, float* db1, int split, void* stream) {
-    PROF(ST_GELU_BWD);
-    hipStream_t st = (hipStream_t)stream;
-    REQUIRE(cols == CFFM_HID, "gelu_bwd: cols must be %d", CFFM_HID);
-    const int rpb = GELU_BWD_ROWS;
-    const int nblk = (int)((rows + rpb - 1) / rpb);
-    float* part = nullptr;
-    if (db1) {
-        part = red_scratch((size_t)nblk * CFFM_HID, st);
-        REQUIRE(part, "gelu_bwd: scratch allocation failed");
-    }
-    CFFM_LAUNCH(k_gelu_bwd, (nblk), (256), 0, st, hraw, b1, dact, part, rows, split);
-    if (db1) {
-        RedSegs segs;
-        segs.nseg = 0;
-        seg_add(segs, 0, CFFM_HID, db1, 0);
-        reduce_records(part, nblk, CFFM_HID, CFFM_HID, segs, st);
-    }
-    CHECK_LAUNCH("gelu_bwd");
-    return 0;
-}
-int cffm_gelu_bwd(const float* hraw, const float* b1, float* dact, long rows, int cols, float* db1, void* stream) {
-    return gelu_bwd_impl(hraw, b1, dact, rows, cols, db1, 0, stream);
-}
-int cffm_residual_out(const float* x1, const float* oraw, const float* b2, float* out, long rows, void* stream) {
-    PROF(ST_RES_OUT);
-    const long n4 = rows * CFFM_C / 4;
-    CFFM_LAUNCH(k_residual_out, (ew_grid(n4)), (256), 0, (hipStream_t)stream, x1, oraw, b2, out, n4);
-    CHECK_LAUNCH("residual_out");
-    return 0;
-}
-
-
 // ------------------------------------------------------------------------------------------- optimizer
-int cffm_adamw_step(const cffm_adamw_chunk* chunks, int nchunks, double lr, double beta1, double beta2, double eps, double weight_decay,
-                    int step, void* stream) {
-    static_assert(sizeof(cffm_adamw_chunk) == sizeof(AdamwChunk), "chunk layout");
-    if (nchunks <= 0) return 0;
-    REQUIRE(step >= 1, "adamw: step must be >= 1, got %d", step);
-    PROF(ST_ADAMW);
-    const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);
-    CFFM_LAUNCH(k_adamw, ((unsigned)nchunks), (256), 0, (hipStream_t)stream, (const AdamwChunk*)chunks, (float)(1.0 - lr * weight_decay), (float)beta1,
-                (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)(lr / bc1), (float)(1.0 / sqrt(bc2)));
-    CHECK_LAUNCH("adamw");
-    return 0;
-}
-
-int cffm_adamw_step_dev(const cffm_adamw_chunk* chunks, int nchunks, const float* grad_base, double lr, double beta1, double beta2,
-                        double eps, double weight_decay, float* state, void* stream) {
-    if (nchunks <= 0) return 0;
-    REQUIRE(chunks && state, "adamw_step_dev: null");
-    PROF(ST_ADAMW);
-    CFFM_LAUNCH(k_adamw_tick, (1), (1), 0, (hipStream_t)stream, state, lr, beta1, beta2);
-    CFFM_LAUNCH(k_adamw_dev, ((unsigned)nchunks), (256), 0, (hipStream_t)stream, (const AdamwChunk*)chunks, grad_base,
-                (float)(1.0 - lr * weight_decay), (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps,
-                (const float*)state);
-    CHECK_LAUNCH("adamw_dev");
-    return 0;
-}
-
 int cffm_adamw_step_rows(const cffm_adamw_chunk2* chunks, int nchunks, const float* grad_base, float* state, const float* sched,
                          double* consts, int nrows, const int* active_rows, int* ticket, void* stream) {
     static_assert(sizeof(cffm_adamw_chunk2) == sizeof(AdamwChunk2), "chunk layout");
@@ -1308,16 +1128,7 @@ int cffm_adamw_step_rows(const cffm_adamw_chunk2* chunks, int nchunks, const flo
 }
 
 // ------------------------------------------------------------------------------------------- CFFM++ (GTC) stages
-int cffm_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* z, float* mean, float* rstd,
-                       long nrows, void* stream) {
-    PROF(ST_LN);
-    CFFM_LAUNCH(k_layernorm, ((unsigned)((nrows + 3) / 4)), (256), 0, (hipStream_t)stream, x, gamma, beta, z, mean, rstd, nrows, 0);
-    CHECK_LAUNCH("layernorm_fwd");
-    return 0;
-}
-
-// the prototype attention on the matrix pipe for K <= 128 (gtc_kernels.h).  CFFM_GTC_MFMA=0 (experiment builds): the VALU kernels for every K
-CFFM_SWITCH(gtc_mfma_sw, "CFFM_GTC_MFMA", 1)
+// the prototype attention on the matrix pipe for K <= 128 (gtc_kernels.h), fp32 on the VALU above
 // workgroups the three matrix-pipe kernels aim for (a wave walks ceil(tiles / (4 x workgroups)) tiles)
 #ifndef GTM_WGS_FWD
 #define GTM_WGS_FWD 512
@@ -1339,7 +1150,7 @@ int cffm_gtc_attn_fwd(const float* q_raw, const float* q_b, const float* kv_raw,
         granted = true;
     }
 #endif
-    if (K <= 128 && gtc_mfma_sw()) {
+    if (K <= 128) {
         // the matrix-pipe form (three-pass bf16 split): ~512 workgroups of four waves, each wave a run of 16-token tiles
         const int tiles = (T + 15) / 16;
         int tpw = (tiles * CFFM_HEADS * B + 4 * GTM_WGS_FWD - 1) / (4 * GTM_WGS_FWD);
@@ -1370,7 +1181,7 @@ int cffm_gtc_attn_bwd(const float* q_raw, const float* q_b, const float* kv_raw,
     PROF(ST_GTC_BWD);
     hipStream_t st = (hipStream_t)stream;
     REQUIRE(K >= 1 && K <= 256 && B >= 1 && T >= 1, "gtc_attn_bwd: K=%d outside 1..256", K);
-    if (K <= 128 && gtc_mfma_sw()) {
+    if (K <= 128) {
         // the matrix-pipe form (gtc_kernels.h): dq per 16-token tile, then dKc / dVc per pair of tiles into one record per workgroup
         const int tiles = (T + 15) / 16, pairs = (T + 31) / 32, U = (K + 31) / 32;
         int tpw = (tiles * CFFM_HEADS * B + 4 * GTM_WGS_DQ - 1) / (4 * GTM_WGS_DQ), ppw = (pairs * CFFM_HEADS * B + 4 * GTM_WGS_DKV - 1) / (4 * GTM_WGS_DKV);
@@ -1423,12 +1234,8 @@ int cffm_gtc_attn_bwd(const float* q_raw, const float* q_b, const float* kv_raw,
 }
 
 // ------------------------------------------------------------------------------------------- fused row-panel stages
-// CFFM_PANEL=0 keeps the round-2 sequence of tiled GEMMs + row kernels (A/B measurements)
-// CFFM_STORE_ACT=0: the fused forward does NOT store gelu(hraw + b1); the fc2 weight gradient re-applies bias + GELU to hraw while it
-// stages its tiles (29.5 MB less written per block, but the GELU then sits in the weight-gradient GEMM's staging path: measured
-// 0.8914 vs 0.8843 ms per step without / with the stored activation, means of three alternating runs -- storing is the default)
-CFFM_SWITCH(store_act, "CFFM_STORE_ACT", 1)
-CFFM_SWITCH(panel_on, "CFFM_PANEL", 1)
+// The fused forward stores act = gelu(hraw + b1) for the fc2 weight gradient (re-applying bias + GELU to hraw while that GEMM stages its
+// tiles writes 29.5 MB less per block but puts the GELU in its staging path: 0.8914 vs 0.8843 ms per step, means of three alternating runs)
 #ifndef MLP_MT
 #define MLP_MT 2
 #endif
@@ -1481,11 +1288,9 @@ static int panel_qkv_dx(const float* dqkv, const float* wfn, float* dx, long M, 
     return panel_mt(M) == 3 ? panel_gemm_launch<3, 2, false, 0>(dqkv, 768, M, 768, wfn, dx, 256, nullptr, nullptr, st, colrec, dqkv_t)
                             : panel_gemm_launch<2, 2, false, 0>(dqkv, 768, M, 768, wfn, dx, 256, nullptr, nullptr, st, colrec, dqkv_t);
 }
-// CFFM_PANEL_QKV=0: the q|k|v Linear keeps the tiled GEMMs (A/B: 0.8843 tiled vs 0.8729 ms per step as row panels, means of three
-// alternating runs with the activation stored)
-CFFM_SWITCH(qkv_colrec_on, "CFFM_QKV_COLREC", 1)
-// The block's four weight gradients by the streaming kernel (dws_kernels.h): their operands in T-frag storage, written by the row-panel
-// kernels that have them in LDS anyway.  CFFM_DW_STREAM=0 (experiment builds): the LDS-staged group on split-4 / fp32 operands, as before.
+// (the q|k|v Linear as row panels against the tiled GEMMs: 0.8729 vs 0.8843 ms per step, means of three alternating runs)
+// The block's four weight gradients take one of two forms: the streaming kernel (dws_kernels.h) on operands in T-frag storage, written
+// by the row-panel kernels that have them in LDS anyway, or the LDS-staged group on split-4 / fp32 operands (CFFM_DW_STREAM_DEFAULT 0).
 #ifndef CFFM_DW_STREAM_DEFAULT
 #define CFFM_DW_STREAM_DEFAULT 0
 #endif
@@ -1494,10 +1299,8 @@ static int dw_stream_sw() { return g_dw_stream; }
 // Process-wide choice between the two forms of the block's weight gradients (both tested): 1 = streaming kernel on T-frag operands, 0 = the
 // LDS-staged group.  The forward leaves the operands in the form the backward will read: do not change it between a forward and its backward.
 int cffm_dw_stream(int on) { const int was = g_dw_stream; if (on >= 0) g_dw_stream = on != 0; return was; }
-CFFM_SWITCH(panel_qkv_sw, "CFFM_PANEL_QKV", 1)
-static constexpr_or_not int panel_qkv_on() { return panel_qkv_sw() && panel_on(); }
 
-long cffm_mlp_records(long NP) { return (NP + 16 * MLP_MT - 1) / (16 * MLP_MT); }
+static long cffm_mlp_records(long NP) { return (NP + 16 * MLP_MT - 1) / (16 * MLP_MT); }
 
 int cffm_panel_pack_weight(const float* w, int N, int K, int form, float* w_frag, void* stream) {
     REQUIRE(w && w_frag && N >= 16 && K >= 16 && N % 32 == 0 && K % 32 == 0 && (form == 0 || form == 1), "panel_pack_weight: bad arguments");
@@ -1508,9 +1311,9 @@ int cffm_panel_pack_weight(const float* w, int N, int K, int form, float* w_frag
 
 // z2s / acts: split-4 copies (what the LDS-staged weight-gradient kernels read), ao_t / z2_t / act_t: T-frag copies (what the streaming one
 // reads, cffm_tfrag_floats(NP, 256 | 256 | 1024) floats each); every one of the five may be NULL
-int cffm_mlp_fwd_tfrag(const float* ao, const float* xt, long xt_bs, int rows_per_batch, const float* wp_f, const float* w1_f, const float* w2_f,
-                       const float* bp, const float* b1, const float* b2, const float* g2, const float* be2, float* x1, float* z2s, float* mean2,
-                       float* rstd2, float* hraw, float* acts, float* x2, float* ao_t, float* z2_t, float* act_t, long NP, void* stream) {
+static int cffm_mlp_fwd_tfrag(const float* ao, const float* xt, long xt_bs, int rows_per_batch, const float* wp_f, const float* w1_f, const float* w2_f,
+                              const float* bp, const float* b1, const float* b2, const float* g2, const float* be2, float* x1, float* z2s, float* mean2,
+                              float* rstd2, float* hraw, float* acts, float* x2, float* ao_t, float* z2_t, float* act_t, long NP, void* stream) {
     REQUIRE(NP >= 0 && NP < (1L << 21) && rows_per_batch >= 1, "mlp_fwd: bad sizes");
     if (!NP) return 0;
     REQUIRE(ao && xt && wp_f && w1_f && w2_f && bp && b1 && b2 && g2 && be2 && x1 && mean2 && rstd2 && hraw && x2, "mlp_fwd: null");
@@ -1535,9 +1338,9 @@ int cffm_mlp_fwd(const float* ao, const float* xt, long xt_bs, int rows_per_batc
 }
 
 // dhs: split-4 copy of dh; dout_t / dh_t / dx1_t: T-frag copies of dout, dh, dx1 (cffm_tfrag_floats(NP, 256 | 1024 | 256) floats); each may be NULL
-int cffm_mlp_bwd_tfrag(const float* dout, const float* hraw, const float* b1, const float* x1, const float* mean2, const float* rstd2,
-                       const float* g2, const float* w2_n, const float* w1_n, const float* wp_n, float* dhs, float* dx1, float* dao, float* dg2,
-                       float* dbe2, float* db1, float* db2, float* dbp, float* dout_t, float* dh_t, float* dx1_t, long NP, void* stream) {
+static int cffm_mlp_bwd_tfrag(const float* dout, const float* hraw, const float* b1, const float* x1, const float* mean2, const float* rstd2,
+                              const float* g2, const float* w2_n, const float* w1_n, const float* wp_n, float* dhs, float* dx1, float* dao, float* dg2,
+                              float* dbe2, float* db1, float* db2, float* dbp, float* dout_t, float* dh_t, float* dx1_t, long NP, void* stream) {
     REQUIRE(NP >= 0 && NP < (1L << 21), "mlp_bwd: bad sizes");
     if (!NP) return 0;
     REQUIRE(dout && hraw && b1 && x1 && mean2 && rstd2 && g2 && w2_n && w1_n && wp_n && dx1 && dao, "mlp_bwd: null");
@@ -1581,17 +1384,14 @@ int cffm_mlp_bwd(const float* dout, const float* hraw, const float* b1, const fl
 // Round 1-4 sequenced ~13 forward / ~20 backward stage launches from Python (vss_cffm_amd/ops.py).  Now ONE entry point per
 // direction, built from the base head's kernels: the q projection and its input gradient are row-panel GEMMs (k_panel_gemm), everything
 // from proj_cluster to the block output is the fused Mlp launch of the base block (k_mlp_fwd / k_mlp_bwd: same shapes), the four large
-// weight gradients are one grouped launch (k_gemm_group_tt), every bias / norm gradient is a record reduction in one launch.
+// weight gradients are one streaming launch (k_dw_stream), every bias / norm gradient is a record reduction in one launch.
 struct GtcWs {     // float offsets into the caller's workspace: what the forward keeps for the backward, then the backward's temporaries
     long z, mean1, rstd1, cn, cmean, crstd, qraw, kvraw, ao, lse, x1, z2, mean2, rstd2, hraw, act, wf, wn, z_t, ao_t, saved;
     long dh, dx1, dao, dq, dz, dkv, dcn, dout_t, dx1_t, dq_t, total;
 };
 // The block's four large weight gradients by the streaming kernel (dws_kernels.h) -- everything of this block runs on ONE stream, so what the
 // kernel saves alone (51 -> 38 us) is saved in the step.  z2 / act / dh are then kept in T-frag storage only, z / ao / dout / dx1 / dq get
-// T-frag copies from the row-panel kernels that stage them.  GTC_DW_STREAM=0: the LDS-staged group on split-4 / fp32 operands.
-#ifndef GTC_DW_STREAM
-#define GTC_DW_STREAM 1
-#endif
+// T-frag copies from the row-panel kernels that stage them.
 #define GTC_WFLOATS (2 * 256 * 256 + 2 * 1024 * 256)     // q third | proj_cluster | fc1 | fc2 in fragment order
 static GtcWs gtc_ws_layout(long nt, long nk) {
     GtcWs w;
@@ -1654,20 +1454,16 @@ int cffm_gtc_block_forward(const cffm_gtc_params* p, const float* x, const float
     }
     {
         PROF(ST_GEMM);
-        float* z_t = GTC_DW_STREAM ? ws + W.z_t : nullptr;
+        float* z_t = ws + W.z_t;
         const int rc = panel_mt(nt) == 3 ? panel_gemm_launch<3, 2, true, 0>(ws + W.z, 256, nt, 256, wf, ws + W.qraw, 256, nullptr, nullptr, st, nullptr, z_t)
                                          : panel_gemm_launch<2, 2, true, 0>(ws + W.z, 256, nt, 256, wf, ws + W.qraw, 256, nullptr, nullptr, st, nullptr, z_t);
         REQUIRE(!rc, "gtc_block_forward: q gemm failed");
         REQUIRE(!gemm_nt(ws + W.cn, p->kv_w, ws + W.kvraw, nk, 512, 256, st), "gtc_block_forward: kv gemm failed");
     }
     TRY(cffm_gtc_attn_fwd(ws + W.qraw, p->qkv_b, ws + W.kvraw, p->kv_b, ws + W.ao, ws + W.lse, B, T, K, stream));
-    if (GTC_DW_STREAM)
-        TRY(cffm_mlp_fwd_tfrag(ws + W.ao, x, 0, (int)nt, wf + 256 * 256, wf + 2 * 256 * 256, wf + 2 * 256 * 256 + CFFM_HID * 256, p->proj_b, p->fc1_b, p->fc2_b,
-                               p->norm2_w, p->norm2_b, ws + W.x1, nullptr, ws + W.mean2, ws + W.rstd2, ws + W.hraw, nullptr, out, ws + W.ao_t, ws + W.z2,
-                               ws + W.act, nt, stream));
-    else
-    TRY(cffm_mlp_fwd(ws + W.ao, x, 0, (int)nt, wf + 256 * 256, wf + 2 * 256 * 256, wf + 2 * 256 * 256 + CFFM_HID * 256, p->proj_b, p->fc1_b, p->fc2_b,
-                     p->norm2_w, p->norm2_b, ws + W.x1, ws + W.z2, ws + W.mean2, ws + W.rstd2, ws + W.hraw, ws + W.act, out, nt, stream));
+    TRY(cffm_mlp_fwd_tfrag(ws + W.ao, x, 0, (int)nt, wf + 256 * 256, wf + 2 * 256 * 256, wf + 2 * 256 * 256 + CFFM_HID * 256, p->proj_b, p->fc1_b, p->fc2_b,
+                           p->norm2_w, p->norm2_b, ws + W.x1, nullptr, ws + W.mean2, ws + W.rstd2, ws + W.hraw, nullptr, out, ws + W.ao_t, ws + W.z2,
+                           ws + W.act, nt, stream));
     return 0;
 }
 
@@ -1691,13 +1487,9 @@ int cffm_gtc_block_backward(const cffm_gtc_params* p, const cffm_gtc_grads* g, c
 #endif
     RedScope reductions(st);      // the bias / norm record reductions below run as ONE launch (finish())
     // x2 = x1 + Mlp(LN2(x1)), x1 = x + o Wpc^T + bpc: the fused input-gradient chain of the base block
-    if (GTC_DW_STREAM)
-        TRY(cffm_mlp_bwd_tfrag(dout, ws + W.hraw, p->fc1_b, ws + W.x1, ws + W.mean2, ws + W.rstd2, p->norm2_w, wn + 2 * 256 * 256 + CFFM_HID * 256,
-                               wn + 2 * 256 * 256, wn + 256 * 256, nullptr, ws + W.dx1, ws + W.dao, g->norm2_w, g->norm2_b, g->fc1_b, g->fc2_b, g->proj_b,
-                               ws + W.dout_t, ws + W.dh, ws + W.dx1_t, nt, stream));
-    else
-    TRY(cffm_mlp_bwd(dout, ws + W.hraw, p->fc1_b, ws + W.x1, ws + W.mean2, ws + W.rstd2, p->norm2_w, wn + 2 * 256 * 256 + CFFM_HID * 256, wn + 2 * 256 * 256,
-                     wn + 256 * 256, ws + W.dh, ws + W.dx1, ws + W.dao, g->norm2_w, g->norm2_b, g->fc1_b, g->fc2_b, g->proj_b, nt, stream));
+    TRY(cffm_mlp_bwd_tfrag(dout, ws + W.hraw, p->fc1_b, ws + W.x1, ws + W.mean2, ws + W.rstd2, p->norm2_w, wn + 2 * 256 * 256 + CFFM_HID * 256,
+                           wn + 2 * 256 * 256, wn + 256 * 256, nullptr, ws + W.dx1, ws + W.dao, g->norm2_w, g->norm2_b, g->fc1_b, g->fc2_b, g->proj_b,
+                           ws + W.dout_t, ws + W.dh, ws + W.dx1_t, nt, stream));
     TRY(cffm_gtc_attn_bwd(ws + W.qraw, p->qkv_b, ws + W.kvraw, p->kv_b, ws + W.ao, ws + W.dao, ws + W.lse, ws + W.dq, ws + W.dkv, B, T, K, stream));
     {
         // dz = dq Wq (row panels; the q bias gradient = column sums of dq out of the staging registers)
@@ -1706,7 +1498,7 @@ int cffm_gtc_block_backward(const cffm_gtc_params* p, const cffm_gtc_grads* g, c
         const long nrec = (nt + 16 * mt - 1) / (16 * mt);
         float* qrec = red_scratch((size_t)nrec * 256, st);
         REQUIRE(qrec, "gtc_block_backward: scratch allocation failed");
-        float* dq_t = GTC_DW_STREAM ? ws + W.dq_t : nullptr;
+        float* dq_t = ws + W.dq_t;
         const int rc = mt == 3 ? panel_gemm_launch<3, 2, false, 0>(ws + W.dq, 256, nt, 256, wn, ws + W.dz, 256, nullptr, nullptr, st, qrec, dq_t)
                                : panel_gemm_launch<2, 2, false, 0>(ws + W.dq, 256, nt, 256, wn, ws + W.dz, 256, nullptr, nullptr, st, qrec, dq_t);
         REQUIRE(!rc, "gtc_block_backward: q input-gradient gemm failed");
@@ -1716,23 +1508,17 @@ int cffm_gtc_block_backward(const cffm_gtc_params* p, const cffm_gtc_grads* g, c
         reduce_records(qrec, (int)nrec, 256, 256, segs, st);
     }
     {
-        // the four large weight gradients in one grouped launch (z, z2, act and dh are in split-4 storage)
+        // the four large weight gradients in one streaming launch (operands in T-frag storage)
         PROF(ST_GEMM); PROF2(ST_G_DW);
-        const cffm_wgrad wg4[4] = {{ws + W.dq, ws + W.z, g->qkv_w, nt, 256, 256}, {ws + W.dh, ws + W.z2, g->fc1_w, nt, CFFM_HID, 256},
-                                   {dout, ws + W.act, g->fc2_w, nt, 256, CFFM_HID}, {ws + W.dx1, ws + W.ao, g->proj_w, nt, 256, 256}};
-        const GemmTNPre pre4[4] = {{0, 1, nullptr}, {1, 1, nullptr}, {0, 1, nullptr}, {0, 0, nullptr}};
-        if (GTC_DW_STREAM) {
-            const cffm_wgrad wt4[4] = {{ws + W.dq_t, ws + W.z_t, g->qkv_w, nt, 256, 256}, {ws + W.dh, ws + W.z2, g->fc1_w, nt, CFFM_HID, 256},
-                                       {ws + W.dout_t, ws + W.act, g->fc2_w, nt, 256, CFFM_HID}, {ws + W.dx1_t, ws + W.ao_t, g->proj_w, nt, 256, 256}};
-            DwsPlan P;
-            REQUIRE(dw_stream_plan((const GemmTN*)wt4, 4, dw_stream_target(), &P), "gtc_block_backward: weight-gradient plan failed");
-            float* part = P.part_floats ? lib_scratch(P.part_floats) : nullptr;
-            REQUIRE(!P.part_floats || part, "gtc_block_backward: scratch allocation failed");
-            // (on the library's side stream, beside the prototype side's chain of small launches below: measured 0.268 vs 0.262 ms at K = 8, 0.296 vs
-            //  0.293 at K = 100 -- the fork and the join cost a replayed graph more than the overlap returns; it stays on the caller's stream)
-            REQUIRE(!dw_group_stream((const GemmTN*)wt4, 4, st, part, dw_stream_target()), "gtc_block_backward: weight-gradient gemm failed");
-        } else
-        REQUIRE(!gemm_tn_group((const GemmTN*)wg4, 4, st, pre4, lib_scratch, 480), "gtc_block_backward: weight-gradient gemm failed");
+        const cffm_wgrad wt4[4] = {{ws + W.dq_t, ws + W.z_t, g->qkv_w, nt, 256, 256}, {ws + W.dh, ws + W.z2, g->fc1_w, nt, CFFM_HID, 256},
+                                   {ws + W.dout_t, ws + W.act, g->fc2_w, nt, 256, CFFM_HID}, {ws + W.dx1_t, ws + W.ao_t, g->proj_w, nt, 256, 256}};
+        DwsPlan P;
+        REQUIRE(dw_stream_plan((const GemmTN*)wt4, 4, dw_stream_target(), &P), "gtc_block_backward: weight-gradient plan failed");
+        float* part = P.part_floats ? lib_scratch(P.part_floats) : nullptr;
+        REQUIRE(!P.part_floats || part, "gtc_block_backward: scratch allocation failed");
+        // (on the library's side stream, beside the prototype side's chain of small launches below: measured 0.268 vs 0.262 ms at K = 8, 0.296 vs
+        //  0.293 at K = 100 -- the fork and the join cost a replayed graph more than the overlap returns; it stays on the caller's stream)
+        REQUIRE(!dw_group_stream((const GemmTN*)wt4, 4, st, part, dw_stream_target()), "gtc_block_backward: weight-gradient gemm failed");
     }
     // the prototype side: [Kc|Vc] = cn Wkv^T + bkv on B*K rows
     TRY(cffm_colsum(ws + W.dkv, nk, 512, g->kv_b, stream));
@@ -1765,10 +1551,10 @@ static int prep_args(PrepArgs& a, const cffm_block_params* params, int d0, int n
         a.w_f[d] = ws + L.w_frag;
     }
     a.nbias = nb;
-    // pack: 0 nothing (library GEMMs) | 1 split-4 copy + fragment-ordered copies | 2 fragment-ordered copies only -- every Linear of the
-    // block runs as a row-panel kernel then and nobody reads the split-4 copy (3 MB read + 3 MB written per block saved)
-    a.pack = (panel_on() && panel_qkv_on()) ? 2 : 1;
-    return nb + 1 + (a.pack ? PREP_WBLOCKS + PREP_FBLOCKS : 0);      // workgroups per block
+    // pack 2: the fragment-ordered weight copies only -- every Linear of the block runs as a row-panel kernel and nobody reads a split-4
+    // copy (3 MB read + 3 MB written per block saved; k_param_prep also knows 0: nothing, 1: split-4 + fragment-ordered copies)
+    a.pack = 2;
+    return nb + 1 + PREP_WBLOCKS + PREP_FBLOCKS;      // workgroups per block
 }
 static int param_prep(const cffm_block_params* params, int n, float* ws0, long ws_stride, const cffm_block_ws& L, void* stream) {
     PROF(ST_BIAS_ASM);
@@ -1803,25 +1589,22 @@ static int block_forward_impl(const cffm_geom* g, const cffm_block_params* p, co
     cffm_block_ws_layout(g, &L);
     const long NR = (long)g->B * g->RC, NP = (long)g->B * g->HW;
     hipStream_t st = (hipStream_t)stream;
-    // Hand-written GEMMs: the tensors only they read (zall, z2, act) are produced in split-4 storage and the weights come
-    // from the split-4 copy k_param_prep made (ws.w_split), so no operand tile is split while it is staged -- except ao,
-    // which the attention backward also reads.  CFFM_GEMM=lib (rocBLAS cross-check) keeps everything plain fp32.
-    constexpr int sp = 1;   // split-4 storage of what only the GEMMs read (zall, z2, act, dh) and of the weights: always (the library-GEMM form that kept plain fp32 left in round 4)
+    // zall is written in split-4 storage (only GEMMs read it; the fused kernels do the same for z2, act and dh)
     // (a pending join with the side-stream parameter prep -- layer_forward_impl -- is taken AFTER this launch: the kernel builds its
     //  pooling-matrix rows from the raw weights then, and the chain's first kernel does not wait for another stream)
     const bool late_join = g_prep_join.pending;
     TRY(ln_pool_fwd_impl(g, x_ref, ref_bs, x_tgt, tgt_bs, p->norm1_w, p->norm1_b, ws + L.M, p->pool_b, ws + L.zall,
-                         ws + L.mean1, ws + L.rstd1, sp, stream, late_join ? p->pool_w : nullptr));
+                         ws + L.mean1, ws + L.rstd1, 1, stream, late_join ? p->pool_w : nullptr));
     if (late_join) {
         g_prep_join.pending = false;
         side_join(g_prep_join.side, st, 0);
     }
-    if (sp && panel_qkv_on()) {
+    {
         PROF(ST_GEMM); PROF2(ST_G_QKV_FWD);
         REQUIRE(!panel_qkv_fwd(ws + L.zall, ws + L.w_frag, p->qkv_b, (h16*)(ws + L.qkv), NR, st, dw_stream_sw() ? ws + L.zall_t : nullptr), "block_forward: qkv gemm failed");
     }
     TRY(cffm_attn_fwd(g, ws + L.qkv, key_src, q_dst, (const void*)(ws + L.bias), ws + L.ao, ws + L.lse, stream));
-    if (sp && panel_on()) {
+    {
         // proj + residual + norm2 + Mlp in one row-panel launch (panel_kernels.h); weights in fragment order from k_param_prep
         const float* wf = ws + L.w_frag;
         PROF(ST_GEMM);
@@ -1832,13 +1615,11 @@ static int block_forward_impl(const cffm_geom* g, const cffm_block_params* p, co
         else
         TRY(cffm_mlp_fwd(ws + L.ao, x_tgt, tgt_bs, g->HW, wf + 768 * 256, wf + 768 * 256 + 256 * 256, wf + 768 * 256 + 256 * 256 + 1024 * 256,
                          p->proj_b, p->fc1_b, p->fc2_b, p->norm2_w, p->norm2_b, ws + L.x1, ws + L.z2, ws + L.mean2, ws + L.rstd2, ws + L.hraw,
-                         store_act() ? ws + L.act : nullptr /* CFFM_STORE_ACT=0: the fc2 weight gradient re-applies bias + GELU to hraw */,
-                         ws + L.x2, NP, stream));
+                         ws + L.act, ws + L.x2, NP, stream));
         CHECK_LAUNCH("block_forward");
-        return 0;
     }
     (void)scratch;
-    return fail(-3, "block_forward: unreachable");
+    return 0;
 }
 
 static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, const cffm_block_grads* gr,
@@ -1850,29 +1631,16 @@ static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, c
 // under stream capture the chain's kernel is ln_pool_bwd's FIRST dependant and keeps its place on the graph's first stream (the graph
 // executor hands every further dependant of a node the next stream, see side_fork_mark).
 #ifndef CFFM_EMU
-static struct { bool has, cs; RedJobs jobs; int parity; } g_tail = {false, false, {}, 0};
-// on_main (end of a layer backward): the optimizer is what waits for these gradients, so they are the chain now -- launched on the
-// caller's stream itself, in front of everything else that follows the last ln_pool_bwd
-// `on` (fork_order bit 6): a side stream that is already ordered behind the ln_pool_bwd in question (the NEXT block's weight-gradient
-// stream, forked behind that block's gather): no fork of its own, so ln_pool_bwd keeps a single dependant
-static int tail_flush(hipStream_t st, bool on_main = false, hipStream_t on = nullptr) {
+static struct { bool has; RedJobs jobs; int parity; } g_tail = {false, {}, 0};
+// (the LAST block's tail of a layer backward is not launched here: the optimizer is what waits for those gradients, so they ride in the
+// CFFA's final reduction launch on the caller's stream, in front of everything else that follows the last ln_pool_bwd -- layer_backward_impl)
+static int tail_flush(hipStream_t st) {
     if (!g_tail.has) return 0;
     g_tail.has = false;
-    hipStream_t s3 = on_main ? st : (on ? on : side_fork_take(st, 3));
-    if (on && !on_main) {
-        g_tail.cs = false;
-        redq_launch(g_tail.jobs, s3);
-        CHECK_LAUNCH("block_backward reductions");
-        side_record(s3, st, g_side.tail_done[g_tail.parity]);
-        g_side.tail_pending[g_tail.parity] = true;
-        return 0;
-    }
-    // the q|k|v bias records come from the column sum on the weight-gradient stream.  On a side stream the tail waits for that stream's
-    // whole block (tail_order: the graph executor then queues it right behind the block's side work; waiting for the column sum alone
-    // it was queued behind the NEXT block's side work); on the caller's stream only for the column sum (cs_order)
-    if (!on_main) (void)hipStreamWaitEvent(s3, g_side.tail_order, 0);
-    else if (g_tail.cs) (void)hipStreamWaitEvent(s3, g_side.cs_order, 0);
-    g_tail.cs = false;
+    hipStream_t s3 = side_fork_take(st, 3);
+    // the tail waits for the weight-gradient stream's whole block (tail_order: the graph executor then queues it right behind the block's
+    // side work; waiting for a single kernel of it, the tail was queued behind the NEXT block's side work)
+    (void)hipStreamWaitEvent(s3, g_side.tail_order, 0);
     redq_launch(g_tail.jobs, s3);
     CHECK_LAUNCH("block_backward reductions");
     if (s3 != st) {
@@ -1882,16 +1650,11 @@ static int tail_flush(hipStream_t st, bool on_main = false, hipStream_t on = nul
     return 0;
 }
 #else
-static int tail_flush(hipStream_t, bool = false, hipStream_t = nullptr) { return 0; }
+static int tail_flush(hipStream_t) { return 0; }
 #endif
-static bool tail_on_main() {     // CFFM_TAIL_MAIN=0: the last block's tail on the side stream like every other block's (A/B)
-    static int v = -1;
-    if (v < 0) { const char* e = cffm_tune("CFFM_TAIL_MAIN"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v != 0;
-}
 static void tail_reset() {      // entry of a layer backward: nothing of a previous (failed) call is left to launch or to wait for
 #ifndef CFFM_EMU
-    g_tail.has = g_tail.cs = false;
+    g_tail.has = false;
     for (int i = 0; i < 2; ++i) g_side.dw_pending[i] = g_side.bias_pending[i] = g_side.tail_pending[i] = false;   // (a call that returned normally ended in side_join_all)
 #endif
 }
@@ -1914,11 +1677,6 @@ static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, c
                                const int* q_dst, const int* inv_ptr, const int* inv_idx, const float* ws, const float* dout,
                                float* dx_tgt, long dtgt_bs, float* scratch, int defer, int par, int slot, int nslots, void* stream) {
     REQUIRE(g && p && gr && ws && dout && scratch, "block_backward: null");
-    {
-        static int defer_env = -1;   // CFFM_DEFER_JOIN=0: every block ends fully joined (round-2 behaviour; A/B measurements)
-        if (defer_env < 0) { const char* e = cffm_tune("CFFM_DEFER_JOIN"); defer_env = (e && e[0] == '0') ? 0 : 1; }
-        defer = defer && defer_env;
-    }
     cffm_block_ws L;
     cffm_block_ws_layout(g, &L);
     const Scratch S = scratch_layout(g);
@@ -1955,9 +1713,8 @@ static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, c
         g_side.dw_pending[par] = false;
     }
 #endif
-    constexpr int sp = 1;   // see block_forward_impl: zall / z2 / act / weights (and dh below) in split-4 storage
-    const int one_group = sp ? dw_one_group(st) : 0;
-    if (sp && !one_group) {
+    const int one_group = dw_one_group(st);
+    if (!one_group) {
         // the grouped form (chosen under stream capture) needs larger partial slabs than the split form: size the side scratch for it
         // now, while allocating is still allowed -- a capture that follows eager steps must not grow it
         const GemmTN all4[4] = {{nullptr, nullptr, nullptr, NR, 768, CFFM_C}, {nullptr, nullptr, nullptr, NP, CFFM_HID, CFFM_C},
@@ -1977,16 +1734,14 @@ static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, c
         return dw_group_stream((const GemmTN*)wg, n, s, part, dw_stream_target(), after);
     };
     // the four problems' operands: T-frag copies (streaming) or the split-4 / fp32 tensors themselves
-    const float* fc2_x = stream_dw ? ws + L.act : ((sp && panel_on() && !store_act()) ? ws + L.hraw : ws + L.act);
     const cffm_wgrad wg_qkv = {stream_dw ? dqkv_t : dqkv, stream_dw ? ws + L.zall_t : ws + L.zall, gr->qkv_w, NR, 768, CFFM_C};
     const cffm_wgrad wg_fc1 = {dact, ws + L.z2, gr->fc1_w, NP, CFFM_HID, CFFM_C};
-    const cffm_wgrad wg_fc2 = {stream_dw ? dout_t : dout, fc2_x, gr->fc2_w, NP, CFFM_C, CFFM_HID};
+    const cffm_wgrad wg_fc2 = {stream_dw ? dout_t : dout, ws + L.act, gr->fc2_w, NP, CFFM_C, CFFM_HID};
     const cffm_wgrad wg_proj = {stream_dw ? dx1_t : dx1, stream_dw ? ws + L.ao_t : ws + L.ao, gr->proj_w, NP, CFFM_C, CFFM_C};
     // x2 = x1 + act W2^T + b2
     // act = gelu(hraw + b1); hraw = z2 W1^T: the GELU backward runs in the epilogue of the fc2 input-gradient GEMM (dact is
     // never materialised; what is stored is dh, in split-4 storage since only GEMMs read it, plus column-sum records of it)
-    const int panel = sp && panel_on();
-    if (panel) {
+    {
         // the input-gradient chain fc2 -> GELU' -> fc1 -> norm2 -> proj in one row-panel launch; dh (split-4), dx1 and the bias / norm
         // gradient records come out of it for the weight-gradient groups and the reductions below
         const float* wfn = ws + L.w_frag + PREP_WFLOATS;
@@ -1999,12 +1754,12 @@ static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, c
         TRY(cffm_mlp_bwd(dout, ws + L.hraw, p->fc1_b, ws + L.x1, ws + L.mean2, ws + L.rstd2, p->norm2_w, wfn + 768 * 256 + 256 * 256 + 1024 * 256,
                          wfn + 768 * 256 + 256 * 256, wfn + 768 * 256, dact, dx1, dao, gr->norm2_w, gr->norm2_b, gr->fc1_b, gr->fc2_b, gr->proj_b, NP,
                          stream));
-        if (!(fork_order() & 64)) TRY(tail_flush(st));    // the previous block's parameter-gradient tail, now that this block's first kernel is ln_pool_bwd's first dependant
+        TRY(tail_flush(st));    // the previous block's parameter-gradient tail, now that this block's first kernel is ln_pool_bwd's first dependant
         if (!one_group) {
             sa = side_fork(st, 0);
             void* stream_a = (void*)sa;
             const cffm_wgrad wga[2] = {wg_fc1, wg_fc2};
-            const GemmTNPre prea[2] = {{1, 1, nullptr}, {0, (panel && !store_act()) ? 2 : 1, p->fc1_b}};
+            const GemmTNPre prea[2] = {{1, 1, nullptr}, {0, 1, p->fc1_b}};
             {
                 void* stream = stream_a;
                 PROF2(ST_G_DW);
@@ -2014,16 +1769,13 @@ static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, c
         }
     }
     // attention: the fused kernel and the dK/dV gather stay on the chain; the bias-gradient tile sum and its scatter into the six
-    // tables go to the side stream (branch 1), the q|k|v bias column sum and the weight gradients of q|k|v / proj after the gather
-    // (branch 2)
-    if (!(fork_order() & 64)) TRY(tail_flush(st));        // (forms of the block whose first kernel is not the fused Mlp backward)
+    // tables get no branch of their own: they follow the weight-gradient group on ITS stream (side_b), so the attention backward has
+    // ONE dependant and the chain stays on its hardware queue
     hipStream_t sb = st, s1 = st;
-    int bias_late = 0, late_ng = 0;
-    float* late_dbp = nullptr;
+    float* dbp;
+    int ng;
     {
         PROF(ST_ATTN_BWD);
-        float* dbp;
-        int ng;
 #ifndef CFFM_EMU
         if (g_side.bias_pending[par]) {   // the bias-gradient tile sum of two blocks ago still owns this set's tile buffer / dbiasT
             side_wait(st, g_side.bias_done[par]);
@@ -2031,108 +1783,67 @@ static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, c
         }
 #endif
         TRY(attn_bwd_fused(g, ws + L.qkv, key_src, q_dst, (const h16*)(ws + L.bias), ws + L.ao, dao, ws + L.lse, dqkv, scratch + S.dkvp, &dbp, &ng, par, stream));
-        // (side work first here, although that makes the chain change hardware queues under graph replay -- see side_fork_mark: with the
-        //  chain launched first the executor parked these side kernels behind the NEXT block's chain and the step's tail grew:
-        //  0.864 vs 0.849 ms per step, means of three alternating runs)
-        if (sp && (fork_order() & 4)) {
-            // no branch of its own: the bias-gradient tile sum and scatter follow the weight-gradient group on ITS stream (below), so
-            // the attention backward has ONE dependant and the chain stays on its hardware queue
-            TRY(attn_bwd_gather(g, inv_ptr, inv_idx, scratch + S.dkvp, dqkv, stream));
-            bias_late = 1; late_dbp = dbp; late_ng = ng;
-        } else if (sp && (fork_order() & 1)) {
-            side_fork_mark(st, 1);
-            TRY(attn_bwd_gather(g, inv_ptr, inv_idx, scratch + S.dkvp, dqkv, stream));
-            s1 = side_fork_take(st, 1);
-            TRY(attn_bwd_bias_sum(dbp, ng, dbiasT, (void*)s1));
-            TRY(cffm_bias_scatter(dbiasT, gr->rpb_own, gr->rpb_ring, gr->rpb_pool, (void*)s1));
-        } else {
-        s1 = sp ? side_fork(st, 1) : st;
-        TRY(attn_bwd_bias_sum(dbp, ng, dbiasT, (void*)s1));
-        TRY(cffm_bias_scatter(dbiasT, gr->rpb_own, gr->rpb_ring, gr->rpb_pool, (void*)s1));
         TRY(attn_bwd_gather(g, inv_ptr, inv_idx, scratch + S.dkvp, dqkv, stream));
-        }
     }
-    // q|k|v = zall Wqkv^T + b (bias folded into the f16 epilogue; its gradient is the column sum of dqkv)
-    int dx_done = 0;
-    // the q|k|v bias gradient = column sums of dqkv: as records out of the row-panel input-gradient GEMM, which stages every row of
-    // dqkv anyway (CFFM_QKV_COLREC=0: the separate column-sum pass over the 32 MB on the side stream, as before)
-    float* qkv_rec = nullptr;
-    if (sp && panel_qkv_on() && qkv_colrec_on()) {
-        const long nrec = panel_qkv_records(NR);
-        qkv_rec = red_scratch((size_t)nrec * 768, st);
-        REQUIRE(qkv_rec, "block_backward: scratch allocation failed");
+    // q|k|v = zall Wqkv^T + b (bias folded into the f16 epilogue); its gradient = the column sums of dqkv, as records out of the
+    // row-panel input-gradient GEMM, which stages every row of dqkv anyway
+    const long nrec = panel_qkv_records(NR);
+    float* qkv_rec = red_scratch((size_t)nrec * 768, st);
+    REQUIRE(qkv_rec, "block_backward: scratch allocation failed");
+    {
         RedSegs segs;
         segs.nseg = 0;
         seg_add(segs, 0, 768, gr->qkv_b, 0);
         reduce_records(qkv_rec, (int)nrec, 768, 768, segs, st);
     }
-    if (sp && ((fork_order() & 2) || stream_dw) && panel_qkv_on()) {     // chain first: the q|k|v input gradient is launched before the side work
+    {   // chain first: the q|k|v input gradient is launched before the side work
         // (streaming weight gradients: the side work forks BEHIND this kernel -- it leaves the T-frag copy of dqkv the q|k|v weight gradient reads)
         if (!stream_dw) side_fork_mark(st, 2);
         PROF(ST_GEMM); PROF2(ST_G_QKV_DX);
         REQUIRE(!panel_qkv_dx(dqkv, ws + L.w_frag + PREP_WFLOATS, dzall, NR, st, qkv_rec, stream_dw ? dqkv_t : nullptr), "block_backward: q|k|v input-gradient gemm failed");
         if (stream_dw) side_fork_mark(st, 2);
-        dx_done = 1;
     }
-    // the block's side work behind the dK/dV gather (weight gradients, bias-gradient tiles, the previous block's tail)
+    // the block's side work behind the q|k|v input gradient: the weight gradients, then the bias-gradient tiles on the same stream
     auto side_b = [&]() -> int {
-    if (sp) {
-        sb = dx_done ? side_fork_take(st, 2) : side_fork(st, 2);
+        sb = side_fork_take(st, 2);
         void* stream_b = (void*)sb;
-        if (!qkv_rec) {
-            TRY(cffm_colsum(dqkv, NR, 768, gr->qkv_b, stream_b));
-#ifndef CFFM_EMU
-            if (sb != st) { (void)hipEventRecord(g_side.cs_order, sb); g_tail.cs = true; }
-#endif
-        }
         if (one_group) {
             // ALL four weight gradients as one grouped launch (~480 workgroups with one slice length, one partial-sum launch: 59 us
             // where two groups of two take 2 x 53), on the side stream beside q|k|v's input gradient and the CFFA backward; every
             // operand lives until the end of the block now that ln_pool_bwd no longer writes over `dout`
             const cffm_wgrad wg4[4] = {wg_qkv, wg_fc1, wg_fc2, wg_proj};
-            const GemmTNPre pre4[4] = {{0, 1, nullptr}, {1, 1, nullptr}, {0, (panel && !store_act()) ? 2 : 1, p->fc1_b}, {0, 0, nullptr}};
+            const GemmTNPre pre4[4] = {{0, 1, nullptr}, {1, 1, nullptr}, {0, 1, p->fc1_b}, {0, 0, nullptr}};
             void* stream = stream_b;
             PROF(ST_GEMM); PROF2(ST_G_DW);
             REQUIRE(!dw_group(wg4, pre4, 4, sb, 480, dw_group_launched), "block_backward: weight-gradient gemm failed");
             sa = sb;
             side_mark(sa, st, 0);
-            if (bias_late) {
+            {
                 PROF(ST_ATTN_BWD);
                 s1 = sb;
-                TRY(attn_bwd_bias_sum(late_dbp, late_ng, dbiasT, (void*)s1));
+                TRY(attn_bwd_bias_sum(dbp, ng, dbiasT, (void*)s1));
                 TRY(cffm_bias_scatter(dbiasT, gr->rpb_own, gr->rpb_ring, gr->rpb_pool, (void*)s1));
-                bias_late = 0;
             }
-            if ((fork_order() & 64) && sb != st) TRY(tail_flush(st, false, sb));   // the PREVIOUS block's record reductions: no fork of their own
         } else {
-        const cffm_wgrad wgb[2] = {wg_qkv, wg_proj};
-        const GemmTNPre preb[2] = {{0, 1, nullptr}, {0, 0, nullptr}};
-        {
-            void* stream = stream_b;
-            PROF(ST_GEMM); PROF2(ST_G_DW);
-            REQUIRE(!dw_group(wgb, preb, 2, sb, 320, dw_group_launched), "block_backward: weight-gradient gemm failed");
-        }
-        if (bias_late) {
+            const cffm_wgrad wgb[2] = {wg_qkv, wg_proj};
+            const GemmTNPre preb[2] = {{0, 1, nullptr}, {0, 0, nullptr}};
+            {
+                void* stream = stream_b;
+                PROF(ST_GEMM); PROF2(ST_G_DW);
+                REQUIRE(!dw_group(wgb, preb, 2, sb, 320, dw_group_launched), "block_backward: weight-gradient gemm failed");
+            }
             PROF(ST_ATTN_BWD);
             s1 = sb;
-            TRY(attn_bwd_bias_sum(late_dbp, late_ng, dbiasT, (void*)s1));
+            TRY(attn_bwd_bias_sum(dbp, ng, dbiasT, (void*)s1));
             TRY(cffm_bias_scatter(dbiasT, gr->rpb_own, gr->rpb_ring, gr->rpb_pool, (void*)s1));
-            bias_late = 0;
         }
-        }
-    }
-    return 0;
+        return 0;
     };
     // Streaming weight gradients under capture: the group is launched AFTER the chain's next kernel (ln_pool_bwd_tgt below), so that kernel
     // is the q|k|v input gradient's first-launched dependant and keeps the chain's hardware queue (see side_fork_mark); nothing the
     // group reads is written by it (fc2's weight gradient reads the T-frag copy of dout, not dout).
-    const bool side_late = stream_dw && one_group && dx_done;
+    const bool side_late = stream_dw && one_group;
     if (!side_late) TRY(side_b());
-    if (dx_done) {
-    } else if (sp && panel_qkv_on()) {
-        PROF(ST_GEMM); PROF2(ST_G_QKV_DX);
-        REQUIRE(!panel_qkv_dx(dqkv, ws + L.w_frag + PREP_WFLOATS, dzall, NR, st, qkv_rec), "block_backward: q|k|v input-gradient gemm failed");
-    }
     if (!side_late && (!one_group || dx_tgt == dout)) side_join(sa, st, 0);    // fc2's weight gradient has read dout before an in-place ln_pool_bwd overwrites it
 #ifndef CFFM_EMU
     if (g_side.dw_pending[par ^ 1] && g_side.dw_dout[par ^ 1] == dx_tgt) {   // (depth >= 3: the block before still reads its dout = our dx_tgt)
@@ -2148,7 +1859,7 @@ static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, c
     // the record reductions (every block-partial record of this backward except the CFFA's is written by now):
     // parameter gradients only -> side stream (branch 3); the caller's stream then waits for the side stream once
 #ifndef CFFM_EMU
-    if (defer && sp && sb != st && s1 != st && g_side.on && (fork_order() & 32)) {
+    if (defer && sb != st && s1 != st && g_side.on) {
         if (g_tail.has) TRY(tail_flush(st));    // (an earlier block's tail nobody has launched yet: before its slot is reused)
         side_fork_mark(st, 3);
         if (s1 != sb) side_order(s1, sb);
@@ -2162,13 +1873,13 @@ static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, c
         return 0;
     }
 #endif
-    hipStream_t s3 = sp ? side_fork(st, 3) : st;
-    if (sp && sb != st && s3 != st) side_order(sb, s3);     // the q|k|v bias records come from branch 2's column sum
-    if (sp && s1 != st && s3 != st && s1 != s3) side_order(s1, s3);   // (four side streams: branch 1 joins through branch 3)
+    hipStream_t s3 = side_fork(st, 3);
+    if (sb != st && s3 != st) side_order(sb, s3);     // (behind the block's side work, as in tail_flush)
+    if (s1 != st && s3 != st && s1 != s3) side_order(s1, s3);   // (four side streams: branch 1 joins through branch 3)
     reductions.finish_on(s3);
     CHECK_LAUNCH("block_backward reductions");
 #ifndef CFFM_EMU
-    if (defer && sp && sb != st && s3 != st) {
+    if (defer && sb != st && s3 != st) {
         // (no wait for the weight-gradient GEMMs: the next block works in the other scratch set; whoever reuses THIS set, or writes
         //  the `dout` they read, waits for dw_done[par] then)
         g_side.dw_pending[par] = true;
@@ -2183,7 +1894,7 @@ static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, c
     (void)defer;
     side_mark(s3, st, 1);
     side_join(s3, st, 1);    // the caller's stream owns every gradient (and the scratch operands) again
-    if (sp && sb != st && sb != s3) { side_mark(sb, st, 0); side_join(sb, st, 0); }   // ... on both side streams
+    if (sb != st && sb != s3) { side_mark(sb, st, 0); side_join(sb, st, 0); }   // ... on both side streams
     return 0;
 }
 
@@ -2420,14 +2131,11 @@ int cffm_upce_maps_bwd(const float* logits, const long long* labels, const int* 
     hipStream_t st = (hipStream_t)stream;
     REQUIRE((long)M * ((w + UPCE_QT - 1) / UPCE_QT) * ((h + UPCE_QT - 1) / UPCE_QT) < (1L << 31), "upce_bwd: too many tiles");
     const unsigned grid = (unsigned)((long)M * ((w + UPCE_QT - 1) / UPCE_QT) * ((h + UPCE_QT - 1) / UPCE_QT));
-    // two forms (CFFM_UPCE_BWD = block | gather): the block form evaluates every output pixel's soft-max about 1.2 x per launch from
-    // register-resident cells (default); the gather form re-evaluates it in each low-resolution pixel it taps (round 1; also the
-    // fallback for down-sampling geometries, where blocks are not contiguous runs)
-    static int form = -1, ty_env = 0, slots = 0;
-    if (form < 0) {
-        const char* e = cffm_tune("CFFM_UPCE_BWD");
-        const char* t = cffm_tune("CFFM_UPCE_TY");
-        ty_env = t ? atoi(t) : 0;
+    // two forms: the block form evaluates every output pixel's soft-max about 1.2 x per launch from register-resident cells; the gather
+    // form re-evaluates it in each low-resolution pixel it taps (round 1; the fallback for down-sampling geometries, where blocks are not
+    // contiguous runs)
+    static int slots = 0;
+    if (!slots) {
         slots = 1024;                                   // resident workgroups of the block kernel on the whole device
 #ifndef CFFM_EMU
         int per_cu = 0, dev = 0, cus = 0;
@@ -2436,20 +2144,17 @@ int cffm_upce_maps_bwd(const float* logits, const long long* labels, const int* 
             per_cu > 0 && cus > 0)
             slots = per_cu * cus;
 #endif
-        form = (e && e[0] == 'g') ? 1 : 0;
     }
-    if ((form == 0 || !plain) && H >= h && W >= w) {
+    if (H >= h && W >= w) {
         // owned cell rows per workgroup: the ring row costs (ty + 1) / ty, a partly filled last wave of workgroups costs its idle slots
         const int TXo = UPCE_BLK_COLS - 1, gxb = (w + TXo - 1) / TXo, cpw = UPCE_BLK_THREADS / UPCE_BLK_COLS, nch = (UPCE_KP(K) / 4 + cpw - 1) / cpw;
-        int ty = ty_env;
-        if (ty <= 0) {
-            double best = -1.0;
-            for (int t = 2; t <= 16 && t <= std::max(h, 2); ++t) {
-                const long nwg = (long)M * gxb * ((h + t - 1) / t) * nch;
-                const long waves = (nwg + slots - 1) / slots;
-                const double eff = (double)t / (t + 1) * (double)nwg / (double)(waves * slots);
-                if (eff > best) { best = eff; ty = t; }
-            }
+        int ty = 0;
+        double best = -1.0;
+        for (int t = 2; t <= 16 && t <= std::max(h, 2); ++t) {
+            const long nwg = (long)M * gxb * ((h + t - 1) / t) * nch;
+            const long waves = (nwg + slots - 1) / slots;
+            const double eff = (double)t / (t + 1) * (double)nwg / (double)(waves * slots);
+            if (eff > best) { best = eff; ty = t; }
         }
         UpceBlkGeom Bk;
         Bk.ty = ty;
@@ -2558,19 +2263,6 @@ int cffm_rows_resize_bwd(const float* ddst, long ddst_map_stride, float* dsrc, l
 }
 
 // ------------------------------------------------------------------------------------------- clip data path
-int cffm_clip_format(const unsigned char* frames, const unsigned char* labels, float* out_img, long long* out_lab, int T, int H, int W,
-                     int y1, int x1, int ch, int cw, int flip, int Ho, int Wo, const float mean[3], const float std[3], int to_rgb,
-                     float pad_val, int seg_pad_val, int reduce_zero_label, void* stream) {
-    return cffm_clip_format_photo(frames, labels, out_img, out_lab, T, H, W, y1, x1, ch, cw, flip, Ho, Wo, mean, std, to_rgb, pad_val,
-                                  seg_pad_val, reduce_zero_label, nullptr, nullptr, stream);
-}
-int cffm_clip_format_photo(const unsigned char* frames, const unsigned char* labels, float* out_img, long long* out_lab, int T, int H, int W,
-                           int y1, int x1, int ch, int cw, int flip, int Ho, int Wo, const float mean[3], const float std[3], int to_rgb,
-                           float pad_val, int seg_pad_val, int reduce_zero_label, const float* brightness_beta, const float* contrast_alpha,
-                           void* stream) {
-    return cffm_clip_format_hsv(frames, labels, out_img, out_lab, T, H, W, y1, x1, ch, cw, flip, Ho, Wo, mean, std, to_rgb, pad_val, seg_pad_val,
-                                reduce_zero_label, brightness_beta, contrast_alpha, nullptr, nullptr, nullptr, stream);
-}
 int cffm_clip_format_hsv(const unsigned char* frames, const unsigned char* labels, float* out_img, long long* out_lab, int T, int H, int W,
                          int y1, int x1, int ch, int cw, int flip, int Ho, int Wo, const float mean[3], const float std[3], int to_rgb,
                          float pad_val, int seg_pad_val, int reduce_zero_label, const float* brightness_beta, const float* contrast_alpha,
@@ -2699,14 +2391,12 @@ int cffm_layer_backward_rows(const cffm_geom* g, int depth, const cffm_block_par
     // the reference frames of every block in one pass + the CFFA parameter gradients, then the last block's parameter-gradient tail
     RedJobs* tail_jobs = nullptr;
 #ifndef CFFM_EMU
-    if (tail_on_main() && g_tail.has) {
-        if (g_tail.cs) (void)hipStreamWaitEvent((hipStream_t)stream, g_side.cs_order, 0);
-        g_tail.has = g_tail.cs = false;
+    if (g_tail.has) {     // the last block's record reductions ride in the CFFA's final reduction launch
+        g_tail.has = false;
         tail_jobs = &g_tail.jobs;
     }
 #endif
     TRY(cffa_finish(g, depth, params, grads, depth - 1, 0, blk0, L.total, x_rows, 4 * img, dx_rows, 4 * img, 0, stream, tail_jobs));
-    TRY(tail_flush((hipStream_t)stream, tail_on_main()));
     side_join_all((hipStream_t)stream);
     return 0;
 }
@@ -2722,12 +2412,10 @@ static int layer_forward_impl(const cffm_geom* g, int depth, const cffm_block_pa
     const long HW = g->HW, img = HW * CFFM_C;
     float* xs = saved;  // NHWC stack [B,4,HW,C]
     float* blk0 = saved + up((long)g->B * 4 * img);
-    // the parameter-derived tables do not depend on x: they are built on the side stream while the input is transposed
+    // the parameter-derived tables do not depend on x: they are built in the launch of the input transpose, or beside it
     hipStream_t st = (hipStream_t)stream;
     side_init(st);
-    static int fused_prep = -1;      // CFFM_PREP_FUSED=0: the prep on the side stream beside the transpose (A/B)
-    if (fused_prep < 0) { const char* e = cffm_tune("CFFM_PREP_FUSED"); fused_prep = (e && e[0] == '0') ? 0 : 1; }
-    if (fused_prep && depth <= PREP_MAXD) {
+    if (depth <= PREP_MAXD) {
         // ONE launch: the input transpose (frames 0..2 also copied to y_full) + the parameter prep of every block (k_transpose_prep)
         PROF(ST_TRANSPOSE);
         PrepArgs a;
@@ -2739,19 +2427,15 @@ static int layer_forward_impl(const cffm_geom* g, int depth, const cffm_block_pa
         CHECK_LAUNCH("transpose + param_prep");
         g_prep_join.pending = false;
     } else {
-    side_fork_mark(st, 0);
-    // NCHW -> NHWC of the four frames; frames 0..2 also go to y_full as they are (the reference's pass-through frames) with the same read
-    TRY(transpose_add(x_nchw, xs, g->B * 4, CFFM_C, (int)HW, img, img, nullptr, 4, 3, stream, y_full));
-    hipStream_t sd = side_fork_take(st, 0);
-    TRY(param_prep(params, depth, blk0, L.total, L, (void*)sd));
-    side_mark(sd, st, 0);
-    {
-        static int early = -1;           // CFFM_PREP_JOIN=early: join in front of the first block (A/B)
-        if (early < 0) { const char* e = cffm_tune("CFFM_PREP_JOIN"); early = (e && e[0] == 'e') ? 1 : 0; }
-        g_prep_join.pending = sd != st && !early;      // joined behind the first block's ln_pool_fwd (block_forward_impl)
+        // deeper layers: the prep on the side stream while the input is transposed
+        side_fork_mark(st, 0);
+        // NCHW -> NHWC of the four frames; frames 0..2 also go to y_full as they are (the reference's pass-through frames) with the same read
+        TRY(transpose_add(x_nchw, xs, g->B * 4, CFFM_C, (int)HW, img, img, nullptr, 4, 3, stream, y_full));
+        hipStream_t sd = side_fork_take(st, 0);
+        TRY(param_prep(params, depth, blk0, L.total, L, (void*)sd));
+        side_mark(sd, st, 0);
+        g_prep_join.pending = sd != st;      // joined behind the first block's ln_pool_fwd (block_forward_impl)
         g_prep_join.side = sd;
-        if (!g_prep_join.pending) side_join(sd, st, 0);
-    }
     }
 #ifndef CFFM_EMU
     g_side.used = 0;   // (that was this call's only side branch, joined here)
@@ -2820,22 +2504,17 @@ static int layer_backward_impl(const cffm_geom* g, int depth, const cffm_block_p
     // that every block's gradient slice is complete when its range returns.
     RedJobs* tail_jobs = nullptr;
 #ifndef CFFM_EMU
-    if (last_block == 0 && tail_on_main() && g_tail.has) {     // the last block's record reductions ride in the CFFA's final reduction launch
-        if (g_tail.cs) (void)hipStreamWaitEvent((hipStream_t)stream, g_side.cs_order, 0);
-        g_tail.has = g_tail.cs = false;
+    if (last_block == 0 && g_tail.has) {     // the last block's record reductions ride in the CFFA's final reduction launch
+        g_tail.has = false;
         tail_jobs = &g_tail.jobs;
     }
 #endif
     TRY(cffa_finish(g, depth, params, grads, first_block, last_block, blk0, L.total, xs, 4 * img, dxs, 4 * img, first_block != depth - 1, stream, tail_jobs));
     // (dy_full: the upstream gradient of the whole [B,4,C,H,W] output -- its pass-through frames 0..2 join dx in the same pass)
-    if (last_block == 0) {
-        // the last block's parameter-gradient tail stays on the caller's stream, in front of the output transpose: no fork behind the
-        // last ln_pool_bwd at all (the transpose on a side stream of its own was queued AHEAD of the blocks' side work by the graph
-        // executor and held it up until the chain had finished: 0.95 ms per step)
-        hipStream_t st = (hipStream_t)stream;
-        if (tail_on_main()) TRY(tail_flush(st, true));
-        TRY(transpose_add(dxs, dx_nchw, g->B * 4, (int)HW, CFFM_C, img, img, dy_full, 4, 3, stream));
-    }
+    // (so the last block's parameter-gradient tail stays on the caller's stream, in front of the output transpose: no fork behind the last
+    // ln_pool_bwd at all -- the transpose on a side stream of its own was queued AHEAD of the blocks' side work by the graph executor and
+    // held it up until the chain had finished: 0.95 ms per step)
+    if (last_block == 0) TRY(transpose_add(dxs, dx_nchw, g->B * 4, (int)HW, CFFM_C, img, img, dy_full, 4, 3, stream));
     TRY(tail_flush((hipStream_t)stream));
     side_join_all((hipStream_t)stream);   // every parameter gradient of the range is complete behind this point of the stream
     return 0;

@@ -3,9 +3,7 @@
 // products per fp32 product, fp32 accumulate).  There is no library GEMM behind this file: rounds 1-3 carried a dlopen-ed
 // rocBLAS SGEMM as a cross-check (CFFM_GEMM=lib); it left with the rest of the alternative code paths in round 4.
 #pragma once
-#include <stdlib.h>
 #include "gemm_kernels.h"
-#include "dw_kernels.h"
 #include "dws_kernels.h"
 
 // ---- hand-written split-bf16 MFMA path (default) -------------------------------------------------------------
@@ -46,14 +44,9 @@ static int gemm_split_launch(const float* A, const float* B, float* C, int M, in
                 B, out, M, N, K, lda, ldb, ldc, klen, split_stride, bias, aux, aux2); } while (0)
     // measured on MI355X (scripts/gemm_bench.py, CFFM-B1 shapes): 128x128 wins when it already gives >= 384 workgroups
     // (qkv / fc1 forward, the 1024-wide input gradient), 64x64 otherwise; prefetch depth beyond the listed one is neutral.
-    static int sel = -1;   // tuning aid: CFFM_GEMM_SEL = 1 -> 128x64 tiles, 2 -> 64x128, 3 -> 128x128 for the small cases
-    if (sel < 0) { const char* e = cffm_tune("CFFM_GEMM_SEL"); sel = e ? atoi(e) : 0; }
     if (b128 >= 384 || prefer_big) {
         GEMM_GO(128, 128, 32, 1);   // a second K-tile in flight in registers: neutral (k-contiguous forms) or one workgroup per CU (others)
-    } else if (sel == 1) GEMM_GO(128, 64, 32, 2);
-    else if (sel == 2) GEMM_GO(64, 128, 32, 2);
-    else if (sel == 3) GEMM_GO(128, 128, 32, 1);
-    else GEMM_GO(64, 64, 32, 3);
+    } else GEMM_GO(64, 64, 32, 3);
 #undef GEMM_GO
     if (ksplit > 1) {
         const long n4 = split_stride / 4;
@@ -65,52 +58,13 @@ static int gemm_split_launch(const float* A, const float* B, float* C, int M, in
 static int gemm_nt_split(const float* x, const float* w, float* y, long M, int N, int K, hipStream_t st) {
     return gemm_split_launch<false, false>(x, w, y, (int)M, N, K, K, K, N, 1, st);
 }
-// the same with the weight (and optionally the activation) in split-4 storage
-template <bool X_PRE>
-static int gemm_nt_split_pre(const float* x, const float* w_s, float* y, long M, int N, int K, hipStream_t st) {
-    return gemm_split_launch<false, false, 0, X_PRE, true>(x, w_s, y, (int)M, N, K, K, K, N, 1, st);
-}
-// hraw[M,N] = x w^T (raw, kept for backward), act = gelu(hraw + b)      (fc1 of the Mlp, cffm_transformer.py:21-22)
-static int gemm_nt_gelu_split(const float* x, const float* w, const float* b, float* hraw, float* act, long M, int N, int K, hipStream_t st) {
-    return gemm_split_launch<false, false, 1>(x, w, hraw, (int)M, N, K, K, K, N, 1, st, b, act);
-}
-// x, w and the written act all in split-4 storage
-static int gemm_nt_gelu_split_pre(const float* x_s, const float* w_s, const float* b, float* hraw, float* act_s, long M, int N, int K,
-                                  hipStream_t st) {
-    return gemm_split_launch<false, false, 5, true, true>(x_s, w_s, hraw, (int)M, N, K, K, K, N, 1, st, b, act_s);
-}
-// out[M,N] = res + x w^T + b                                             (fc2 + residual, cffm_transformer.py:824)
-static int gemm_nt_residual_split(const float* x, const float* w, const float* b, const float* res, float* out, long M, int N, int K,
-                                  hipStream_t st) {
-    return gemm_split_launch<false, false, 2>(x, w, out, (int)M, N, K, K, K, N, 1, st, b, const_cast<float*>(res));
-}
-static int gemm_nt_residual_split_pre(const float* x_s, const float* w_s, const float* b, const float* res, float* out, long M, int N,
-                                      int K, hipStream_t st) {
-    return gemm_split_launch<false, false, 2, true, true>(x_s, w_s, out, (int)M, N, K, K, K, N, 1, st, b, const_cast<float*>(res));
-}
 // qkv16[M,768] (f16) = (x w^T + b) with the q third pre-scaled                (qkv Linear feeding the CFM kernels)
 static int gemm_nt_qkv16_split(const float* x, const float* w, const float* b, h16* qkv16, long M, int N, int K, hipStream_t st) {
     return gemm_split_launch<false, false, 3>(x, w, nullptr, (int)M, N, K, K, K, N, 1, st, b, (float*)qkv16);
 }
-static int gemm_nt_qkv16_split_pre(const float* x_s, const float* w_s, const float* b, h16* qkv16, long M, int N, int K, hipStream_t st) {
-    return gemm_split_launch<false, false, 3, true, true>(x_s, w_s, nullptr, (int)M, N, K, K, K, N, 1, st, b, (float*)qkv16);
-}
 // dx[M,K] = dy[M,N] w[N,K]: output cols = K, contraction = N
 static int gemm_nn_split(const float* dy, const float* w, float* dx, long M, int N, int K, hipStream_t st) {
     return gemm_split_launch<false, true>(dy, w, dx, (int)M, K, N, N, K, K, 1, st);
-}
-// dh[M,K] = (dy[M,N] w[N,K]) * gelu'(hraw + b1), in split-4 storage or plain; part[2 * ceil(M/128) * 2][K] = column-sum
-// records of dh (the bias gradient of fc1).  Always 128x128 tiles (the record layout is theirs).
-#define GEMM_GELUBWD_RECORDS(M) (4 * (((M) + 127) / 128))
-template <bool SPLIT_OUT>
-static int gemm_nn_gelubwd_split_pre(const float* dy, const float* w_s, const float* hraw, const float* b1, float* dh, float* part,
-                                     long M, int N, int K, hipStream_t st) {
-    return gemm_split_launch<false, true, SPLIT_OUT ? 7 : 6, false, true>(dy, w_s, dh, (int)M, K, N, N, K, K, 1, st, b1,
-                                                                          const_cast<float*>(hraw), 1, part);
-}
-template <bool DY_PRE>
-static int gemm_nn_split_pre(const float* dy, const float* w_s, float* dx, long M, int N, int K, hipStream_t st) {
-    return gemm_split_launch<false, true, 0, DY_PRE, true>(dy, w_s, dx, (int)M, K, N, N, K, K, 1, st);
 }
 // dw[N,K] = dy[M,N]^T x[M,K]: output N x K, contraction = M (long) split over workgroups
 template <bool DY_PRE = false, bool X_PRE = false>
@@ -138,8 +92,7 @@ static size_t gemm_tn_group_partial_floats(const GemmTN* pr, int n, int target_w
         if (pr[p].N % 128 || pr[p].K % 128 || pr[p].M < 32) return 0;
         units += (long)(pr[p].N / 128) * (pr[p].K / 128) * ((pr[p].M + 31) / 32);
     }
-    const char* e = cffm_tune("CFFM_GROUP_WGS");
-    const int env = e ? atoi(e) : 0, target = env > 0 ? env : (target_wgs > 0 ? target_wgs : 480);
+    const int target = target_wgs > 0 ? target_wgs : 480;
     long ksteps = (units + target - 1) / target;
     if (ksteps < 4) ksteps = 4;
     const long klen = ksteps * 32;
@@ -174,9 +127,7 @@ static int gemm_tn_group_split(const GemmTN* pr, int n, hipStream_t st, const Ge
     // one slice length for every problem: ~480 workgroups (two per CU are co-resident: 80 KB of LDS each)
     long units = 0;
     for (int p = 0; p < n; ++p) units += (long)(pr[p].N / 128) * (pr[p].K / 128) * ((pr[p].M + 31) / 32);
-    static int target_env = -1;   // tuning aid: CFFM_GROUP_WGS
-    if (target_env < 0) { const char* e = cffm_tune("CFFM_GROUP_WGS"); target_env = e ? atoi(e) : 0; if (target_env < 0) target_env = 0; }
-    const int target = target_env ? target_env : (target_wgs > 0 ? target_wgs : 480);
+    const int target = target_wgs > 0 ? target_wgs : 480;
     long ksteps = (units + target - 1) / target;
     if (ksteps < 4) ksteps = 4;
     const int klen = (int)ksteps * 32;
@@ -220,70 +171,8 @@ static int gemm_tn_group_split(const GemmTN* pr, int n, hipStream_t st, const Ge
     // 8 KB more LDS than the tiles need: ONE workgroup of the group per CU instead of two.  Two fill a CU's LDS exactly, and the CFFA
     // backward that runs beside the group in a block backward (69 KB per workgroup) then finds no slot until the group's workgroups
     // finish; with one per CU the two kernels really share the CUs: the group 62 -> 70 us, k_ln_pool_bwd 85 -> 77, step 0.717-0.730 ->
-    // 0.713-0.722 ms (same box, three alternating runs; 256 / 384 / 512 workgroups instead of 480: slower).  CFFM_DW_LDS_PAD=0: two per CU.
-    static int lds_pad = -1;
-    if (lds_pad < 0) { const char* e = cffm_tune("CFFM_DW_LDS_PAD"); lds_pad = e ? atoi(e) : 8192; if (lds_pad < 0 || lds_pad > 16384) lds_pad = 8192; }
-    CFFM_LAUNCH(k_gemm_group_tt, ((unsigned)wg), (256), GEMM_LDS(128, 128, 32) + lds_pad, st, G);
-    if (after_gemm) after_gemm(st);
-    if (nsum) {
-        Sg.cnt = nsum;
-        for (int q = nsum; q < 4; ++q) { Sg.part[q] = nullptr; Sg.out[q] = nullptr; Sg.n[q] = 0; Sg.nsplit[q] = 0; Sg.blk_end[q] = blk; }
-        CFFM_LAUNCH(k_sum_splits_group, ((unsigned)blk), (256), 0, st, Sg);
-    }
-    return 0;
-}
-
-// ---- weight gradients with both operands in split-4 storage: the LDS-DMA kernel (dw_kernels.h), up to DWD_MAX problems per launch ----
-static size_t dw_dma_partial_floats(const GemmTN* pr, int n, int target_wgs, int* klen_out) {
-    long units = 0;
-    for (int p = 0; p < n; ++p) units += (long)(pr[p].N / 128) * (pr[p].K / 128) * ((pr[p].M + 31) / 32);
-    long ksteps = (units + target_wgs - 1) / target_wgs;
-    if (ksteps < 4) ksteps = 4;
-    const long klen = ksteps * 32;
-    size_t part = 0;
-    for (int p = 0; p < n; ++p) {
-        const long ks = (pr[p].M + klen - 1) / klen;
-        if (ks > 1) part += (size_t)ks * pr[p].N * pr[p].K;
-    }
-    *klen_out = (int)klen;
-    return part;
-}
-// `part`: dw_dma_partial_floats(...) floats of slab scratch (or NULL when that is 0)
-static int dw_group_dma(const GemmTN* pr, int n, hipStream_t st, float* part, int target_wgs, void (*after_gemm)(hipStream_t) = nullptr) {
-    if (n < 1 || n > DWD_MAX) return -1;
-    for (int p = 0; p < n; ++p)
-        if (pr[p].N % 128 || pr[p].K % 128 || pr[p].M < 1 || (long)pr[p].M * pr[p].N * 4 >= (1L << 32) || (long)pr[p].M * pr[p].K * 4 >= (1L << 32)) return -1;
-    int klen;
-    const size_t need = dw_dma_partial_floats(pr, n, target_wgs, &klen);
-    if (need && !part) return -1;
-    DwGroup G;
-    SumGroup Sg;
-    int wg = 0, blk = 0, nsum = 0;
-    for (int p = 0; p < n; ++p) {
-        const int ks = (int)((pr[p].M + klen - 1) / klen);
-        G.A[p] = pr[p].dy; G.B[p] = pr[p].x; G.N[p] = pr[p].N; G.K[p] = pr[p].K; G.M[p] = (int)pr[p].M;
-        G.C[p] = pr[p].dw;
-        if (ks > 1) {
-            G.C[p] = part;
-            Sg.part[nsum] = part; Sg.out[nsum] = pr[p].dw; Sg.n[nsum] = (long)pr[p].N * pr[p].K; Sg.nsplit[nsum] = ks;
-            blk += (int)((Sg.n[nsum] / 4 + 255) / 256);
-            Sg.blk_end[nsum] = blk;
-            ++nsum;
-            part += (size_t)ks * pr[p].N * pr[p].K;
-        }
-        wg += (pr[p].N / 128) * (pr[p].K / 128) * ks;
-        G.wg_end[p] = wg;
-    }
-    for (int p = n; p < DWD_MAX; ++p) { G.A[p] = G.B[p] = nullptr; G.C[p] = nullptr; G.N[p] = G.K[p] = 128; G.M[p] = 0; G.wg_end[p] = wg; }
-    G.klen = klen; G.n = n;
-#ifndef CFFM_EMU
-    static bool granted = false;
-    if (!granted) {
-        if (hipFuncSetAttribute((const void*)k_dw_dma, hipFuncAttributeMaxDynamicSharedMemorySize, DWD_LDS) != hipSuccess) return -1;
-        granted = true;
-    }
-#endif
-    CFFM_LAUNCH(k_dw_dma, ((unsigned)wg), (256), DWD_LDS, st, G);
+    // 0.713-0.722 ms (same box, three alternating runs; 256 / 384 / 512 workgroups instead of 480: slower).
+    CFFM_LAUNCH(k_gemm_group_tt, ((unsigned)wg), (256), GEMM_LDS(128, 128, 32) + 8192, st, G);
     if (after_gemm) after_gemm(st);
     if (nsum) {
         Sg.cnt = nsum;
@@ -327,11 +216,7 @@ static bool dw_stream_plan(const GemmTN* pr, int n, int target_wgs, DwsPlan* P) 
     }
     return true;
 }
-static int dw_stream_target() {      // tuning aid: CFFM_DWS_WGS
-    static int v = -1;
-    if (v < 0) { const char* e = cffm_tune("CFFM_DWS_WGS"); v = e ? atoi(e) : 0; if (v < 1) v = 256; }
-    return v;
-}
+static int dw_stream_target() { return 256; }      // workgroups a streaming group aims for: one per CU
 // pr[p].dy / .x: T-frag storage of dy [M][N] / x [M][K] (rows past M zero); `part`: plan.part_floats floats of slab scratch (or NULL when 0)
 static int dw_group_stream(const GemmTN* pr, int n, hipStream_t st, float* part, int target_wgs, void (*after_gemm)(hipStream_t) = nullptr) {
     DwsPlan P;

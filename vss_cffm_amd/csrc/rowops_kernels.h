@@ -1,9 +1,7 @@
 // rowops_kernels.h -- HBM-bound row-wise kernels around the GEMMs of one CFFM block:
 //   bias table assembly / scatter      (cffm_transformer.py:536-587)
-//   residual + LayerNorm(norm2)        (cffm_transformer.py:823-824)
-//   bias + exact-erf GELU              (Mlp, cffm_transformer.py:10-26)
-//   final residual                     (cffm_transformer.py:824)
-//   column sums for the Linear bias gradients.
+//   LayerNorm backward with residual   (cffm_transformer.py:823-824)
+//   column sums for the Linear bias gradients, split-K sums, the AdamW update.
 // One wave per 256-channel row (1 KiB coalesced f32x4 accesses), 4 rows per workgroup.
 #pragma once
 #include "cffm_common.h"
@@ -192,30 +190,6 @@ __global__ void __launch_bounds__(256) k_bias_scatter(const float* __restrict__ 
 }
 #define BIAS_SCATTER_THREADS (CFFM_HEADS * 49 * 132 + 16 * (169 * CFFM_HEADS + CFFM_HEADS * (121 + 169 + 121 + 81)))
 
-// --------------------------------------------------------------------------- x1 = xt + (yraw + bproj); z2 = LN2(x1)
-__global__ void __launch_bounds__(256) k_residual_ln(const float* __restrict__ xt, long xt_bs, int rows_per_batch,
-                                                      const float* __restrict__ yraw, const float* __restrict__ bproj,
-                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                      float* __restrict__ x1, float* __restrict__ z2,
-                                                      float* __restrict__ mean_out, float* __restrict__ rstd_out, long nrows,
-                                                      int split /* z2 in split-4 storage */) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= nrows) return;
-    const long b = row / rows_per_batch, r = row % rows_per_batch;
-    const f32x4 a = *(const f32x4*)(xt + b * xt_bs + r * CFFM_C + 4 * lane);
-    const f32x4 y = *(const f32x4*)(yraw + row * CFFM_C + 4 * lane) + *(const f32x4*)(bproj + 4 * lane);
-    const f32x4 v = a + y;
-    *(f32x4*)(x1 + row * CFFM_C + 4 * lane) = v;
-    const float mu = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.f / CFFM_C);
-    const f32x4 d = v - mu;
-    const float var = wave_sum(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]) * (1.f / CFFM_C);
-    const float rs = 1.f / sqrtf(var + CFFM_LN_EPS);
-    const f32x4 zv = d * rs * *(const f32x4*)(gamma + 4 * lane) + *(const f32x4*)(beta + 4 * lane);
-    *(f32x4*)(z2 + row * CFFM_C + 4 * lane) = split ? split4_pack(zv) : zv;
-    if (lane == 0) { mean_out[row] = mu; rstd_out[row] = rs; }
-}
-
 // backward of z2 = LN(x1): dx1 = dres + LNbwd(dz2).  Every workgroup writes one partial record
 // part[blk][1024] = dgamma | dbeta | colsum(dres) | colsum(dx1) (the last two are the fc2 / proj bias
 // gradients, folded in because this kernel streams those rows anyway); k_reduce_partials sums them.
@@ -345,64 +319,6 @@ __global__ void __launch_bounds__(1024) k_reduce_records_multi(RedJobs J) {
     reduce_records_body(J.part[j], J.nblk[j], J.stride[j], J.total[j], J.segs[j], blk, red);
 }
 
-// dst = src in split-4 storage; n4 groups of 4 floats
-__global__ void __launch_bounds__(256) k_split4(const float* __restrict__ src, float* __restrict__ dst, long n4) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) ((f32x4*)dst)[i] = split4_pack(((const f32x4*)src)[i]);
-}
-
-// --------------------------------------------------------------------------- act = gelu(hraw + b1)
-__global__ void __launch_bounds__(256) k_bias_gelu(const float* __restrict__ hraw, const float* __restrict__ b1,
-                                                    float* __restrict__ act, long n4, int ncol4) {
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n4; e += (long)gridDim.x * 256) {
-        const f32x4 v = ((const f32x4*)hraw)[e] + ((const f32x4*)b1)[e % ncol4];
-        f32x4 o;
-        o[0] = gelu_erf(v[0]); o[1] = gelu_erf(v[1]); o[2] = gelu_erf(v[2]); o[3] = gelu_erf(v[3]);
-        ((f32x4*)act)[e] = o;
-    }
-}
-// dhraw = dact * gelu'(hraw + b1) (in place on dact); thread t owns columns 4t..4t+3 of the 1024, a workgroup
-// owns `rows_per_block` rows and writes colsum partials part[blk][1024] (fc1 bias gradient) when part != NULL.
-#define GELU_BWD_ROWS 16   // rows per workgroup (rows_per_block of the launch must equal it), read in batches of 4
-__global__ void __launch_bounds__(256, 4) k_gelu_bwd(const float* __restrict__ hraw, const float* __restrict__ b1,
-                                                      float* __restrict__ dact, float* __restrict__ part, long nrows,
-                                                      int split /* result in split-4 storage */) {
-    const int t = threadIdx.x;
-    const f32x4 bb = ((const f32x4*)b1)[t];
-    f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-    // dact is updated in place: a load issued after a store to the same array cannot be hoisted by the compiler, so the
-    // rows go in batches of 4, every row of a batch read before the first is written (8 independent 16-byte loads per lane);
-    // the ~75 registers leave six waves per SIMD to cover the batch boundaries
-    for (long r0 = (long)blockIdx.x * GELU_BWD_ROWS; r0 < (long)(blockIdx.x + 1) * GELU_BWD_ROWS && r0 < nrows; r0 += 4) {
-        f32x4 v[4], d[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            v[k] = d[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (r0 + k < nrows) {
-                v[k] = ((const f32x4*)(hraw + (r0 + k) * CFFM_HID))[t];
-                d[k] = ((const f32x4*)(dact + (r0 + k) * CFFM_HID))[t];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (r0 + k >= nrows) break;
-            const f32x4 x = v[k] + bb;
-            f32x4 o = d[k];
-            o[0] *= gelu_erf_grad(x[0]); o[1] *= gelu_erf_grad(x[1]); o[2] *= gelu_erf_grad(x[2]); o[3] *= gelu_erf_grad(x[3]);
-            ((f32x4*)(dact + (r0 + k) * CFFM_HID))[t] = split ? split4_pack(o) : o;
-            acc += o;
-            sched_fence();   // one row's arithmetic at a time: keeps the register count low
-        }
-    }
-    if (part) ((f32x4*)(part + (long)blockIdx.x * CFFM_HID))[t] = acc;
-}
-
-// --------------------------------------------------------------------------- out = x1 + (oraw + b2)
-__global__ void __launch_bounds__(256) k_residual_out(const float* __restrict__ x1, const float* __restrict__ oraw,
-                                                       const float* __restrict__ b2, float* __restrict__ out, long n4) {
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n4; e += (long)gridDim.x * 256)
-        ((f32x4*)out)[e] = ((const f32x4*)x1)[e] + ((const f32x4*)oraw)[e] + ((const f32x4*)b2)[e % (CFFM_C / 4)];
-}
-
 // --------------------------------------------------------------------------- column sums (Linear bias grads)
 // part[slice][c] = sum over the slice's rows of a[r][c]; grid (ncol/256, nslices); k_reduce_partials finishes.
 #define COLSUM_ROWS 32   // rows per workgroup
@@ -484,69 +400,8 @@ __global__ void __launch_bounds__(256) k_sum_splits_group(SumGroup G) {
 // p, m, v out), every one a 16-byte access per lane when the chunk is 16-byte aligned.  A multi-tensor launch whose
 // chunks are 64 K elements leaves most of the 256 CUs idle on a 1.6 M-parameter model; 2 K-element chunks give ~800
 // workgroups and the update runs at the HBM rate.
-struct AdamwChunk { float* p; const float* g; float* m; float* v; long n; };
-__global__ void __launch_bounds__(256) k_adamw(const AdamwChunk* __restrict__ chunks, float decay /* 1 - lr*wd */, float beta1,
-                                                float beta2, float omb1 /* 1 - beta1, rounded from double */, float omb2, float eps,
-                                                float step_size /* lr / bc1 */, float inv_sqrt_bc2) {
-    const AdamwChunk c = chunks[blockIdx.x];
-    const bool vec = (((uintptr_t)c.p | (uintptr_t)c.g | (uintptr_t)c.m | (uintptr_t)c.v) & 15) == 0;
-    const long n4 = vec ? c.n / 4 : 0;
-    for (long e = threadIdx.x; e < n4; e += 256) {
-        f32x4 p = ((const f32x4*)c.p)[e], m = ((const f32x4*)c.m)[e], v = ((const f32x4*)c.v)[e];
-        const f32x4 g = ((const f32x4*)c.g)[e];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            m[k] = beta1 * m[k] + omb1 * g[k];
-            v[k] = beta2 * v[k] + omb2 * g[k] * g[k];
-            p[k] = p[k] * decay - step_size * (m[k] / (sqrtf(v[k]) * inv_sqrt_bc2 + eps));
-        }
-        ((f32x4*)c.p)[e] = p; ((f32x4*)c.m)[e] = m; ((f32x4*)c.v)[e] = v;
-    }
-    for (long e = 4 * n4 + threadIdx.x; e < c.n; e += 256) {
-        const float g = c.g[e];
-        const float m = beta1 * c.m[e] + omb1 * g, v = beta2 * c.v[e] + omb2 * g * g;
-        c.m[e] = m; c.v[e] = v;
-        c.p[e] = c.p[e] * decay - step_size * (m / (sqrtf(v) * inv_sqrt_bc2 + eps));
-    }
-}
-
-// Graph-capturable variant: the step count and the two bias-correction factors live in device memory (state[0] = t as a
-// float, state[1] = lr / (1 - b1^t), state[2] = 1 / sqrt(1 - b2^t)); k_adamw_tick advances them on the stream, so a captured
-// training step replays with the right t every time.  `grad_base` != NULL: the chunk table's g field is a BYTE OFFSET from
-// it (the layer's gradients share one buffer whose address may change from step to step -- the table never does).
-__global__ void k_adamw_tick(float* __restrict__ state, double lr, double beta1, double beta2) {
-    const double t = (double)state[0] + 1.0;
-    state[0] = (float)t;
-    state[1] = (float)(lr / (1.0 - pow(beta1, t)));
-    state[2] = (float)(1.0 / sqrt(1.0 - pow(beta2, t)));
-}
-__global__ void __launch_bounds__(256) k_adamw_dev(const AdamwChunk* __restrict__ chunks, const float* __restrict__ grad_base, float decay,
-                                                    float beta1, float beta2, float omb1, float omb2, float eps,
-                                                    const float* __restrict__ state) {
-    AdamwChunk c = chunks[blockIdx.x];
-    if (grad_base) c.g = (const float*)((const char*)grad_base + (uintptr_t)c.g);
-    const float step_size = state[1], inv_sqrt_bc2 = state[2];
-    const bool vec = (((uintptr_t)c.p | (uintptr_t)c.g | (uintptr_t)c.m | (uintptr_t)c.v) & 15) == 0;
-    const long n4 = vec ? c.n / 4 : 0;
-    for (long e = threadIdx.x; e < n4; e += 256) {
-        f32x4 p = ((const f32x4*)c.p)[e], m = ((const f32x4*)c.m)[e], v = ((const f32x4*)c.v)[e];
-        const f32x4 g = ((const f32x4*)c.g)[e];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            m[k] = beta1 * m[k] + omb1 * g[k];
-            v[k] = beta2 * v[k] + omb2 * g[k] * g[k];
-            p[k] = p[k] * decay - step_size * (m[k] / (sqrtf(v[k]) * inv_sqrt_bc2 + eps));
-        }
-        ((f32x4*)c.p)[e] = p; ((f32x4*)c.m)[e] = m; ((f32x4*)c.v)[e] = v;
-    }
-    for (long e = 4 * n4 + threadIdx.x; e < c.n; e += 256) {
-        const float g = c.g[e];
-        const float m = beta1 * c.m[e] + omb1 * g, v = beta2 * c.v[e] + omb2 * g * g;
-        c.m[e] = m; c.v[e] = v;
-        c.p[e] = c.p[e] * decay - step_size * (m / (sqrtf(v) * inv_sqrt_bc2 + eps));
-    }
-}
-
+// `grad_base` != NULL: the chunk table's g field is a BYTE OFFSET from it (the layer's gradients share one buffer whose address may
+// change from step to step -- the table never does).
 // Multi-group form (one launch for EVERY parameter group of the optimizer): a chunk names the ROW of the hyper-parameter
 // tables it is updated with.  Per row: consts[ADAMW_NCONST] (double: beta1, beta2, eps, schedule kind, max_iters, power, min_lr,
 // warmup_iters, warmup_ratio, first iteration, and -- slot 10, the one WRITTEN here -- the optimizer's global iteration count), sched[2] (float: base lr, weight decay -- a device copy of a pinned host mirror,

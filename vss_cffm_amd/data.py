@@ -5,7 +5,7 @@ Reference: ``CustomDataset_video2`` (mmseg/datasets/custom.py:1959) picks the fr
 edge cases :2366-2388 -- and runs the pipeline of local_configs/_base_/datasets/vspw_repeat2.py:8-19 on them, frame by frame in
 numpy / cv2 inside the dataloader workers.  Here the random DECISIONS are drawn on the host in the reference's order (same numpy /
 ``random`` calls, so a seeded run picks the same crop and flip), and crop + flip + BGR->RGB + normalisation + padding + CHW stacking
-are ONE kernel over the whole clip (``cffm_clip_format_photo``, csrc/clip_kernels.h), including the brightness / contrast steps of
+are ONE kernel over the whole clip (``cffm_clip_format_hsv``, csrc/clip_kernels.h), including the brightness / contrast steps of
 ``PhotoMetricDistortion_clips`` (``PhotoMetricDistortionClips``).  Not covered: image decoding, the random rescale and the test-time
 ``AlignedResize_clips`` (cv2's fixed-point bilinear resize) and the saturation / hue steps of the photometric distortion (cv2's 8-bit
 HSV conversion) -- none of them can be pinned without cv2, which neither box has; they stay upstream of ``ClipFormatter`` (frames

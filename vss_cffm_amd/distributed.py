@@ -2,7 +2,7 @@
 
 The reference trains under MMDistributedDataParallel (mmseg/apis/train.py:57-65): parameters broadcast from rank 0 once,
 gradients averaged over the ranks every step, the exchange overlapped with the backward pass by the bucketed reducer.
-`_LayerFn.backward` produces every parameter gradient of the layer in ONE buffer laid out block by block (the .grad tensors
+`_LayerFullFn.backward` (and `_LayerRowsFn.backward`) produces every parameter gradient of the layer in ONE buffer laid out block by block (the .grad tensors
 are views of it) and runs the blocks last-to-first, so the exchange here is one all-reduce PER BLOCK, started as soon as that
 block's kernels are enqueued and travelling over xGMI while the previous block's backward runs (`BlockwiseReducer`) -- no
 per-parameter reducer hooks, no 52 copies into a bucket, no gradient-ready bookkeeping.  `allreduce_gradients` is the
@@ -35,7 +35,7 @@ def allreduce_gradients(params, average=True, grads=None):
         return 0
     bases = None
     # fast path: every gradient is a dense slice of the FIRST one's storage (autograd hands the layer's gradient views over as
-    # aliases of the one buffer `_LayerFn.backward` allocated) -> one flat span of that storage, found with address
+    # aliases of the one buffer `_LayerFullFn.backward` allocated) -> one flat span of that storage, found with address
     # arithmetic only
     g0 = grads[0]
     st = g0.untyped_storage()
@@ -51,7 +51,7 @@ def allreduce_gradients(params, average=True, grads=None):
     if ok:
         bases = [torch.empty(0, dtype=torch.float32, device=g0.device).set_(st, (lo - s_lo) // 4, ((hi - lo) // 4,))]
     else:   # general case: per storage, merge only ADJACENT or overlapping gradient ranges (a gap of <= 3 elements counts as
-        #         adjacent: 16-byte alignment padding, which `_LayerFn.backward` zero-fills) and reduce every merged range on its
+        #         adjacent: 16-byte alignment padding, which `_LayerFullFn.backward` zero-fills) and reduce every merged range on its
         #         own -- other data living between two gradient views of one storage is never touched
         spans, bases = {}, []
         for g in grads:
@@ -87,7 +87,7 @@ def allreduce_gradients(params, average=True, grads=None):
 class BlockwiseReducer:
     """Gradient exchange overlapped with the backward pass, block by block.
 
-    ``_LayerFn.backward`` runs the layer's blocks last-to-first and lays every block's parameter gradients out as one
+    ``_LayerFullFn.backward`` runs the layer's blocks last-to-first and lays every block's parameter gradients out as one
     contiguous slice of the flat gradient buffer.  With this reducer installed it hands each slice over as soon as that block's
     kernels are enqueued; the reducer starts an asynchronous all-reduce of the slice (RCCL runs it on its own stream, ordered
     after the compute stream's position at that moment), so block i's exchange travels over xGMI while block i - 1's backward

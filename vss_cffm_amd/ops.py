@@ -171,93 +171,12 @@ block_grad_hook = None
 current_backward_params = None
 
 
-class _LayerFn(torch.autograd.Function):
-    """BasicLayer3d3.forward (cffm_transformer.py:917-927) as one custom op: x [B,T,256,H,W] and the
-    26*depth block parameters -> the new target frame [B,256,H,W]."""
-
-    @staticmethod
-    def forward(ctx, x, depth, *params):
-        lib = _lib.get()
-        _require_device(x, 'cffm layer input')
-        if x.dim() != 5 or x.shape[2] != 256:
-            raise _lib.CffmError('expected x [B,T,256,H,W], got %s' % (tuple(x.shape),))
-        if x.shape[1] != 4:
-            # the reference indexes reference frames 0..2 and the target [-1] (cffm_transformer.py:780-792)
-            raise IndexError('CFFM block needs T == 4 frames (3 reference + target), got T=%d' % x.shape[1])
-        assert len(params) == NPB * depth
-        b, _, _, h0, w0 = x.shape
-        x = x.contiguous()
-        for p in params:
-            if not p.is_contiguous() or p.dtype != torch.float32:
-                raise _lib.CffmError('cffm layer parameters must be contiguous float32')
-        g = make_geom(lib, b, h0, w0)
-        key_src, q_dst, inv_ptr, inv_idx = device_tables(h0, w0, x.device)
-        saved = torch.empty(lib.cffm_layer_saved_floats(C.byref(g), depth), dtype=torch.float32, device=x.device)
-        scratch = torch.empty(lib.cffm_layer_scratch_floats(C.byref(g)), dtype=torch.float32, device=x.device)
-        y = torch.empty(b, 256, h0, w0, dtype=torch.float32, device=x.device)
-        pstructs = block_structs(params, depth)
-        _lib.check(lib.cffm_layer_forward(C.byref(g), depth, pstructs, _ptr(x), _ptr(y), _ptr(key_src), _ptr(q_dst),
-                                          _ptr(saved), _ptr(scratch), _stream(x)), lib)
-        ctx.depth, ctx.geom_args = depth, (b, h0, w0)
-        ctx.save_for_backward(saved, key_src, q_dst, inv_ptr, inv_idx, *params)
-        ctx.scratch = scratch
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.get()
-        saved, key_src, q_dst, inv_ptr, inv_idx, *params = ctx.saved_tensors
-        depth = ctx.depth
-        b, h0, w0 = ctx.geom_args
-        g = make_geom(lib, b, h0, w0)
-        # dy is normally the last-frame slice of the [B,4,256,H,W] upstream gradient (the torch.cat in cffm_layer): dense inside
-        # a clip, 4 images apart between clips -- handed over with its batch stride instead of being copied
-        img = 256 * h0 * w0
-        if dy.dim() == 4 and dy.stride()[1:] == (h0 * w0, w0, 1) and (b == 1 or dy.stride(0) >= img):
-            dy_bs = dy.stride(0) if b > 1 else img
-        else:
-            dy, dy_bs = dy.contiguous(), img
-        # one allocation for every parameter gradient (16-byte aligned slices), returned as views
-        sizes = [(p.numel() + 3) // 4 * 4 for p in params]
-        # (the <= 12-byte padding gaps between slices travel through the gradient all-reduce with them and must not carry NaN / Inf
-        # bit patterns of recycled memory: the library zeroes them inside the backward of the pooling Linears -- the only tensors
-        # with a gap behind them -- see cffm_grad_slices_padded in include/cffm_hip.h; a zero-fill of the whole 6.8 MB buffer was a
-        # 7 us kernel on the chain in front of the backward, an index_fill_ of the gaps still a 4.7 us one)
-        flat = torch.empty(sum(sizes), dtype=torch.float32, device=dy.device)
-        grads = [c[:p.numel()].view(p.shape) if c.numel() != p.numel() else c.view(p.shape)
-                 for c, p in zip(flat.split(sizes), params)]
-        dx = torch.empty(b, 4, 256, h0, w0, dtype=torch.float32, device=dy.device)
-        pstructs = block_structs(params, depth)
-        gstructs = block_structs(grads, depth)
-        hook = block_grad_hook
-        if hook is None:
-            _checked_padded(lib, lib.cffm_layer_backward, C.byref(g), depth, pstructs, gstructs, _ptr(dy), dy_bs, _ptr(dx), _ptr(key_src),
-                                               _ptr(q_dst), _ptr(inv_ptr), _ptr(inv_idx), _ptr(saved), _ptr(ctx.scratch),
-                                               _stream(dy))
-        else:
-            # block by block (last block first, as the chain runs): once a block's kernels are enqueued its slice of the
-            # flat gradient buffer is handed to the hook -- data-parallel training starts that block's all-reduce there,
-            # overlapping it with the backward of the blocks still to come (vss_cffm_amd.distributed.BlockwiseReducer)
-            per = sum(sizes[:NPB])
-            global current_backward_params
-            current_backward_params = params
-            try:
-                for i in range(depth - 1, -1, -1):
-                    _checked_padded(lib, lib.cffm_layer_backward_range, C.byref(g), depth, pstructs, gstructs, _ptr(dy), dy_bs, _ptr(dx),
-                                                             _ptr(key_src), _ptr(q_dst), _ptr(inv_ptr), _ptr(inv_idx), _ptr(saved),
-                                                             _ptr(ctx.scratch), i, i, _stream(dy))
-                    hook(i, flat[i * per:(i + 1) * per], depth)
-            finally:
-                current_backward_params = None
-        return (dx, None) + tuple(grads)
-
-
 class LayerPieces:
     """The layer's forward and backward as explicit pieces over STATIC buffers, without autograd: what a data-parallel training
     loop replays from HIP graphs when it wants the gradient exchange of block i to overlap the backward of block i - 1 --
     graph(forward + backward of the last blocks) | all-reduce(those blocks' gradient slices, asynchronous) | graph(backward of
-    block 0) | all-reduce(block 0's slice) | graph(optimizer)  (bench.py, N > 1).  The same library calls, in the same order,
-    as ``_LayerFn``; ``grads`` are views of one flat buffer (``flat``), ``block_slice(i)`` is block i's part of it."""
+    block 0) | all-reduce(block 0's slice) | graph(optimizer)  (bench.py, N > 1).  ``cffm_layer_forward`` / ``cffm_layer_backward_range``
+    on the new target frame; ``grads`` are views of one flat buffer (``flat``), ``block_slice(i)`` is block i's part of it."""
 
     def __init__(self, x, depth, params):
         lib = _lib.get()
@@ -344,8 +263,13 @@ class _LayerFullFn(torch.autograd.Function):
         b, h0, w0 = ctx.geom_args
         g = make_geom(lib, b, h0, w0)
         dy = dy.contiguous()
+        # one allocation for every parameter gradient (16-byte aligned slices), returned as views
         sizes = [(p.numel() + 3) // 4 * 4 for p in params]
-        flat = torch.empty(sum(sizes), dtype=torch.float32, device=dy.device)       # (the library zeroes the alignment gaps: see _LayerFn.backward)
+        # (the <= 12-byte padding gaps between slices travel through the gradient all-reduce with them and must not carry NaN / Inf
+        # bit patterns of recycled memory: the library zeroes them inside the backward of the pooling Linears -- the only tensors
+        # with a gap behind them -- see cffm_grad_slices_padded in include/cffm_hip.h; a zero-fill of the whole 6.8 MB buffer was a
+        # 7 us kernel on the chain in front of the backward, an index_fill_ of the gaps still a 4.7 us one)
+        flat = torch.empty(sum(sizes), dtype=torch.float32, device=dy.device)
         grads = [c[:p.numel()].view(p.shape) if c.numel() != p.numel() else c.view(p.shape)
                  for c, p in zip(flat.split(sizes), params)]
         dx = torch.empty(b, 4, 256, h0, w0, dtype=torch.float32, device=dy.device)
@@ -370,11 +294,6 @@ def cffm_layer(x, depth, params):
     """x [B,4,256,H,W]; params: flat list of 26*depth tensors (BLOCK_PARAM_KEYS order per block).
     Returns the reference's output [B,4,256,H,W]: frames 0..2 are the input, frame 3 is new."""
     return _LayerFullFn.apply(x, depth, *params)
-
-
-def cffm_layer_target(x, depth, params):
-    """the new target frame only, [B,256,H,W] (callers that use nothing else: cffm_head.py:145)"""
-    return _LayerFn.apply(x, depth, *params)
 
 
 # ---------------------------------------------------------------------------------------------- NCHW <-> token rows
@@ -703,7 +622,7 @@ class _CatIntoFn(torch.autograd.Function):
 _DEFERRED = []         # tensors the deferred branch (cffm_defer_begin) still touches; cleared by _join_deferred
 
 
-def _join_deferred(t=None):
+def _join_deferred():
     """the caller's stream continues behind the deferred branch (no-op when nothing is pending): called by whoever consumes deferred results
     (bn_relu_pool's backward) and once more at the end of every backward pass that deferred something"""
     if _DEFERRED:
@@ -843,7 +762,7 @@ def cat_into(x, x2):
 # ---------------------------------------------------------------------------------------------- the layer on token rows
 class _LayerRowsFn(torch.autograd.Function):
     """BasicLayer3d3 on channels-last token rows: x_rows [B,4,H*W,256] -> the new target frame [B,H*W,256].  Same kernels as
-    _LayerFn without the four NCHW <-> NHWC transposes (the heads' neighbours of the hot path work on rows too)."""
+    _LayerFullFn without the four NCHW <-> NHWC transposes (the heads' neighbours of the hot path work on rows too)."""
 
     @staticmethod
     def forward(ctx, x_rows, h0, w0, depth, *params):
@@ -875,7 +794,7 @@ class _LayerRowsFn(torch.autograd.Function):
         g = make_geom(lib, b, h0, w0)
         dy = dy.contiguous()
         sizes = [(p.numel() + 3) // 4 * 4 for p in params]
-        flat = torch.empty(sum(sizes), dtype=torch.float32, device=dy.device)       # (the library zeroes the alignment gaps: see _LayerFn.backward)
+        flat = torch.empty(sum(sizes), dtype=torch.float32, device=dy.device)       # (the library zeroes the alignment gaps: see _LayerFullFn.backward)
         grads = [c[:p.numel()].view(p.shape) for c, p in zip(flat.split(sizes), params)]
         dx = torch.empty(b, 4, h0 * w0, 256, dtype=torch.float32, device=dy.device)
         _checked_padded(lib, lib.cffm_layer_backward_rows, C.byref(g), depth, block_structs(params, depth), block_structs(grads, depth), _ptr(x_rows),

@@ -21,7 +21,7 @@ walks the table with one workgroup per chunk.  A chunk names the ROW of three sm
 A row is a (parameter group, step count) pair: parameters that first receive a gradient later than the rest of their group
 (un-freezing, conditionally used branches) get a row -- and a bias correction -- of their own, as torch's per-parameter
 step does; a row advances its step count only in the steps in which one of its parameters has a gradient (the chunk table
-carries a flag per row), so intermittently used parameters keep torch's bias correction and schedule iteration.  When all gradients alias one buffer -- what ``_LayerFn.backward`` produces -- the table stores their byte
+carries a flag per row), so intermittently used parameters keep torch's bias correction and schedule iteration.  When all gradients alias one buffer -- what ``_LayerFullFn.backward`` / ``_LayerRowsFn.backward`` produce -- the table stores their byte
 offsets inside it and the buffer's address is a kernel argument: the table is built once, wherever the allocator puts the
 gradients.  Otherwise (DistributedDataParallel bucket views, foreign gradients) it stores absolute addresses and is
 rebuilt only when one of them changes.  The cache key covers every address the table holds (parameters, gradients, both
