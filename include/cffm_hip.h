@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CFFM_ABI_VERSION 11
+#define CFFM_ABI_VERSION 12
 
 typedef struct cffm_geom {
     int B, H0, W0;      /* clips, unpadded 1/8-scale grid                                   */
@@ -321,6 +321,26 @@ int cffm_layer_forward_rows(const cffm_geom* g, int depth, const cffm_block_para
 int cffm_layer_backward_rows(const cffm_geom* g, int depth, const cffm_block_params* params, const cffm_block_grads* grads,
                              const float* x_rows, const float* dy_rows, float* dx_rows, const int* key_src, const int* q_dst,
                              const int* inv_ptr, const int* inv_idx, const float* saved, float* scratch, void* stream);
+
+/* ---- ABI 12: the layer's forward for inference (nothing is kept for a backward) ----
+ * The same kernels as the training forward in store-free instantiations: the output equals cffm_layer_forward_rows / _forward_full
+ * bit for bit.  What depends on the parameters alone -- per block the f16 position-bias fragments, the pooling matrix and the
+ * forward-form fragment-ordered copies of the four Linear weights -- is prepared ONCE per set of weights:
+ *   cffm_layer_prepared_floats: floats of `prepared` for a layer of `depth` blocks (independent of the geometry);
+ *   cffm_layer_prepare:         fills it; call again whenever a parameter has changed;
+ *   cffm_layer_infer_ws_floats: floats of the transient workspace `ws` (zall | f16 q|k|v | ao | two x2 buffers the blocks
+ *                               ping-pong between): independent of depth, contents undefined before and after a call;
+ *   cffm_layer_infer_rows:      x_rows [B,4,HW,256] -> y_rows [B,HW,256] (the new target frame), channels-last on both sides;
+ *   cffm_layer_infer_full:      x [B,4,256,H0,W0] -> y_full [B,4,256,H0,W0], frames 0..2 = the input frames
+ *                               (y_full also serves as scratch during the call; it must not alias x).
+ * Everything is enqueued on `stream` alone (no side streams, no allocation): a call captured into a HIP graph is one chain. */
+long cffm_layer_prepared_floats(int depth);
+int cffm_layer_prepare(int depth, const cffm_block_params* params, float* prepared, void* stream);
+long cffm_layer_infer_ws_floats(const cffm_geom* g);
+int cffm_layer_infer_rows(const cffm_geom* g, int depth, const cffm_block_params* params, const float* prepared, const float* x_rows,
+                          float* y_rows, const int* key_src, const int* q_dst, float* ws, void* stream);
+int cffm_layer_infer_full(const cffm_geom* g, int depth, const cffm_block_params* params, const float* prepared, const float* x_nchw,
+                          float* y_full_nchw, const int* key_src, const int* q_dst, float* ws, void* stream);
 
 /* ---- `linear_fuse`'s BatchNorm + ReLU and the 1/4 -> 1/8 resize that builds the clip stack (cffm_head.py:119, :131-135), on token
  * rows [pixels,256].  With even H, W the bilinear 1/2 resize (align_corners=False) is exactly a 2x2 average.

@@ -10,7 +10,7 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libcffm_hip.so')
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 vp, ci, cl, cd, cf = C.c_void_p, C.c_int, C.c_long, C.c_double, C.c_float
 
@@ -105,6 +105,11 @@ SIGNATURES = {
     'cffm_vc_counts': (ci, [vp, vp, ci, cl, ci, vp, vp]),
     'cffm_layer_forward_rows': (ci, [GP, ci, BP, vp, vp, vp, vp, vp, vp, vp]),
     'cffm_layer_backward_rows': (ci, [GP, ci, BP, BP, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    'cffm_layer_prepared_floats': (cl, [ci]),
+    'cffm_layer_prepare': (ci, [ci, BP, vp, vp]),
+    'cffm_layer_infer_ws_floats': (cl, [GP]),
+    'cffm_layer_infer_rows': (ci, [GP, ci, BP, vp, vp, vp, vp, vp, vp, vp]),
+    'cffm_layer_infer_full': (ci, [GP, ci, BP, vp, vp, vp, vp, vp, vp, vp]),
     'cffm_colstats_records': (cl, [cl]),
     'cffm_colstats': (ci, [vp, cl, vp, vp]),
     'cffm_bn_relu_pool_records': (cl, [ci, ci, ci]),

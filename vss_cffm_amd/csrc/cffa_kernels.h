@@ -194,6 +194,10 @@ __device__ __forceinline__ int frame_group(int frame) { return frame == 3 ? 0 : 
 #define LNP_PIX ((CFFM_WA + LNP_WAVES - 1) / LNP_WAVES)      // pixel rows per wave
 // (six waves per SIMD = three workgroups per CU: all 648 workgroups of a B = 2 launch resident at once instead of 512 + a 136-workgroup
 // second round -- 80 VGPRs with one spilled dword; 17.0 -> 15.2 us.  Four per CU would need 64 VGPRs: 87 spills)
+// INFER = true: the forward of a call that keeps nothing for a backward (the inference forward of the layer) -- mean_out / rstd_out are
+// not written and the pooling matrix always comes prepared (M != NULL; pw is not read).  Selected at compile time: the training
+// instantiation is the kernel it was, and the arithmetic of the two is the same, instruction for instruction.
+template <bool INFER>
 __global__ void __launch_bounds__(LNP_THREADS, 6) k_ln_pool_fwd(Geo G, const float* __restrict__ x_ref, long ref_bs,
                                                       const float* __restrict__ x_tgt, long tgt_bs,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -208,7 +212,8 @@ __global__ void __launch_bounds__(LNP_THREADS, 6) k_ln_pool_fwd(Geo G, const flo
     int g0, ncell;
     frame_cells(frame, g0, ncell);
     // (M == NULL: the first block of a layer forward, so that this kernel does not wait for the side-stream parameter prep)
-    for (int e = threadIdx.x; e < ncell * CFFM_WA; e += LNP_THREADS) sM[e] = M ? M[g0 * CFFM_WA + e] : pool_matrix_entry(pw, g0 + e / CFFM_WA, e % CFFM_WA);
+    for (int e = threadIdx.x; e < ncell * CFFM_WA; e += LNP_THREADS)
+        sM[e] = (INFER || M) ? M[g0 * CFFM_WA + e] : pool_matrix_entry(pw, g0 + e / CFFM_WA, e % CFFM_WA);
     __syncthreads();
     const float* xf = (frame == 3) ? x_tgt + (long)b * tgt_bs : x_ref + (long)b * ref_bs + (long)frame * G.HW * CFFM_C;
     const f32x4 gm = *(const f32x4*)(gamma + 4 * lane), bt = *(const f32x4*)(beta + 4 * lane);
@@ -241,7 +246,7 @@ __global__ void __launch_bounds__(LNP_THREADS, 6) k_ln_pool_fwd(Geo G, const flo
                 const float var = wave_sum(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]) * (1.f / CFFM_C);
                 const float rs = 1.f / sqrtf(var + CFFM_LN_EPS);
                 z = d * rs * gm + bt;
-                if (lane == 0) {
+                if (!INFER && lane == 0) {
                     mean_out[((long)b * 4 + frame) * G.HW + pix] = mu;
                     rstd_out[((long)b * 4 + frame) * G.HW + pix] = rs;
                 }

@@ -749,7 +749,7 @@ static int ln_pool_fwd_impl(const cffm_geom* g, const float* x_ref, long ref_bs,
     PoolB pb;
     PoolW pw;
     for (int i = 0; i < 4; ++i) { pb.b[i] = pool_b[i]; pw.w[i] = pool_w ? pool_w[i] : nullptr; }
-    CFFM_LAUNCH(k_ln_pool_fwd, (g->nW, 4, g->B), (LNP_THREADS), 0, (hipStream_t)stream, to_geo(g), x_ref, ref_bs, x_tgt, tgt_bs, gamma,
+    CFFM_LAUNCH(k_ln_pool_fwd<false>, (g->nW, 4, g->B), (LNP_THREADS), 0, (hipStream_t)stream, to_geo(g), x_ref, ref_bs, x_tgt, tgt_bs, gamma,
                 beta, pool_w ? nullptr : M, pw, pb, zall, mean, rstd, split);
     CHECK_LAUNCH("ln_pool_fwd");
     return 0;
@@ -934,7 +934,7 @@ int cffm_attn_fwd(const cffm_geom* g, const void* qkv16, const int* key_src, con
     REQUIRE(g && qkv16 && key_src && q_dst && biasH && ao && lse, "attn_fwd: null");
     const h16* bias = (const h16*)biasH;
     // one workgroup per (window, head), four per CU
-    CFFM_LAUNCH(k_cfm_attn_fwd, (g->B * g->nW * CFFM_HEADS), (256), ATT_FWD_LDS, (hipStream_t)stream, to_geo(g), (const h16*)qkv16,
+    CFFM_LAUNCH(k_cfm_attn_fwd<false>, (g->B * g->nW * CFFM_HEADS), (256), ATT_FWD_LDS, (hipStream_t)stream, to_geo(g), (const h16*)qkv16,
                 key_src, q_dst, bias, ao, lse);
     CHECK_LAUNCH("attn_fwd");
     return 0;
@@ -2461,6 +2461,170 @@ int cffm_layer_forward_full(const cffm_geom* g, int depth, const cffm_block_para
     REQUIRE(g && y_full_nchw && y_full_nchw != x_nchw, "layer_forward_full: bad arguments");
     const long img = g->HW * CFFM_C;
     return layer_forward_impl(g, depth, params, x_nchw, y_full_nchw + 3 * img, 4 * img, y_full_nchw, key_src, q_dst, saved, scratch, stream);
+}
+
+// ------------------------------------------------------------------------------------------- inference forward (ABI 12)
+// BasicLayer3d3.forward (cffm_transformer.py:917-927) for calls that autograd records nothing of: the same four kernels per block in their
+// store-free instantiations (k_ln_pool_fwd<true>, the q|k|v row-panel GEMM without its T-frag copy, k_cfm_attn_fwd<true>,
+// k_mlp_fwd<MT, D, true>) -- same arithmetic in the same order, so the output equals the training forward's bit for bit -- with
+//   * the parameter-only data (bias fragments, pooling matrix, forward-form fragment-ordered weights) in a buffer the caller prepares
+//     ONCE per set of weights (cffm_layer_prepare: k_param_prep on a grid that stops in front of the input-gradient forms),
+//   * one transient workspace that does not grow with depth: zall | f16 q|k|v | ao | two x2 buffers the blocks ping-pong between,
+//   * the last block's x2 written straight into the caller's rows,
+//   * every launch on the caller's stream, no library-side allocation: a captured call is a single chain.
+struct PreparedLayout { long bias, M, w_frag, total; };
+static PreparedLayout prepared_layout() {
+    PreparedLayout L;
+    long p = 0;
+    L.bias = p; p += up((long)BIASH_HALFS / 2);
+    L.M = p; p += up(CFFM_NCELL * CFFM_WA);
+    L.w_frag = p; p += up(PREP_WFLOATS);          // qkv | proj | fc1 | fc2, forward (NT) form
+    L.total = p;
+    return L;
+}
+struct InferWs { long zall, qkv, ao, x2[2], total; };
+static InferWs infer_ws_layout(const cffm_geom* g) {
+    const long B = g->B, HW = g->HW, RC = g->RC;
+    InferWs w;
+    long p = 0;
+    w.zall = p; p += up(B * RC * CFFM_C);
+    w.qkv = p; p += up(B * RC * 768 / 2);         // f16 q|k|v
+    w.ao = p; p += up(B * HW * CFFM_C);
+    w.x2[0] = p; p += up(B * HW * CFFM_C);
+    w.x2[1] = p; p += up(B * HW * CFFM_C);
+    w.total = p;
+    return w;
+}
+long cffm_layer_prepared_floats(int depth) { return depth < 1 ? -1 : depth * prepared_layout().total; }
+long cffm_layer_infer_ws_floats(const cffm_geom* g) { return (!g || g->B < 1 || g->HW < 1 || g->RC < 1) ? -1 : infer_ws_layout(g).total; }
+
+static int infer_lds_grant() {
+#ifndef CFFM_EMU
+    static bool granted = false;
+    if (!granted) {
+        if (hipFuncSetAttribute((const void*)k_mlp_fwd<MLP_MT, MLP_D, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PNL_FUSED_LDS(MLP_MT)) != hipSuccess ||
+            hipFuncSetAttribute((const void*)k_panel_gemm<2, 6, 2, 4, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, PNL_LDS(2)) != hipSuccess ||
+            hipFuncSetAttribute((const void*)k_panel_gemm<3, 6, 2, 4, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, PNL_LDS(3)) != hipSuccess)
+            return -1;
+        granted = true;
+    }
+#endif
+    return 0;
+}
+// Panel height of the inference Mlp kernel.  The training choice (MLP_MT = 2: 32 rows) leaves more than half of the 256 CUs idle when a
+// call has under 4096 rows (B = 1 on the 60 x 60 grid: 113 workgroups); 16-row panels then still fit one round (225 workgroups).  Measured
+// on the layer, depth 2, eager: 126.0 -> 119.3 us at 3600 rows; 16-row panels in two rounds lose (B = 2 60 x 60 166 -> 200 us, 60 x 108
+// 155 -> 189 us: every workgroup streams all 2.25 MB of weights), so the rule stops at one round.  Below 1024 rows nothing was measured:
+// the training choice stays.  Rows are independent and a row's sums keep their order: the output does not depend on the choice.
+static int infer_mlp_mt(long NP) { return (NP > 1024 && (NP + 15) / 16 <= 256) ? 1 : MLP_MT; }
+static int infer_check_params(const cffm_block_params* params, int depth, const char* who) {
+    for (int i = 0; i < depth; ++i) {
+        const cffm_block_params& p = params[i];
+        bool ok = p.norm1_w && p.norm1_b && p.rpb_own && p.rpb_ring && p.qkv_w && p.qkv_b && p.proj_w && p.proj_b && p.norm2_w && p.norm2_b &&
+                  p.fc1_w && p.fc1_b && p.fc2_w && p.fc2_b;
+        for (int q = 0; q < 4; ++q) ok = ok && p.pool_w[q] && p.pool_b[q] && p.rpb_pool[q];
+        REQUIRE(ok, "%s: null parameter in block %d", who, i);
+    }
+    return 0;
+}
+int cffm_layer_prepare(int depth, const cffm_block_params* params, float* prepared, void* stream) {
+    REQUIRE(params && prepared && depth >= 1, "layer_prepare: bad arguments");
+    TRY(infer_check_params(params, depth, "layer_prepare"));
+    REQUIRE(!infer_lds_grant(), "layer_prepare: LDS grant failed");     // (here, so that the first inference call may already be a captured one)
+    const PreparedLayout P = prepared_layout();
+    cffm_block_ws L = {};
+    L.bias = P.bias; L.M = P.M; L.w_frag = P.w_frag;     // (w_split is not written: pack 2)
+    PROF(ST_BIAS_ASM);
+    for (int d0 = 0; d0 < depth; d0 += PREP_MAXD) {
+        const int nd = (depth - d0 < PREP_MAXD) ? depth - d0 : PREP_MAXD;
+        PrepArgs a;
+        // the grid stops in front of the workgroups that write the input-gradient forms: only a backward reads those
+        const int pnx = prep_args(a, params, d0, nd, prepared, P.total, L) - PREP_FBLOCKS / 2;
+        CFFM_LAUNCH(k_param_prep, (pnx, nd), (256), 0, (hipStream_t)stream, a);
+    }
+    CHECK_LAUNCH("layer_prepare");
+    return 0;
+}
+
+// the blocks of one call: `stack` = NHWC frames [B,4,HW,256]; the last block's output rows [B,HW,256] go to `y_rows`
+static int layer_infer_blocks(const cffm_geom* g, int depth, const cffm_block_params* params, const float* prepared, const float* stack,
+                              float* y_rows, const int* key_src, const int* q_dst, float* ws, void* stream) {
+    REQUIRE(!infer_lds_grant(), "layer_infer: LDS grant failed");
+    const PreparedLayout P = prepared_layout();
+    const InferWs W = infer_ws_layout(g);
+    const long HW = g->HW, img = HW * CFFM_C, NR = (long)g->B * g->RC, NP = (long)g->B * HW;
+    REQUIRE(NP < (1L << 21), "layer_infer: bad sizes");
+    hipStream_t st = (hipStream_t)stream;
+    const Geo G = to_geo(g);
+    for (int i = 0; i < depth; ++i) {
+        const cffm_block_params* p = &params[i];
+        const float* pre = prepared + (long)i * P.total;
+        const float* wf = pre + P.w_frag;
+        const float* tgt = (i == 0) ? stack + 3 * img : ws + W.x2[(i - 1) & 1];
+        const long tgt_bs = (i == 0) ? 4 * img : img;
+        float* x2 = (i == depth - 1) ? y_rows : ws + W.x2[i & 1];
+        {
+            PROF(ST_LN_POOL_FWD);
+            PoolB pb;
+            for (int q = 0; q < 4; ++q) pb.b[q] = p->pool_b[q];
+            CFFM_LAUNCH(k_ln_pool_fwd<true>, (g->nW, 4, g->B), (LNP_THREADS), 0, st, G, stack, 4 * img, tgt, tgt_bs, p->norm1_w, p->norm1_b, pre + P.M,
+                        PoolW(), pb, ws + W.zall, nullptr, nullptr, 1);
+        }
+        {
+            PROF(ST_GEMM); PROF2(ST_G_QKV_FWD);
+            REQUIRE(!panel_qkv_fwd(ws + W.zall, wf, p->qkv_b, (h16*)(ws + W.qkv), NR, st, nullptr), "layer_infer: qkv gemm failed");
+        }
+        {
+            PROF(ST_ATTN_FWD);
+            CFFM_LAUNCH(k_cfm_attn_fwd<true>, (g->B * g->nW * CFFM_HEADS), (256), ATT_FWD_LDS, st, G, (const h16*)(ws + W.qkv), key_src, q_dst,
+                        (const h16*)(pre + P.bias), ws + W.ao, nullptr);
+        }
+        {
+            PROF(ST_GEMM); PROF2(ST_MLP_FWD);
+            MlpFwdArgs a = {};
+            a.ao = ws + W.ao; a.xt = tgt; a.xt_bs = tgt_bs; a.rows_per_batch = g->HW;
+            a.wp = (const f32x4*)(wf + 768 * 256); a.w1 = (const f32x4*)(wf + 768 * 256 + 256 * 256); a.w2 = (const f32x4*)(wf + 768 * 256 + 256 * 256 + 1024 * 256);
+            a.bp = p->proj_b; a.b1 = p->fc1_b; a.b2 = p->fc2_b; a.g2 = p->norm2_w; a.be2 = p->norm2_b;
+            a.x2 = x2; a.NP = (int)NP;
+            if (infer_mlp_mt(NP) == 1) {
+                CFFM_LAUNCH((k_mlp_fwd<1, MLP_D, true>), ((unsigned)((NP + 15) / 16)), (PNL_THREADS), PNL_FUSED_LDS(1), st, a);
+            } else {
+                CFFM_LAUNCH((k_mlp_fwd<MLP_MT, MLP_D, true>), ((unsigned)cffm_mlp_records(NP)), (PNL_THREADS), PNL_FUSED_LDS(MLP_MT), st, a);
+            }
+        }
+        CHECK_LAUNCH("layer_infer block");
+    }
+    return 0;
+}
+static int layer_infer_check(const cffm_geom* g, int depth, const cffm_block_params* params, const float* prepared, const void* x, const void* y,
+                             const int* key_src, const int* q_dst, const float* ws, const char* who) {
+    REQUIRE(g && params && prepared && x && y && key_src && q_dst && ws && depth >= 1, "%s: bad arguments", who);
+    REQUIRE(g->B >= 1 && g->HW == g->H0 * g->W0 && g->RC == 64 * g->nW && g->nW == g->gy * g->gx && g->nW >= 1, "%s: geometry not initialised", who);
+    REQUIRE(x != y, "%s: input and output must not alias", who);
+    return infer_check_params(params, depth, who);
+}
+int cffm_layer_infer_rows(const cffm_geom* g, int depth, const cffm_block_params* params, const float* prepared, const float* x_rows, float* y_rows,
+                          const int* key_src, const int* q_dst, float* ws, void* stream) {
+    TRY(layer_infer_check(g, depth, params, prepared, x_rows, y_rows, key_src, q_dst, ws, "layer_infer_rows"));
+    return layer_infer_blocks(g, depth, params, prepared, x_rows, y_rows, key_src, q_dst, ws, stream);
+}
+// The reference's whole output [B,4,C,H,W].  The NHWC stack the blocks read needs as much room as the output has: it is built IN
+// y_full (so the workspace stays what the rows form needs) and y_full gets its real contents when the last block is done -- frames
+// 0..2 copied from the input, frame 3 transposed from the last block's rows.
+int cffm_layer_infer_full(const cffm_geom* g, int depth, const cffm_block_params* params, const float* prepared, const float* x_nchw,
+                          float* y_full_nchw, const int* key_src, const int* q_dst, float* ws, void* stream) {
+    TRY(layer_infer_check(g, depth, params, prepared, x_nchw, y_full_nchw, key_src, q_dst, ws, "layer_infer_full"));
+    const InferWs W = infer_ws_layout(g);
+    const long HW = g->HW, img = HW * CFFM_C;
+    float* stack = y_full_nchw;
+    TRY(transpose_add(x_nchw, stack, g->B * 4, CFFM_C, (int)HW, img, img, nullptr, 1, -1, stream));
+    float* last = ws + W.x2[(depth - 1) & 1];
+    TRY(layer_infer_blocks(g, depth, params, prepared, stack, last, key_src, q_dst, ws, stream));
+    for (int b = 0; b < g->B; ++b)
+        REQUIRE(hipMemcpyAsync(y_full_nchw + (long)b * 4 * img, x_nchw + (long)b * 4 * img, (size_t)3 * img * sizeof(float), hipMemcpyDeviceToDevice,
+                               (hipStream_t)stream) == hipSuccess, "layer_infer_full: copy failed");
+    TRY(cffm_transpose(last, y_full_nchw + 3 * img, g->B, (int)HW, CFFM_C, img, 4 * img, stream));
+    return 0;
 }
 
 // blocks first_block, first_block - 1, ..., last_block of the layer backward (depth - 1 >= first >= last >= 0): the piece with

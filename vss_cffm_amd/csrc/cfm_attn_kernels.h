@@ -177,6 +177,8 @@ __device__ __forceinline__ void stage_kv(buf_t rs_qkv, uint32_t soff_k, const in
 //  not by the ds_write pass; the LDS-DMA leg, the ablation switches and the shader-clock stamps of rounds 2-5 live in the repository's
 //  history: scripts/README.md, "profiling legs")
 #define FWD_OCC 4   // workgroups per CU: 39.2 KB of LDS and <= 128 VGPRs each
+// INFER = true (the inference forward of the layer): nothing is kept for a backward -- lse_out is not written; same arithmetic otherwise
+template <bool INFER>
 __global__ void __launch_bounds__(256, FWD_OCC) k_cfm_attn_fwd(Geo G, const h16* __restrict__ qkv,
                                                        const int* __restrict__ key_src, const int* __restrict__ q_dst,
                                                        const h16* __restrict__ biasH, float* __restrict__ ao,
@@ -262,7 +264,7 @@ __global__ void __launch_bounds__(256, FWD_OCC) k_cfm_attn_fwd(Geo G, const h16*
     const float l = osum[0];      // every row of the ones-product is the column sum: l of query l15, in all four lane groups
 
     // ---- epilogue: normalise, un-window, drop padded pixels (cffm_transformer.py:812-821) ------------
-    if (g == 0) lse_out[((long)wb * CFFM_HEADS + h) * CFFM_NQ_PAD + qcol] = (qcol < CFFM_WA) ? m + logf(l) : 0.f;
+    if (!INFER && g == 0) lse_out[((long)wb * CFFM_HEADS + h) * CFFM_NQ_PAD + qcol] = (qcol < CFFM_WA) ? m + logf(l) : 0.f;
     if (qdst >= 0) {
         const float inv = 1.f / l;
         float* orow = ao + ((long)b * G.HW + qdst) * CFFM_C + h * CFFM_HD + 4 * g;

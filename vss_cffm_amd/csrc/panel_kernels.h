@@ -392,7 +392,11 @@ struct MlpFwdArgs {
     int NP;
 };
 
-template <int MT, int D>
+// INFER = true: the forward of a call that keeps nothing for a backward (the inference forward of the layer) -- of everything below
+// only x2 is stored (x1, the LayerNorm statistics, hraw and the split-4 / T-frag operand copies of the weight gradients are not, and
+// their pointers are not read).  Selected at compile time: the training instantiation is the kernel it was, and the arithmetic of the
+// two is the same, instruction for instruction.
+template <int MT, int D, bool INFER = false>
 __global__ void __launch_bounds__(PNL_THREADS) k_mlp_fwd(MlpFwdArgs a) {
     CFFM_DYN_SMEM(smem);
     bf16* P = (bf16*)smem;                         // ao panel, later the z2 panel
@@ -421,7 +425,7 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_fwd(MlpFwdArgs a) {
     }
     pnl_lds_barrier();
     const long NP32 = ((long)NP + 31) / 32 * 32;
-    if (a.ao_t) pnl_tfrag_store<MT>(P, P + PNL_IMG(MT), a.ao_t, m0, 0, 16, NP, NP32, wave, lane);
+    if (!INFER && a.ao_t) pnl_tfrag_store<MT>(P, P + PNL_IMG(MT), a.ao_t, m0, 0, 16, NP, NP32, wave, lane);
     const f32x4 z4 = (f32x4){0.f, 0.f, 0.f, 0.f};
     f32x4 acc[2][MT];
 #pragma unroll
@@ -454,7 +458,7 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_fwd(MlpFwdArgs a) {
             }
             const f32x4 v = acc[t][i] + bv + r;
             x1v[t][i] = v;
-            if (valid[i]) *(f32x4*)(a.x1 + mrow[i] * 256 + n) = v;
+            if (!INFER && valid[i]) *(f32x4*)(a.x1 + mrow[i] * 256 + n) = v;
             s[i] += (v[0] + v[1]) + (v[2] + v[3]);
         }
     }
@@ -487,7 +491,7 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_fwd(MlpFwdArgs a) {
 #pragma unroll
         for (int w = 0; w < PNL_WAVES; ++w) tot += red[(PNL_WAVES + w) * 16 * MT + 16 * i + l15];
         rs[i] = 1.f / sqrtf(tot * (1.f / 256) + CFFM_LN_EPS);
-        if (wave == 0 && g == 0 && valid[i]) { a.mean2[mrow[i]] = mu[i]; a.rstd2[mrow[i]] = rs[i]; }
+        if (!INFER && wave == 0 && g == 0 && valid[i]) { a.mean2[mrow[i]] = mu[i]; a.rstd2[mrow[i]] = rs[i]; }
     }
     // z2 -> the panel image (the ao image is dead: every wave finished its proj product before the first barrier above)
 #pragma unroll
@@ -500,11 +504,11 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_fwd(MlpFwdArgs a) {
             bf16x4 h, l;
             split4(zv, h, l);
             pnl_img_put(P, P + PNL_IMG(MT), 16 * i + l15, n, h, l);
-            if (valid[i] && a.z2s) *(f32x4*)(a.z2s + mrow[i] * 256 + n) = pnl_pack_hl(h, l);
+            if (!INFER && valid[i] && a.z2s) *(f32x4*)(a.z2s + mrow[i] * 256 + n) = pnl_pack_hl(h, l);
         }
     }
     pnl_lds_barrier();
-    if (a.z2_t) pnl_tfrag_store<MT>(P, P + PNL_IMG(MT), a.z2_t, m0, 0, 16, NP, NP32, wave, lane);
+    if (!INFER && a.z2_t) pnl_tfrag_store<MT>(P, P + PNL_IMG(MT), a.z2_t, m0, 0, 16, NP, NP32, wave, lane);
     // ---- Mlp: hidden chunks of 256 features: fc1 chunk -> GELU -> chunk image -> fc2 accumulates over the chunk
     f32x4 acc2[2][MT];
 #pragma unroll
@@ -531,14 +535,14 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_fwd(MlpFwdArgs a) {
                 bf16x4 h, l;
                 split4(av, h, l);
                 pnl_img_put(Ah, Ah + PNL_IMG(MT), 16 * i + l15, nl, h, l);
-                if (valid[i]) {
+                if (!INFER && valid[i]) {
                     *(f32x4*)(a.hraw + mrow[i] * 1024 + n) = raw;
                     if (a.acts) *(f32x4*)(a.acts + mrow[i] * 1024 + n) = pnl_pack_hl(h, l);
                 }
             }
         }
         pnl_lds_barrier();
-        if (a.act_t) pnl_tfrag_store<MT>(Ah, Ah + PNL_IMG(MT), a.act_t, m0, 16 * c, 64, NP, NP32, wave, lane);
+        if (!INFER && a.act_t) pnl_tfrag_store<MT>(Ah, Ah + PNL_IMG(MT), a.act_t, m0, 16 * c, 64, NP, NP32, wave, lane);
         const int cn = c < 3 ? c + 1 : 0;
         pnl_chunk_mma<MT, 2, 2, D>(acc2, ring, Ah, Ah + PNL_IMG(MT), s2, 2 * wave, 8 * c, l15, g, s1, 16 * cn + 2 * wave, 0);
     }
@@ -550,7 +554,7 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_fwd(MlpFwdArgs a) {
         for (int i = 0; i < MT; ++i)
             if (valid[i]) *(f32x4*)(a.x2 + mrow[i] * 256 + n) = x1v[t][i] + acc2[t][i] + bv;
     }
-    if (a.NP < 0) a.mean2[tid] = (float)touch;     // (never taken: keeps the warm-up loads)
+    if (a.NP < 0) (INFER ? a.x2 : a.mean2)[tid] = (float)touch;     // (never taken: keeps the warm-up loads)
 }
 
 struct MlpBwdArgs {

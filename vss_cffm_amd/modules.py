@@ -136,15 +136,54 @@ class BasicLayer3d3(nn.Module):
                                     focal_window=focal_window, focal_l_clips=focal_l_clips,
                                     focal_kernel_clips=focal_kernel_clips) for i in range(depth)])
         self.downsample = None
+        self._prep = None       # (key, tensor): the prepared parameter data of the inference forward, see _prepared()
+
+    # ---- inference path: taken when autograd would record nothing (ops.cffm_layer_infer / cffm_layer_rows_infer: same output, bit for
+    # bit, nothing saved for a backward, parameter-only data prepared once per set of weights instead of once per call)
+    @staticmethod
+    def _records_nothing(x, params):
+        return not torch.is_grad_enabled() or not (x.requires_grad or any(p.requires_grad for p in params))
+
+    def _prepared(self, params):
+        """The prepared parameter data (ops.layer_prepare) for the weights as they are NOW.  How the cache is kept valid:
+        * its key is (data_ptr, _version) of every block parameter: an in-place update through the parameter itself (p.add_ / p.copy_
+          under no_grad -- what torch's optimisers and load_state_dict do) bumps _version, a move (.to(), .cuda(), a re-assigned
+          .data) changes data_ptr;
+        * two kinds of writes bump NO version: vss_cffm_amd.optim.AdamW updates the parameters through raw pointers inside the
+          library, and `p.data` is a tensor with a version counter of its own (p.data.add_ leaves p._version alone).  The key alone
+          would serve stale weights after either.  So every train(mode) call -- train() AND eval() -- drops the cache: weights
+          change between a train() and the next eval(), and an evaluation calls eval() once and then forwards many times;
+        * loading a state dict drops it too (_load_from_state_dict).
+        Whoever writes parameter memory behind autograd's back and then forwards again WITHOUT a train() / eval() call in between
+        must call drop_prepared() themselves."""
+        key = tuple((p.data_ptr(), p._version) for p in params)
+        if self._prep is None or self._prep[0] != key:
+            self._prep = (key, ops.layer_prepare(self.depth, params))
+        return self._prep[1]
+
+    def drop_prepared(self):
+        self._prep = None
+
+    def train(self, mode=True):
+        self._prep = None       # eval() is train(False): both directions drop the cache, see _prepared()
+        return super().train(mode)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self._prep = None       # (runs for this module whenever it, or a module above it, loads a state dict)
+        return super()._load_from_state_dict(*args, **kwargs)
 
     def forward(self, x, batch_size=None, num_clips=None):
         params = [p for blk in self.blocks for p in blk.param_list()]
+        if self._records_nothing(x, params):
+            return ops.cffm_layer_infer(x, self.depth, params, self._prepared(params))
         return ops.cffm_layer(x, self.depth, params)
 
     def forward_rows(self, x_rows, h, w):
         """The same layer on channels-last token rows: x_rows [B, T=4, h*w, 256] -> the NEW TARGET FRAME only, [B, h*w, 256]
         (frames 0..2 of the reference's output are its input frames).  What the heads call: no NCHW <-> NHWC transposes."""
         params = [p for blk in self.blocks for p in blk.param_list()]
+        if self._records_nothing(x_rows, params):
+            return ops.cffm_layer_rows_infer(x_rows, h, w, self.depth, params, self._prepared(params))
         return ops.cffm_layer_rows(x_rows, h, w, self.depth, params)
 
 

@@ -809,6 +809,84 @@ def cffm_layer_rows(x_rows, h0, w0, depth, params):
     return _LayerRowsFn.apply(x_rows, h0, w0, depth, *params)
 
 
+# ---------------------------------------------------------------------------------------------- the layer without a backward
+# The inference forward (include/cffm_hip.h, ABI 12): plain functions, nothing recorded, nothing saved.  Same kernels in store-free
+# instantiations -- the result equals cffm_layer / cffm_layer_rows bit for bit.  `prepared` holds what depends on the parameters
+# alone (layer_prepare); the caller rebuilds it whenever a parameter changes (BasicLayer3d3 keeps one per module, modules.py).
+def _check_layer_params(params, depth):
+    if len(params) != NPB * depth:
+        raise _lib.CffmError('expected %d parameter tensors for depth %d, got %d' % (NPB * depth, depth, len(params)))
+    for p in params:
+        _require_device(p, 'cffm layer parameter')
+        if not p.is_contiguous():
+            raise _lib.CffmError('cffm layer parameters must be contiguous float32')
+
+
+def layer_prepare(depth, params):
+    """The parameter-only inputs of the inference forward for these 26 * depth tensors: per block the position-bias fragments, the
+    pooling matrix and the forward-form fragment-ordered Linear weights, in one tensor (``cffm_layer_prepare``)."""
+    lib = _lib.get()
+    _check_layer_params(params, depth)
+    dev = params[0].device
+    prepared = torch.empty(lib.cffm_layer_prepared_floats(depth), dtype=torch.float32, device=dev)
+    _lib.check(lib.cffm_layer_prepare(depth, block_structs(params, depth), _ptr(prepared), _stream(prepared)), lib)
+    return prepared
+
+
+def _infer_buffers(lib, g, depth, prepared, ws, out, out_shape, dev):
+    if prepared.dtype != torch.float32 or prepared.numel() < lib.cffm_layer_prepared_floats(depth) or prepared.device != dev:
+        raise _lib.CffmError('`prepared` does not belong to a layer of depth %d on %s (ops.layer_prepare)' % (depth, dev))
+    need = lib.cffm_layer_infer_ws_floats(C.byref(g))
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.float32, device=dev)
+    elif ws.dtype != torch.float32 or ws.numel() < need or ws.device != dev or not ws.is_contiguous():
+        raise _lib.CffmError('inference workspace: %d contiguous fp32 values on %s expected' % (need, dev))
+    if out is None:
+        out = torch.empty(out_shape, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != tuple(out_shape) or out.device != dev or not out.is_contiguous():
+        raise _lib.CffmError('inference output: contiguous fp32 %s on %s expected' % (tuple(out_shape), dev))
+    return ws, out
+
+
+def cffm_layer_infer(x, depth, params, prepared, ws=None, out=None):
+    """cffm_layer without autograd: x [B,4,256,H,W] -> [B,4,256,H,W] (frames 0..2 are the input frames).  ``ws`` / ``out``: optional
+    caller-owned workspace (``cffm_layer_infer_ws_floats`` floats) and result tensor, e.g. static buffers of a captured graph."""
+    lib = _lib.get()
+    _require_device(x, 'cffm layer input')
+    if x.dim() != 5 or x.shape[2] != 256:
+        raise _lib.CffmError('expected x [B,T,256,H,W], got %s' % (tuple(x.shape),))
+    if x.shape[1] != 4:
+        raise IndexError('CFFM block needs T == 4 frames (3 reference + target), got T=%d' % x.shape[1])
+    if len(params) != NPB * depth:         # (dtype / device / contiguity were checked when `prepared` was built from them)
+        raise _lib.CffmError('expected %d parameter tensors for depth %d, got %d' % (NPB * depth, depth, len(params)))
+    b, _, _, h0, w0 = x.shape
+    x = x.detach().contiguous()
+    g = make_geom(lib, b, h0, w0)
+    key_src, q_dst = device_tables(h0, w0, x.device)[:2]
+    ws, out = _infer_buffers(lib, g, depth, prepared, ws, out, (b, 4, 256, h0, w0), x.device)
+    _lib.check(lib.cffm_layer_infer_full(C.byref(g), depth, block_structs(params, depth), _ptr(prepared), _ptr(x), _ptr(out), _ptr(key_src),
+                                         _ptr(q_dst), _ptr(ws), _stream(x)), lib)
+    return out
+
+
+def cffm_layer_rows_infer(x_rows, h0, w0, depth, params, prepared, ws=None, out=None):
+    """cffm_layer_rows without autograd: x_rows [B,4,H*W,256] -> the new target frame [B,H*W,256]."""
+    lib = _lib.get()
+    _require_device(x_rows, 'cffm layer input')
+    if x_rows.dim() != 4 or x_rows.shape[1] != 4 or x_rows.shape[2] != h0 * w0 or x_rows.shape[3] != 256:
+        raise _lib.CffmError('expected x_rows [B,4,%d,256], got %s' % (h0 * w0, tuple(x_rows.shape)))
+    if len(params) != NPB * depth:
+        raise _lib.CffmError('expected %d parameter tensors for depth %d, got %d' % (NPB * depth, depth, len(params)))
+    x_rows = x_rows.detach().contiguous()
+    b = x_rows.shape[0]
+    g = make_geom(lib, b, h0, w0)
+    key_src, q_dst = device_tables(h0, w0, x_rows.device)[:2]
+    ws, out = _infer_buffers(lib, g, depth, prepared, ws, out, (b, h0 * w0, 256), x_rows.device)
+    _lib.check(lib.cffm_layer_infer_rows(C.byref(g), depth, block_structs(params, depth), _ptr(prepared), _ptr(x_rows), _ptr(out), _ptr(key_src),
+                                         _ptr(q_dst), _ptr(ws), _stream(x_rows)), lib)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- BN + ReLU + 1/8 clip stack
 class _BnReluPoolFn(torch.autograd.Function):
     """y [N,256,H,W] (channels-last memory) -> (fused = ReLU(BatchNorm(y)) [N,256,H,W] channels-last, stack = 2x2 average of
