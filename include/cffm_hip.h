@@ -14,6 +14,7 @@
  *   cffm_mlp_fwd / _bwd              <->  proj + residual + norm2 + Mlp + residual  :602, :823-824
  *   cffm_gtc_*                       <->  BasicLayer_cluster / WindowAttention_cluster (CFFM++)
  *                                                         pvt/swin_transformer_2d.py:1103-1148, :208-262
+ *   cffm_kmeans                      <->  KMeans(...).fit_predict of the prototype-generating head  cffm_head.py:280-282
  *
  * Conventions: every pointer is a DEVICE pointer (fp32 unless stated) borrowed for the duration of
  * the call; `stream` is a hipStream_t (NULL = default stream); work is enqueued asynchronously on it;
@@ -27,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CFFM_ABI_VERSION 12
+#define CFFM_ABI_VERSION 13
 
 typedef struct cffm_geom {
     int B, H0, W0;      /* clips, unpadded 1/8-scale grid                                   */
@@ -442,6 +443,21 @@ typedef struct {
  * sched is read by the device when the launch runs: it may be device memory or pinned, device-visible host memory. */
 int cffm_adamw_step_rows(const cffm_adamw_chunk2* chunks /* device */, int nchunks, const float* grad_base, float* state,
                          const float* sched, double* consts, int nrows, const int* active_rows, int* ticket, void* stream);
+
+/* ---- ABI 13: k-means on token rows (the prototype-generating stage of CFFM++, cffm_head.py:280-282) ----
+ * Lloyd's algorithm, euclidean, `iters` iterations, on x [N,256] for 1 <= K <= 128 centres, N >= K:
+ *   assign  label_i = argmin_j (|c_j|^2 - 2 x_i.c_j) on the matrix pipe (three-pass bf16 hi / lo split); bit-equal scores go to the
+ *           lowest centre index;
+ *   update  c_j = mean of the points labelled j (fixed summation order: the same bits on every run); a centre that attracted no
+ *           point keeps its value.
+ * centers_inout [K,256] holds the initial centres on entry and the result on return.  labels_out [N] / counts_out [K] (int32, either
+ * may be NULL) are those of the LAST ASSIGNMENT MADE, i.e. against the centres that entered the last iteration.
+ * workspace: cffm_kmeans_workspace_bytes(N, K) bytes (-1 for bad sizes), written before it is read.  All iterations are enqueued on
+ * `stream` by the one call (2 * iters + 1 kernels, no host round trip, no allocation): it can be captured into a HIP graph.
+ * x, centers_inout and workspace must be 16-byte aligned.  K < 1, K > 128, N < K, iters < 1 are errors. */
+long cffm_kmeans_workspace_bytes(long N, int K);
+int cffm_kmeans(const float* x, long N, int K, int iters, float* centers_inout, int* labels_out, int* counts_out, void* workspace,
+                void* stream);
 
 #ifdef __cplusplus
 }

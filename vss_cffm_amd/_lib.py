@@ -10,7 +10,7 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libcffm_hip.so')
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 vp, ci, cl, cd, cf = C.c_void_p, C.c_int, C.c_long, C.c_double, C.c_float
 
@@ -129,6 +129,8 @@ SIGNATURES = {
     'cffm_upce_maps_fwd': (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cl, cl, ci, ci, vp]),
     'cffm_upce_maps_bwd': (ci, [vp, vp, vp, vp, vp, vp, C.c_float, vp, ci, ci, ci, ci, ci, ci, ci, ci, cl, cl, ci, ci, vp]),
     'cffm_adamw_step_rows': (ci, [vp, ci, vp, vp, vp, vp, ci, vp, vp, vp]),
+    'cffm_kmeans_workspace_bytes': (cl, [cl, ci]),
+    'cffm_kmeans': (ci, [vp, cl, ci, ci, vp, vp, vp, vp, vp]),
 }
 
 

@@ -8,6 +8,7 @@
 #include "segfuse_kernels.h"
 #include "segloss_kernels.h"
 #include "headfuse_kernels.h"
+#include "kmeans_kernels.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -2703,6 +2704,76 @@ int cffm_layer_backward(const cffm_geom* g, int depth, const cffm_block_params* 
                         const int* inv_ptr, const int* inv_idx, const float* saved, float* scratch, void* stream) {
     return cffm_layer_backward_range(g, depth, params, grads, dy_tgt_nchw, dy_bs, dx_nchw, key_src, q_dst, inv_ptr, inv_idx, saved, scratch,
                                      depth - 1, 0, stream);
+}
+
+// ------------------------------------------------------------------------------------------- k-means (CFFM++ prototype generation)
+// workspace: centre fragments | partial sums [P][K][256] | partial counts [P][K]   (kmeans_kernels.h)
+}  // extern "C"
+struct KmPlan { int KT, tpw, P; size_t frag_b, part_b, cnt_b; };
+static KmPlan km_plan(long N, int K) {
+    KmPlan p;
+    p.KT = (K + 15) / 16;
+    const long tiles = (N + 15) / 16;
+    long tpw = (tiles + 4L * KM_WGS - 1) / (4L * KM_WGS);
+    if (tpw < 1) tpw = 1;
+    if (tpw > KM_MAX_TPW) tpw = KM_MAX_TPW;
+    p.tpw = (int)tpw;
+    p.P = (int)((N + 64 * tpw - 1) / (64 * tpw));
+    p.frag_b = (size_t)km_frag_words(p.KT) * 16;
+    p.part_b = ((size_t)p.P * K * CFFM_C * 4 + 255) / 256 * 256;
+    p.cnt_b = ((size_t)p.P * K * 4 + 255) / 256 * 256;
+    return p;
+}
+static int km_check(const char* who, long N, int K) {
+    REQUIRE(K >= 1 && K <= 128, "%s: K=%d outside 1..128", who, K);
+    REQUIRE(N >= K && N <= (1L << 30), "%s: N=%ld outside K..2^30 (K=%d)", who, N, K);
+    return 0;
+}
+template <int KT>
+static int km_run(const float* x, int N, int K, int iters, float* centers, int* labels, int* counts, char* ws, const KmPlan& p, hipStream_t st) {
+    const size_t lds = (size_t)km_step_lds(KT, p.tpw);
+#ifndef CFFM_EMU
+    static size_t granted = 0;
+    if (lds > granted) {
+        REQUIRE(hipFuncSetAttribute((const void*)k_km_step<KT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)km_step_lds(KT, KM_MAX_TPW)) == hipSuccess,
+                "kmeans: LDS grant failed");
+        granted = (size_t)km_step_lds(KT, KM_MAX_TPW);
+    }
+#endif
+    f32x4* frags = (f32x4*)ws;
+    float* partial = (float*)(ws + p.frag_b);
+    int* pcount = (int*)(ws + p.frag_b + p.part_b);
+    // the fragments of the centres as given (no records: every centre "keeps its value")
+    CFFM_LAUNCH(k_km_reduce, (16 * KT, 4), (256), 0, st, (const float*)partial, (const int*)pcount, 0, K, centers, (bf16*)frags, (int*)nullptr);
+    for (int it = 0; it < iters; ++it) {
+        const bool last = it == iters - 1;
+        CFFM_LAUNCH(k_km_step<KT>, (p.P), (256), lds, st, x, N, K, (const f32x4*)frags, partial, pcount, last ? labels : (int*)nullptr, p.tpw);
+        CFFM_LAUNCH(k_km_reduce, (16 * KT, 4), (256), 0, st, (const float*)partial, (const int*)pcount, p.P, K, centers, (bf16*)frags,
+                    last ? counts : (int*)nullptr);
+    }
+    CHECK_LAUNCH("kmeans");
+    return 0;
+}
+extern "C" {
+long cffm_kmeans_workspace_bytes(long N, int K) {
+    if (km_check("kmeans_workspace_bytes", N, K)) return -1;
+    const KmPlan p = km_plan(N, K);
+    return (long)(p.frag_b + p.part_b + p.cnt_b);
+}
+int cffm_kmeans(const float* x, long N, int K, int iters, float* centers_inout, int* labels_out, int* counts_out, void* workspace, void* stream) {
+    TRY(km_check("kmeans", N, K));
+    REQUIRE(iters >= 1, "kmeans: iters=%d < 1", iters);
+    REQUIRE(x && centers_inout && workspace, "kmeans: null x / centers / workspace");
+    REQUIRE(((uintptr_t)x | (uintptr_t)centers_inout | (uintptr_t)workspace) % 16 == 0, "kmeans: x / centers / workspace must be 16-byte aligned");
+    const KmPlan p = km_plan(N, K);
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    switch (p.KT) {
+#define KM_CASE(KT_) case KT_: return km_run<KT_>(x, (int)N, K, iters, centers_inout, labels_out, counts_out, ws, p, st);
+        KM_CASE(1) KM_CASE(2) KM_CASE(3) KM_CASE(4) KM_CASE(5) KM_CASE(6) KM_CASE(7) KM_CASE(8)
+#undef KM_CASE
+    }
+    return fail(-1, "kmeans: K=%d", K);
 }
 
 }  // extern "C"

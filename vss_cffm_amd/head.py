@@ -10,7 +10,8 @@ contract and state_dict keys, around the MI355X hot path.
 For GPU tensors the whole head runs in libcffm_hip.so on token rows (``rows_impl='hip'``): the SegFormer embedding
 (``ops.segformer_fuse``), ``linear_fuse``'s BatchNorm + ReLU + the 1/4 -> 1/8 resize (``ops.bn_relu_pool``), ``decoder_focal`` /
 ``decoder_swin`` (the hot path), the 1x1 classifiers (``ops.conv1x1``), the 1/8 -> 1/4 resize of the clip-level logits
-(``ops.rows_resize``) and resize + cross entropy + accuracy (``ops.head_cross_entropy``); ``rows_impl='torch'``, CPU tensors and
+(``ops.rows_resize``), resize + cross entropy + accuracy (``ops.head_cross_entropy``) and, in the prototype-generating head's eval forward,
+the k-means on the clip stack rows (``cluster.kmeans``); ``rows_impl='torch'``, CPU tensors and
 non-default loss settings take the reference's op sequence in stock PyTorch around the hot path.
 mmcv is absent on both boxes, so ``ConvModule`` / ``resize`` are re-provided with the same parameter names.
 """
@@ -23,6 +24,7 @@ import torch.nn.functional as F
 
 from .modules import BasicLayer3d3, BasicLayer_cluster
 from . import _lib
+from .cluster import kmeans
 from .ops import bn_relu_pool, cat_into, cat_room, conv1x1, frame_logits_cat, late_params, head_cross_entropy, resize_cross_entropy, rows_resize, segformer_fuse
 from .registry import HEADS, LOSSES, build_loss
 
@@ -309,12 +311,13 @@ class _CffmHeadBase(BaseDecodeHead_clips_flow):
                 and isinstance(bn, torch.nn.modules.batchnorm._BatchNorm) and bn.affine and bn.track_running_stats
                 and isinstance(self.linear_fuse.activate, nn.ReLU))
 
-    def _rows_front(self, inputs, batch_size, num_clips):
+    def _rows_front(self, inputs, batch_size, num_clips, need_clip=None):
         """-> (fused [N,256,h,w] channels-last, clip-stack rows [N,h/2,w/2,256] or None, frame logits [B,T,K,h,w])."""
         c1, c2, c3, c4 = self._transform_inputs(inputs)
         lins = (self.linear_c1, self.linear_c2, self.linear_c3, self.linear_c4)
         y = segformer_fuse([c1, c2, c3, c4], [l.proj.weight for l in lins], [l.proj.bias for l in lins], self.linear_fuse.conv.weight)
-        need_clip = self.training or num_clips == self.num_clips
+        if need_clip is None:
+            need_clip = self.training or num_clips == self.num_clips
         # Dropout2d in front of `linear_pred` (cffm_head.py:120) rides in the BatchNorm + ReLU pass: a [N,256] table of 0 / 1/(1-p)
         # factors (whole channels of a frame, as nn.Dropout2d draws them) instead of two passes over the 118 MB map
         mask = None
@@ -409,12 +412,38 @@ class CFFMHead_clips_resize1_8_gene_prototype(_CffmHeadBase):
         super().__init__(feature_strides, **kwargs)
         self.n_clusters, self.save_path = 100, './cluster_centers/'
 
+    kmeans_iters = 10       # fast_pytorch_kmeans.KMeans(max_iter=10), cffm_head.py:280
+
     def forward_test(self, inputs, img_metas, test_cfg, batch_size=None, num_clips=None, img=None):
         return self.forward(inputs, batch_size, num_clips, img, img_metas)
+
+    def _save_centers(self, centers, img_metas):
+        video = img_metas[0]['filename'].split('/')[-3]
+        os.makedirs(self.save_path + video, exist_ok=True)
+        torch.save(centers, self.save_path + video + '/centers.pt')
+
+    def _forward_rows(self, inputs, batch_size, num_clips, img_metas):
+        """Eval on token rows: the clip stack `_rows_front` leaves as [B*T, h2*w2, 256] rows IS the [T*h2*w2, 256] point matrix of a clip
+        (no permute, no copy); the clustering is one library call per clip (cluster.kmeans).  The reference clusters whatever
+        `num_clips` is (cffm_head.py:262-282), so the stack is always asked for."""
+        fused, stack, dropped = self._rows_front(inputs, batch_size, num_clips, need_clip=True)
+        x = self._frame_logits(fused, batch_size, num_clips, dropped=dropped)
+        assert batch_size == 1
+        points = stack.detach().view(batch_size, -1, stack.shape[-1])
+        centers = kmeans(points, self.n_clusters, iters=self.kmeans_iters)[0]                  # [1, K, 256]
+        self._save_centers(centers, img_metas)
+        return x[:, -1]
+
+    def _kmeans_rows_ok(self, inputs):
+        c1 = inputs[self.in_index[0]]
+        points = (c1.shape[0] * (c1.shape[2] // 2) * (c1.shape[3] // 2))                       # batch_size = 1: every frame is of the one clip
+        return 1 <= self.n_clusters <= 128 and points >= self.n_clusters and self.linear_fuse.conv.out_channels == 256
 
     def forward(self, inputs, batch_size=None, num_clips=None, imgs=None, img_metas=None):
         if self.training:
             assert self.num_clips == num_clips
+        if not self.training and self._rows_path_ok(inputs) and self._kmeans_rows_ok(inputs):
+            return self._forward_rows(inputs, batch_size, num_clips, img_metas)
         fused = self._fuse(inputs)
         x = self._frame_logits(fused, batch_size, num_clips)
         assert batch_size == 1
