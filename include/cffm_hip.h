@@ -15,6 +15,8 @@
  *   cffm_gtc_*                       <->  BasicLayer_cluster / WindowAttention_cluster (CFFM++)
  *                                                         pvt/swin_transformer_2d.py:1103-1148, :208-262
  *   cffm_kmeans                      <->  KMeans(...).fit_predict of the prototype-generating head  cffm_head.py:280-282
+ *   cffm_predict                     <->  EncoderDecoder_clips' resize, resize, softmax, flip, argmax
+ *                                                         segmentors/encoder_decoder.py:367-378, :502-572
  *
  * Conventions: every pointer is a DEVICE pointer (fp32 unless stated) borrowed for the duration of
  * the call; `stream` is a hipStream_t (NULL = default stream); work is enqueued asynchronously on it;
@@ -458,6 +460,24 @@ int cffm_adamw_step_rows(const cffm_adamw_chunk2* chunks /* device */, int nchun
 long cffm_kmeans_workspace_bytes(long N, int K);
 int cffm_kmeans(const float* x, long N, int K, int iters, float* centers_inout, int* labels_out, int* counts_out, void* workspace,
                 void* stream);
+
+/* ---- added under ABI 13, additive (no existing declaration changes, so the version stays 13): prediction ----
+ * What EncoderDecoder_clips does between the head's eval forward and the metrics (segmentors/encoder_decoder.py:367-378 encode_decode's
+ * resize to the input size, :502-516 whole_inference's resize to ori_shape, :542 softmax, :543-550 flip, :564 argmax) in ONE launch:
+ *   pred[M][H][W] (int64) = argmax_k of the logits [.,K,h,w] resized bilinearly (align_corners=False) to (Hm,Wm) and then to (H,W); the
+ *   resized logits exist only in registers.  The arg-max is taken over the interpolated logits (no exponential); equal values go to the
+ *   lowest class index, as in torch.argmax.  When (Hm,Wm) == (H,W) the second stage is the identity.
+ *   probs[M][K][H][W] (fp32, or NULL): the softmax over K of the same interpolated logits, written (accumulate = 0) or added
+ *   (accumulate != 0: the in-place sum over augmentations of aug_test, :582-586).  probs == NULL selects a kernel without exponentials;
+ *   pred may be NULL only when probs is given.
+ * flip: 0 none, 1 horizontal, 2 vertical -- the OUTPUT is flipped: pixel (y, x) of pred / probs is what the unflipped call has at
+ * (y, W-1-x) / (H-1-y, x).
+ * The logits are addressed as in cffm_upce_maps_fwd: element (m, k, r, c) at (m / inner) * ms_outer + (m % inner) * ms_inner + k * ks +
+ * (r * w + c) * ps with one of ks, ps equal to 1 -- plain [M,K,h,w], the heads' token rows [.., h, w, K], several maps of a clip buffer.
+ * 1 <= K <= 256; Hm / h and Wm / w in 1..8; H / Hm and W / Wm in 0.5..2 (per axis, integer or not); anything else is an error and
+ * enqueues nothing.  No workspace, no allocation, no host round trip: the call can be captured into a HIP graph. */
+int cffm_predict(const float* logits, long long* pred, float* probs, int accumulate, int M, int K, int h, int w, int Hm, int Wm, int H,
+                 int W, int flip, int inner, long ms_outer, long ms_inner, int ks, int ps, void* stream);
 
 #ifdef __cplusplus
 }

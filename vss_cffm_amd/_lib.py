@@ -131,6 +131,7 @@ SIGNATURES = {
     'cffm_adamw_step_rows': (ci, [vp, ci, vp, vp, vp, vp, ci, vp, vp, vp]),
     'cffm_kmeans_workspace_bytes': (cl, [cl, ci]),
     'cffm_kmeans': (ci, [vp, cl, ci, ci, vp, vp, vp, vp, vp]),
+    'cffm_predict': (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, cl, cl, ci, ci, vp]),
 }
 
 

@@ -9,6 +9,7 @@
 #include "segloss_kernels.h"
 #include "headfuse_kernels.h"
 #include "kmeans_kernels.h"
+#include "predict_kernels.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -2774,6 +2775,63 @@ int cffm_kmeans(const float* x, long N, int K, int iters, float* centers_inout, 
 #undef KM_CASE
     }
     return fail(-1, "kmeans: K=%d", K);
+}
+
+// ------------------------------------------------------------------------------------------- prediction: two-stage resize + (soft-max) + flip + arg-max
+}  // extern "C"
+// rows of the low-resolution map that PRED_TILE consecutive output pixels can tap under both stages, as a bound in closed form (no
+// restatement of the tap rule whose rounding could differ from the device's): a resize with source step s = in / out maps pixels d .. d + n
+// to source positions s n apart, and first tap .. last tap (floor + 1) of positions p apart are at most p + 3 rows; PRED_TILE instead of
+// PRED_TILE - 1 steps leaves a whole row to fp32 rounding in either stage
+static int pred_span(int in, int mid, int out) {
+    const int mid_dist = (int)std::ceil((double)PRED_TILE * mid / out) + 2;      // last minus first stage-1 row
+    return std::min((int)std::ceil((double)mid_dist * in / mid) + 3, in);
+}
+template <bool PROBS>
+static void pred_launch(int ny, int nx, unsigned grid, size_t lds, hipStream_t st, const float* logits, long long* pred, float* probs,
+                        const PredGeom& G) {
+    if (ny == 2 && nx == 2) CFFM_LAUNCH((k_predict<PROBS, 2, 2>), (grid), (256), lds, st, logits, pred, probs, G);
+    else if (ny == 2) CFFM_LAUNCH((k_predict<PROBS, 2, 3>), (grid), (256), lds, st, logits, pred, probs, G);
+    else if (nx == 2) CFFM_LAUNCH((k_predict<PROBS, 3, 2>), (grid), (256), lds, st, logits, pred, probs, G);
+    else CFFM_LAUNCH((k_predict<PROBS, 3, 3>), (grid), (256), lds, st, logits, pred, probs, G);
+}
+extern "C" {
+int cffm_predict(const float* logits, long long* pred, float* probs, int accumulate, int M, int K, int h, int w, int Hm, int Wm, int H,
+                 int W, int flip, int inner, long ms_outer, long ms_inner, int ks, int ps, void* stream) {
+    REQUIRE(K >= 1 && K <= 256, "predict: K=%d outside 1..256", K);
+    REQUIRE(M >= 0 && h >= 1 && w >= 1 && Hm >= 1 && Wm >= 1 && H >= 1 && W >= 1, "predict: bad sizes M=%d, %dx%d -> %dx%d -> %dx%d", M, h, w, Hm,
+            Wm, H, W);
+    REQUIRE(Hm >= h && Wm >= w && (long)Hm <= (long)PRED_MAX_RATIO * h && (long)Wm <= (long)PRED_MAX_RATIO * w,
+            "predict: stage-1 resize %dx%d -> %dx%d outside the factors 1..%d", h, w, Hm, Wm, PRED_MAX_RATIO);
+    REQUIRE(2L * H >= Hm && H <= 2L * Hm && 2L * W >= Wm && W <= 2L * Wm, "predict: stage-2 resize %dx%d -> %dx%d outside the factors 0.5..2", Hm,
+            Wm, H, W);
+    REQUIRE(flip >= 0 && flip <= 2, "predict: flip=%d (0 none, 1 horizontal, 2 vertical)", flip);
+    REQUIRE(probs || !accumulate, "predict: accumulate needs probs");
+    if (!M) return 0;
+    REQUIRE(logits && (pred || probs), "predict: null logits, or neither pred nor probs");
+    UpceGeom U;
+    U.K = K; U.h = h; U.w = w;
+    TRY(upce_layout(U, inner, ms_outer, ms_inner, ks, ps, "predict"));
+    PredGeom G;
+    G.M = M; G.K = K; G.h = h; G.w = w; G.Hm = Hm; G.Wm = Wm; G.H = H; G.W = W; G.flip = flip; G.accumulate = accumulate ? 1 : 0;
+    G.inner = inner; G.ms_outer = ms_outer; G.ms_inner = ms_inner; G.ks = ks; G.ps = ps;
+    G.rn = pred_span(h, Hm, H);
+    G.cn = pred_span(w, Wm, W);
+    // the tile holds every class when it fits the LDS budget (any upsampling in total does), otherwise the classes pass through in chunks
+    const int KP = UPCE_KP(K), cells = G.rn * G.cn;
+    REQUIRE(cells <= PRED_LDS_FLOATS / 4, "predict: the low-resolution footprint of a tile (%d x %d cells) does not fit the LDS", G.rn, G.cn);
+    G.KC = std::min(KP, (PRED_LDS_FLOATS / cells) & ~3);
+    G.nchunk = (KP + G.KC - 1) / G.KC;
+    const size_t lds = (size_t)cells * G.KC * sizeof(float);
+    const long tiles = (long)M * ((H + PRED_TILE - 1) / PRED_TILE) * ((W + PRED_TILE - 1) / PRED_TILE);
+    REQUIRE(tiles < (1L << 31), "predict: too many tiles");
+    // a stage-2 axis of equal sizes is the identity (every lambda is 0): two taps per axis instead of three
+    const int ny = H == Hm ? 2 : 3, nx = W == Wm ? 2 : 3;
+    hipStream_t st = (hipStream_t)stream;
+    if (probs) pred_launch<true>(ny, nx, (unsigned)tiles, lds, st, logits, pred, probs, G);
+    else pred_launch<false>(ny, nx, (unsigned)tiles, lds, st, logits, pred, probs, G);
+    CHECK_LAUNCH("predict");
+    return 0;
 }
 
 }  // extern "C"

@@ -1260,3 +1260,52 @@ class _GtcBlockFn(torch.autograd.Function):
 def gtc_block(x, centers, params):
     """params: 14 tensors in GTC_PARAM_KEYS order."""
     return _GtcBlockFn.apply(x, centers, *params)
+
+
+# ---------------------------------------------------------------------------------------------- prediction (resize, resize, softmax, flip, arg-max)
+_FLIPS = {None: 0, False: 0, 'horizontal': 1, 'vertical': 2}
+
+
+def _predict_layout(logits):
+    """(ms_outer, ks, ps) of [B,K,h,w] logits the library can read where they lie, or None: plain memory (cells contiguous) or the heads'
+    token rows [B,h,w,K] viewed as [B,K,h,w] (classes contiguous), rows dense either way; the stride of a size-1 dimension says nothing"""
+    b, k, h, w = logits.shape
+    sb, sk, sh, sw = logits.stride()
+    if (w == 1 or sw == 1) and (h == 1 or sh == w) and (k == 1 or sk == h * w):
+        return (sb if b > 1 else 0), h * w, 1
+    if (k == 1 or sk == 1) and (w == 1 or sw == k) and (h == 1 or sh == w * k):
+        return (sb if b > 1 else 0), 1, k
+    return None
+
+
+def predict(logits, size, ori_size=None, flip=None, probs=None, accumulate=False, want_pred=True):
+    """Label maps int64 [B,H,W] from logits [B,K,h,w]: bilinear resize (align_corners=False) to `size` (the network input), a second one to
+    `ori_size` (None: `size`), softmax over K, flip of the result ('horizontal' / 'vertical'), arg-max -- EncoderDecoder_clips' tail
+    (encoder_decoder.py:367-378, 502-572) in ONE kernel of libcffm_hip.so; the resized logits and the probabilities never exist.  The
+    logits are read where they lie when the class stride or the pixel stride is 1 (the heads' permuted token-row views: no copy).
+    `probs` (fp32 [B,K,H,W], contiguous): also write the softmax probabilities there, or add them with `accumulate` (the sum over
+    augmentations of aug_test); with `want_pred=False` only that is done and None is returned.  No autograd."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 4:
+        raise _lib.CffmError('predict: logits must be a [B,K,h,w] tensor')
+    _require_device(logits, 'predict logits')
+    if flip not in _FLIPS:
+        raise _lib.CffmError("predict: flip must be None, 'horizontal' or 'vertical', got %r" % (flip,))
+    lib = _lib.get()
+    logits = logits.detach()
+    layout = _predict_layout(logits)
+    if layout is None:
+        logits = logits.contiguous()
+        layout = _predict_layout(logits)
+    b, k, h, w = logits.shape
+    hm, wm = int(size[0]), int(size[1])
+    H, W = (hm, wm) if ori_size is None else (int(ori_size[0]), int(ori_size[1]))
+    if probs is not None:
+        if probs.dtype != torch.float32 or probs.device != logits.device or tuple(probs.shape) != (b, k, H, W) or not probs.is_contiguous():
+            raise _lib.CffmError('predict: probs must be a contiguous fp32 [%d,%d,%d,%d] tensor on %s' % (b, k, H, W, logits.device))
+    elif accumulate or not want_pred:
+        raise _lib.CffmError('predict: accumulate / want_pred=False need probs')
+    ms_outer, ks, ps = layout
+    args = (int(bool(accumulate)), b, k, h, w, hm, wm, H, W, _FLIPS[flip], 1, ms_outer, 0, ks, ps, _stream(logits))
+    pred = torch.empty((b, H, W), dtype=torch.int64, device=logits.device) if want_pred else None
+    _lib.check(lib.cffm_predict(_ptr(logits), _ptr(pred), _ptr(probs), *args), lib)
+    return pred
