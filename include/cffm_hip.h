@@ -17,6 +17,7 @@
  *   cffm_kmeans                      <->  KMeans(...).fit_predict of the prototype-generating head  cffm_head.py:280-282
  *   cffm_predict                     <->  EncoderDecoder_clips' resize, resize, softmax, flip, argmax
  *                                                         segmentors/encoder_decoder.py:367-378, :502-572
+ *   cffm_dwconv_gelu_fwd / _bwd      <->  Mlp's DWConv + GELU of the MiT backbone  backbones/mix_transformer.py:48-55, 358-369
  *
  * Conventions: every pointer is a DEVICE pointer (fp32 unless stated) borrowed for the duration of
  * the call; `stream` is a hipStream_t (NULL = default stream); work is enqueued asynchronously on it;
@@ -478,6 +479,21 @@ int cffm_kmeans(const float* x, long N, int K, int iters, float* centers_inout, 
  * enqueues nothing.  No workspace, no allocation, no host round trip: the call can be captured into a HIP graph. */
 int cffm_predict(const float* logits, long long* pred, float* probs, int accumulate, int M, int K, int h, int w, int Hm, int Wm, int H,
                  int W, int flip, int inner, long ms_outer, long ms_inner, int ks, int ps, void* stream);
+
+/* ---- added under ABI 13, additive: the middle of MiT's Mix-FFN (backbones/mix_transformer.py:48-55, 358-369) on token rows ----
+ * h [M][H*W][C] (M images, row-major pixels, channel fastest), w [C][1][3][3], b [C]; zero padding outside each image:
+ *   u[m,y,x,c] = b[c] + sum_{i,j in 0..2} w[c,i,j] h[m, y+i-1, x+j-1, c],     out = u Phi(u)   (the exact-erf GELU)
+ * in one pass: the NCHW view, the depthwise Conv2d, the transpose back and the GELU of the reference never exist as tensors, and u is
+ * not stored.  The backward recomputes u from h; with g = dout gelu'(u):
+ *   dh[m,y,x,c] = sum_{i,j} w[c,i,j] g[m, y-i+1, x-j+1, c],   dw[c,i,j] = sum_{m,y,x} g[m,y,x,c] h[m, y+i-1, x+j-1, c],   db[c] = sum g
+ * dw / db are summed in a fixed order (no atomics): the same bits run after run.  workspace: cffm_dwconv_gelu_bwd_workspace_bytes
+ * bytes (-1 for bad sizes), 16-byte aligned; every byte that is read is written by the same call.
+ * Errors (nothing is enqueued, the outputs stay as they are): C < 4, C % 4 != 0, M / H / W < 1, M*H*W*C >= 2^31, a null pointer or
+ * one that is not 16-byte aligned.  No allocation, no host round trip: the calls can be captured into a HIP graph. */
+int cffm_dwconv_gelu_fwd(const float* h, const float* w, const float* b, float* out, int M, int H, int W, int C, void* stream);
+long cffm_dwconv_gelu_bwd_workspace_bytes(int M, int H, int W, int C);
+int cffm_dwconv_gelu_bwd(const float* h, const float* w, const float* b, const float* dout, float* dh, float* dw, float* db,
+                         void* workspace, int M, int H, int W, int C, void* stream);
 
 #ifdef __cplusplus
 }

@@ -4,13 +4,14 @@ reference's own module / registry names.  See DESIGN.md and include/cffm_hip.h."
 from .modules import (BasicLayer3d3, BasicLayer_cluster, CffmTransformerBlock3d3, Mlp,  # noqa: F401
                       SwinTransformerBlock_cluster, WindowAttention3d3, WindowAttention_cluster)
 from .cluster import kmeans, kmeans_workspace  # noqa: F401,E402
-from .ops import predict  # noqa: F401,E402
+from .ops import dwconv_gelu, predict  # noqa: F401,E402
 from . import head  # noqa: F401,E402  (registers the three CFFM heads and CrossEntropyLoss)
 from .config import Config  # noqa: F401,E402
 from . import optim  # noqa: F401,E402
 from . import distributed  # noqa: F401,E402
 from . import evaluation  # noqa: F401,E402
 from . import segmentor  # noqa: F401,E402  (registers EncoderDecoder_clips)
+from . import backbone  # noqa: F401,E402  (registers mit_b0 ... mit_b5)
 from .registry import (BACKBONES, HEADS, LOSSES, NECKS, SEGMENTORS, Registry, build_backbone,  # noqa: F401,E402
                        build_from_cfg, build_head, build_loss, build_neck, build_segmentor)
 from .checkpoint import load_reference_checkpoint  # noqa: F401,E402

@@ -132,6 +132,9 @@ SIGNATURES = {
     'cffm_kmeans_workspace_bytes': (cl, [cl, ci]),
     'cffm_kmeans': (ci, [vp, cl, ci, ci, vp, vp, vp, vp, vp]),
     'cffm_predict': (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, cl, cl, ci, ci, vp]),
+    'cffm_dwconv_gelu_fwd': (ci, [vp, vp, vp, vp, ci, ci, ci, ci, vp]),
+    'cffm_dwconv_gelu_bwd_workspace_bytes': (cl, [ci, ci, ci, ci]),
+    'cffm_dwconv_gelu_bwd': (ci, [vp] * 8 + [ci, ci, ci, ci, vp]),
 }
 
 

@@ -1,0 +1,259 @@
+"""Mix Transformer backbones ``mit_b0`` .. ``mit_b5`` (SegFormer's encoder; the reference's mmseg/models/backbones/mix_transformer.py)
+under the reference's class, constructor-keyword and attribute names, so a reference checkpoint's ``backbone.*`` keys load key for key.
+
+Four stages; each is an overlapping patch embedding (strided Conv2d + LayerNorm on token rows), `depth` blocks of spatial-reduction
+attention + Mix-FFN with stochastic depth, and a LayerNorm; each stage hands a contiguous NCHW map (strides 4 / 8 / 16 / 32) to the head.
+
+The Mix-FFN is fc1 -> depthwise 3 x 3 Conv2d on the NCHW view -> GELU -> fc2.  With ``Mlp.dwconv_impl = 'hip'`` everything between the
+two Linear layers is ONE pass of libcffm_hip.so over the token rows (``ops.dwconv_gelu`` -> cffm_dwconv_gelu_fwd / _bwd): no NCHW view,
+no transpose copies, and two saved activations instead of three.  ``'torch'`` is the reference's op sequence in stock PyTorch: the A/B
+partner in the tests and what CPU tensors, other dtypes, other activations and dropout > 0 get.  Attention stays on PyTorch
+(matmul, softmax, matmul in the reference's order).
+"""
+import math
+from functools import partial
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+from .checkpoint import load_reference_checkpoint
+from .ops import dwconv_gelu
+from .registry import BACKBONES
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def _init_weights(m):
+    """the reference's _init_weights: Linear ~ truncated N(0, 0.02) with zero bias, LayerNorm 1 / 0, Conv2d ~ N(0, sqrt(2 / fan_out))"""
+    if isinstance(m, nn.Linear):
+        nn.init.trunc_normal_(m.weight, std=.02)
+        if m.bias is not None:
+            nn.init.constant_(m.bias, 0)
+    elif isinstance(m, nn.LayerNorm):
+        nn.init.constant_(m.bias, 0)
+        nn.init.constant_(m.weight, 1.0)
+    elif isinstance(m, nn.Conv2d):
+        fan_out = m.kernel_size[0] * m.kernel_size[1] * m.out_channels // m.groups
+        m.weight.data.normal_(0, math.sqrt(2.0 / fan_out))
+        if m.bias is not None:
+            m.bias.data.zero_()
+
+
+class DropPath(nn.Module):
+    """Stochastic depth per sample (timm's DropPath): in training the residual branch of a sample is dropped with probability
+    `drop_prob` and the kept ones are scaled by 1 / keep.  Identity in eval mode and at drop_prob = 0."""
+
+    def __init__(self, drop_prob=0.):
+        super().__init__()
+        self.drop_prob = drop_prob
+
+    def forward(self, x):
+        if self.drop_prob == 0. or not self.training:
+            return x
+        keep = 1 - self.drop_prob
+        mask = keep + torch.rand((x.shape[0],) + (1,) * (x.dim() - 1), dtype=x.dtype, device=x.device)
+        return x.div(keep) * mask.floor_()
+
+    def extra_repr(self):
+        return 'drop_prob=%s' % (self.drop_prob,)
+
+
+class DWConv(nn.Module):
+    """depthwise 3 x 3 convolution of token rows [B, H*W, C] through their NCHW view"""
+
+    def __init__(self, dim=768):
+        super().__init__()
+        self.dwconv = nn.Conv2d(dim, dim, 3, 1, 1, bias=True, groups=dim)
+
+    def forward(self, x, H, W):
+        B, N, C = x.shape
+        x = self.dwconv(x.transpose(1, 2).view(B, C, H, W))
+        return x.flatten(2).transpose(1, 2)
+
+
+class Mlp(nn.Module):
+    # 'hip': dwconv + bias + GELU in one kernel of libcffm_hip.so for fp32 GPU tensors (it raises when the library is missing);
+    # 'torch': the reference's op sequence (what everything else gets, and the A/B partner in the tests)
+    dwconv_impl = 'hip'
+
+    def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.):
+        super().__init__()
+        out_features = out_features or in_features
+        hidden_features = hidden_features or in_features
+        self.fc1 = nn.Linear(in_features, hidden_features)
+        self.dwconv = DWConv(hidden_features)
+        self.act = act_layer()
+        self.fc2 = nn.Linear(hidden_features, out_features)
+        self.drop = nn.Dropout(drop)
+        self.apply(_init_weights)
+
+    def _fused(self, x):
+        return (self.dwconv_impl == 'hip' and (x.is_cuda or _lib._override is not None) and x.dtype == torch.float32
+                and type(self.act) is nn.GELU and getattr(self.act, 'approximate', 'none') == 'none' and self.drop.p == 0
+                and x.shape[-1] % 4 == 0)
+
+    def forward(self, x, H, W):
+        x = self.fc1(x)
+        if self._fused(x):
+            x = dwconv_gelu(x, self.dwconv.dwconv.weight, self.dwconv.dwconv.bias, H, W)
+        else:
+            x = self.drop(self.act(self.dwconv(x, H, W)))
+        return self.drop(self.fc2(x))
+
+
+class Attention(nn.Module):
+    """multi-head self-attention whose keys / values come from the map reduced by a strided `sr` convolution (sr_ratio > 1)"""
+
+    def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, attn_drop=0., proj_drop=0., sr_ratio=1):
+        super().__init__()
+        assert dim % num_heads == 0, 'dim %d should be divided by num_heads %d.' % (dim, num_heads)
+        self.dim = dim
+        self.num_heads = num_heads
+        self.scale = qk_scale or (dim // num_heads) ** -0.5
+        self.q = nn.Linear(dim, dim, bias=qkv_bias)
+        self.kv = nn.Linear(dim, dim * 2, bias=qkv_bias)
+        self.attn_drop = nn.Dropout(attn_drop)
+        self.proj = nn.Linear(dim, dim)
+        self.proj_drop = nn.Dropout(proj_drop)
+        self.sr_ratio = sr_ratio
+        if sr_ratio > 1:
+            self.sr = nn.Conv2d(dim, dim, kernel_size=sr_ratio, stride=sr_ratio)
+            self.norm = nn.LayerNorm(dim)
+        self.apply(_init_weights)
+
+    def forward(self, x, H, W):
+        B, N, C = x.shape
+        hd = C // self.num_heads
+        q = self.q(x).reshape(B, N, self.num_heads, hd).permute(0, 2, 1, 3)
+        if self.sr_ratio > 1:
+            x = self.norm(self.sr(x.permute(0, 2, 1).reshape(B, C, H, W)).reshape(B, C, -1).permute(0, 2, 1))
+        k, v = self.kv(x).reshape(B, -1, 2, self.num_heads, hd).permute(2, 0, 3, 1, 4)
+        attn = self.attn_drop(((q @ k.transpose(-2, -1)) * self.scale).softmax(dim=-1))
+        return self.proj_drop(self.proj((attn @ v).transpose(1, 2).reshape(B, N, C)))
+
+
+class Block(nn.Module):
+    def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, qk_scale=None, drop=0., attn_drop=0., drop_path=0.,
+                 act_layer=nn.GELU, norm_layer=nn.LayerNorm, sr_ratio=1):
+        super().__init__()
+        self.norm1 = norm_layer(dim)
+        self.attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale, attn_drop=attn_drop, proj_drop=drop,
+                              sr_ratio=sr_ratio)
+        self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()
+        self.norm2 = norm_layer(dim)
+        self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
+        self.apply(_init_weights)
+
+    def forward(self, x, H, W):
+        x = x + self.drop_path(self.attn(self.norm1(x), H, W))
+        return x + self.drop_path(self.mlp(self.norm2(x), H, W))
+
+
+class OverlapPatchEmbed(nn.Module):
+    """image (or the previous stage's map) -> token rows: a strided convolution with overlapping windows, then LayerNorm"""
+
+    def __init__(self, img_size=224, patch_size=7, stride=4, in_chans=3, embed_dim=768):
+        super().__init__()
+        self.img_size, self.patch_size = _pair(img_size), _pair(patch_size)
+        self.H, self.W = self.img_size[0] // self.patch_size[0], self.img_size[1] // self.patch_size[1]
+        self.num_patches = self.H * self.W
+        self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=self.patch_size, stride=stride,
+                              padding=(self.patch_size[0] // 2, self.patch_size[1] // 2))
+        self.norm = nn.LayerNorm(embed_dim)
+        self.apply(_init_weights)
+
+    def forward(self, x):
+        x = self.proj(x)
+        H, W = x.shape[2:]
+        return self.norm(x.flatten(2).transpose(1, 2)), H, W
+
+
+class MixVisionTransformer(nn.Module):
+    def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dims=[64, 128, 256, 512], num_heads=[1, 2, 4, 8],
+                 mlp_ratios=[4, 4, 4, 4], qkv_bias=False, qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.,
+                 norm_layer=nn.LayerNorm, depths=[3, 4, 6, 3], sr_ratios=[8, 4, 2, 1]):
+        super().__init__()
+        self.num_classes = num_classes
+        self.depths = depths
+        dpr = self._rates(drop_path_rate)
+        chans = [in_chans] + list(embed_dims)
+        for i in range(4):
+            self.add_module('patch_embed%d' % (i + 1), OverlapPatchEmbed(
+                img_size=img_size if i == 0 else img_size // (2 ** (i + 1)), patch_size=7 if i == 0 else 3, stride=4 if i == 0 else 2,
+                in_chans=chans[i], embed_dim=chans[i + 1]))
+        # (all patch embeddings first, then block1, norm1, block2, ...: the order of the reference's state_dict)
+        for i in range(4):
+            self.add_module('block%d' % (i + 1), nn.ModuleList([
+                Block(dim=embed_dims[i], num_heads=num_heads[i], mlp_ratio=mlp_ratios[i], qkv_bias=qkv_bias, qk_scale=qk_scale,
+                      drop=drop_rate, attn_drop=attn_drop_rate, drop_path=dpr[i][j], norm_layer=norm_layer, sr_ratio=sr_ratios[i])
+                for j in range(depths[i])]))
+            self.add_module('norm%d' % (i + 1), norm_layer(embed_dims[i]))
+        self.apply(_init_weights)
+
+    def _rates(self, drop_path_rate):
+        """the drop-path rate of every block, rising linearly from 0 to `drop_path_rate` over all blocks, per stage"""
+        flat = [x.item() for x in torch.linspace(0, drop_path_rate, sum(self.depths))]
+        out, cur = [], 0
+        for d in self.depths:
+            out.append(flat[cur:cur + d])
+            cur += d
+        return out
+
+    def init_weights(self, pretrained=None, trusted=False):
+        """pretrained: a checkpoint path, loaded non-strictly (missing / unexpected / mismatched keys are reported, not raised): a bare
+        backbone state dict (ImageNet files carry extra ``head.*`` keys) or an mmcv-format model checkpoint, of which the
+        ``backbone.``-prefixed keys are taken.  Returns (missing, unexpected) for a path, None otherwise."""
+        if not (isinstance(pretrained, (str, bytes)) or hasattr(pretrained, '__fspath__')):
+            return None
+        missing, unexpected, _ = load_reference_checkpoint(self, pretrained, prefix='backbone.', strict=False, trusted=trusted)
+        if missing or unexpected:
+            print('%s.init_weights(%s): missing keys %s, unexpected keys %s' % (type(self).__name__, pretrained, missing, unexpected))
+        return missing, unexpected
+
+    def reset_drop_path(self, drop_path_rate):
+        for i, rates in enumerate(self._rates(drop_path_rate)):
+            for blk, r in zip(getattr(self, 'block%d' % (i + 1)), rates):
+                blk.drop_path.drop_prob = r
+
+    def freeze_patch_emb(self):
+        self.patch_embed1.requires_grad = False      # (as in the reference: an attribute on the module, the parameters keep theirs)
+
+    @torch.jit.ignore
+    def no_weight_decay(self):
+        return {'pos_embed1', 'pos_embed2', 'pos_embed3', 'pos_embed4', 'cls_token'}
+
+    def forward_features(self, x):
+        B = x.shape[0]
+        outs = []
+        for i in range(1, 5):
+            x, H, W = getattr(self, 'patch_embed%d' % i)(x)
+            for blk in getattr(self, 'block%d' % i):
+                x = blk(x, H, W)
+            x = getattr(self, 'norm%d' % i)(x)
+            x = x.reshape(B, H, W, -1).permute(0, 3, 1, 2).contiguous()
+            outs.append(x)
+        return outs
+
+    def forward(self, x):
+        return self.forward_features(x)
+
+
+def _variant(name, embed_dims, depths):
+    def __init__(self, **kwargs):          # the configs pass style='pytorch' (and nothing else is honoured by the reference either)
+        MixVisionTransformer.__init__(self, patch_size=4, embed_dims=list(embed_dims), num_heads=[1, 2, 5, 8], mlp_ratios=[4, 4, 4, 4],
+                                      qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), depths=list(depths),
+                                      sr_ratios=[8, 4, 2, 1], drop_rate=0.0, drop_path_rate=0.1)
+    cls = type(name, (MixVisionTransformer,), {'__init__': __init__, '__module__': __name__, '__qualname__': name})
+    return BACKBONES.register_module()(cls)
+
+
+_WIDE = (64, 128, 320, 512)
+mit_b0 = _variant('mit_b0', (32, 64, 160, 256), (2, 2, 2, 2))
+mit_b1 = _variant('mit_b1', _WIDE, (2, 2, 2, 2))
+mit_b2 = _variant('mit_b2', _WIDE, (3, 4, 6, 3))
+mit_b3 = _variant('mit_b3', _WIDE, (3, 4, 18, 3))
+mit_b4 = _variant('mit_b4', _WIDE, (3, 8, 27, 3))
+mit_b5 = _variant('mit_b5', _WIDE, (3, 6, 40, 3))

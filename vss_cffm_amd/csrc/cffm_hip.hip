@@ -10,6 +10,7 @@
 #include "headfuse_kernels.h"
 #include "kmeans_kernels.h"
 #include "predict_kernels.h"
+#include "mixffn_kernels.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -2831,6 +2832,64 @@ int cffm_predict(const float* logits, long long* pred, float* probs, int accumul
     if (probs) pred_launch<true>(ny, nx, (unsigned)tiles, lds, st, logits, pred, probs, G);
     else pred_launch<false>(ny, nx, (unsigned)tiles, lds, st, logits, pred, probs, G);
     CHECK_LAUNCH("predict");
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------- Mix-FFN middle: depthwise 3 x 3 + bias + GELU on token rows
+}  // extern "C"
+static int dwg_check(const char* who, int M, int H, int W, int C) {
+    REQUIRE(C >= 4 && C % 4 == 0, "%s: C=%d must be a multiple of 4, at least 4", who, C);
+    REQUIRE(M >= 1 && H >= 1 && W >= 1, "%s: bad sizes M=%d H=%d W=%d", who, M, H, W);
+    REQUIRE((long)M * H * W * C < (1L << 31), "%s: M*H*W*C = %ld is not below 2^31", who, (long)M * H * W * C);
+    return 0;
+}
+// Strips and slots of one launch (mixffn_kernels.h).  The image is cut into y-strips until `lanes` lanes have work (never below
+// DWG_MIN_YS rows: every strip re-reads two halo rows); the live lanes are capped at `lanes` (a memory-bound grid of <= 2048
+// workgroups, the rest is strided), `per_slot` waves sharing a slot.
+static DwgGeom dwg_plan(int M, int H, int W, int C, int xr, long lanes, int per_slot) {
+    DwgGeom G;
+    G.M = M; G.H = H; G.W = W; G.C = C; G.C4 = C / 4;
+    G.nxr = (W + xr - 1) / xr;
+    int ys = H;
+    while (ys > DWG_MIN_YS && (long)M * ((H + ys - 1) / ys) * G.nxr * G.C4 < lanes) ys = (ys + 1) / 2;
+    G.YS = ys;
+    G.nys = (H + ys - 1) / ys;
+    G.nsp = (long)M * G.nys * G.nxr;
+    G.S = std::min((G.nsp + per_slot - 1) / per_slot, std::max(1L, lanes / per_slot / G.C4));
+    return G;
+}
+#define DWG_FWD_LANES (2048L * 256)     // forward and dh: up to 2048 workgroups of 256 lanes
+#define DWG_BWD1_LANES (1024L * 256)    // first backward pass: up to 1024 workgroups, each leaving a 10 KB slab of partial sums
+static bool dwg_aligned(const void* p) { return p && (uintptr_t)p % 16 == 0; }
+extern "C" {
+int cffm_dwconv_gelu_fwd(const float* h, const float* w, const float* b, float* out, int M, int H, int W, int C, void* stream) {
+    TRY(dwg_check("dwconv_gelu_fwd", M, H, W, C));
+    REQUIRE(dwg_aligned(h) && dwg_aligned(w) && dwg_aligned(b) && dwg_aligned(out), "dwconv_gelu_fwd: h / w / b / out must be non-null and 16-byte aligned");
+    const DwgGeom G = dwg_plan(M, H, W, C, DWG_XR, DWG_FWD_LANES, 1);
+    CFFM_LAUNCH(k_dwg_fwd, ((unsigned)((G.S * G.C4 + 255) / 256)), (256), 0, (hipStream_t)stream, h, w, b, out, G);
+    CHECK_LAUNCH("dwconv_gelu_fwd");
+    return 0;
+}
+long cffm_dwconv_gelu_bwd_workspace_bytes(int M, int H, int W, int C) {
+    if (dwg_check("dwconv_gelu_bwd_workspace_bytes", M, H, W, C)) return -1;
+    const DwgGeom G1 = dwg_plan(M, H, W, C, DWG_XR_BWD, DWG_BWD1_LANES, 4);
+    return (long)M * H * W * C * 4 + G1.S * DWG_NACC * G1.C4 * 16;
+}
+int cffm_dwconv_gelu_bwd(const float* h, const float* w, const float* b, const float* dout, float* dh, float* dw, float* db,
+                         void* workspace, int M, int H, int W, int C, void* stream) {
+    TRY(dwg_check("dwconv_gelu_bwd", M, H, W, C));
+    REQUIRE(dwg_aligned(h) && dwg_aligned(w) && dwg_aligned(b) && dwg_aligned(dout) && dwg_aligned(dh) && dwg_aligned(dw) && dwg_aligned(db) &&
+            dwg_aligned(workspace), "dwconv_gelu_bwd: h / w / b / dout / dh / dw / db / workspace must be non-null and 16-byte aligned");
+    const DwgGeom G1 = dwg_plan(M, H, W, C, DWG_XR_BWD, DWG_BWD1_LANES, 4);
+    const DwgGeom G2 = dwg_plan(M, H, W, C, DWG_XR, DWG_FWD_LANES, 1);
+    float* g = (float*)workspace;                              // [M][H][W][C]
+    f32x4* part = (f32x4*)(g + (long)M * H * W * C);           // [S][10][C4] f32x4 (M*H*W*C is a multiple of 4: 16-byte aligned)
+    const int nred = DWG_NACC * ((G1.C4 + 15) / 16);
+    hipStream_t st = (hipStream_t)stream;
+    CFFM_LAUNCH(k_dwg_bwd1, ((unsigned)((G1.S * G1.C4 + 63) / 64)), (256), 0, st, h, w, b, dout, g, part, G1);
+    CFFM_LAUNCH(k_dwg_bwd2, ((unsigned)(nred + (G2.S * G2.C4 + 255) / 256)), (256), 0, st, (const float*)g, w, dh, (const f32x4*)part, dw, db, G2,
+                G1.S, nred);
+    CHECK_LAUNCH("dwconv_gelu_bwd");
     return 0;
 }
 

@@ -1309,3 +1309,52 @@ def predict(logits, size, ori_size=None, flip=None, probs=None, accumulate=False
     pred = torch.empty((b, H, W), dtype=torch.int64, device=logits.device) if want_pred else None
     _lib.check(lib.cffm_predict(_ptr(logits), _ptr(pred), _ptr(probs), *args), lib)
     return pred
+
+
+# ---------------------------------------------------------------------------------------------- Mix-FFN middle (depthwise 3x3 + bias + GELU)
+class _DwconvGeluFn(torch.autograd.Function):
+    """gelu(dwconv3x3(h) + b) on token rows [M, H*W, C] (csrc/mixffn_kernels.h).  Saved: h, weight, bias -- the pre-activation is
+    recomputed in the backward, whose workspace (the GELU-scaled gradient + the partial weight-gradient slabs) lives only inside it."""
+
+    @staticmethod
+    def forward(ctx, h, weight, bias, H, W):
+        lib = _lib.get()
+        # every input contiguous BEFORE the stream is looked up or anything is enqueued: a copy made later would be ordered against nothing
+        h, weight, bias = h.contiguous(), weight.contiguous(), bias.contiguous()
+        m, n, c = h.shape
+        out = torch.empty_like(h)
+        _lib.check(lib.cffm_dwconv_gelu_fwd(_ptr(h), _ptr(weight), _ptr(bias), _ptr(out), m, H, W, c, _stream(h)), lib)
+        ctx.save_for_backward(h, weight, bias)
+        ctx.dims = (m, H, W, c)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.get()
+        h, weight, bias = ctx.saved_tensors
+        m, H, W, c = ctx.dims
+        dout = dout.contiguous()
+        dh, dw, db = torch.empty_like(h), torch.empty_like(weight), torch.empty_like(bias)
+        nbytes = lib.cffm_dwconv_gelu_bwd_workspace_bytes(m, H, W, c)
+        if nbytes < 0:
+            raise _lib.CffmError('libcffm_hip: %s' % lib.cffm_last_error().decode())
+        ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=h.device)
+        _lib.check(lib.cffm_dwconv_gelu_bwd(_ptr(h), _ptr(weight), _ptr(bias), _ptr(dout), _ptr(dh), _ptr(dw), _ptr(db), _ptr(ws), m, H, W, c,
+                                            _stream(h)), lib)
+        return dh, dw, db, None, None
+
+
+def dwconv_gelu(h, weight, bias, H, W):
+    """MiT's Mix-FFN between fc1 and fc2 (mix_transformer.py:48-55, 358-369) in one pass: h [M, H*W, C] fp32 token rows, weight [C,1,3,3]
+    and bias [C] of the depthwise Conv2d(C, C, 3, 1, 1, groups=C) -> gelu(conv(h) + bias) as token rows.  Differentiable in h, weight and
+    bias (dw / db bit-reproducible); under no_grad only the forward runs and nothing is saved.  Launches on the current stream."""
+    if not isinstance(h, torch.Tensor) or h.dim() != 3:
+        raise _lib.CffmError('dwconv_gelu: h must be a [M, H*W, C] tensor')
+    for t, what in ((h, 'dwconv_gelu h'), (weight, 'dwconv_gelu weight'), (bias, 'dwconv_gelu bias')):
+        _require_device(t, what)
+    H, W = int(H), int(W)
+    m, n, c = h.shape
+    if n != H * W or tuple(weight.shape) != (c, 1, 3, 3) or tuple(bias.shape) != (c,):
+        raise _lib.CffmError('dwconv_gelu: h %s with H=%d W=%d needs weight [%d,1,3,3] and bias [%d], got %s / %s'
+                             % (tuple(h.shape), H, W, c, c, tuple(weight.shape), tuple(bias.shape)))
+    return _DwconvGeluFn.apply(h, weight, bias, H, W)

@@ -9,7 +9,8 @@ logits, the probabilities and the permute copy of the token-row logits never exi
 PyTorch: the A/B partner in the tests and what CPU tensors get outside the emulator.
 
 Refusals (NotImplementedError), like the heads' for non-CFFM hyper-parameters: ``test_cfg.mode == 'slide'``, a neck, an auxiliary head --
-no CFFM config uses them.  The MiT backbone is not part of this package: the segmentor takes whatever ``BACKBONES`` builds.
+no CFFM config uses them.  The backbone is whatever ``BACKBONES`` builds: ``mit_b0`` .. ``mit_b5`` (backbone.py) as every CFFM config names them,
+``init_weights(pretrained=path)`` handing the checkpoint path on to the backbone.
 """
 import torch
 import torch.nn as nn
