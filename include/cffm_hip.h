@@ -18,6 +18,8 @@
  *   cffm_predict                     <->  EncoderDecoder_clips' resize, resize, softmax, flip, argmax
  *                                                         segmentors/encoder_decoder.py:367-378, :502-572
  *   cffm_dwconv_gelu_fwd / _bwd      <->  Mlp's DWConv + GELU of the MiT backbone  backbones/mix_transformer.py:48-55, 358-369
+ *   cffm_sra_attn_fwd / _bwd         <->  the attention core of the MiT backbone's Attention.forward (q k^T, scale, softmax, attn v)
+ *                                                         backbones/mix_transformer.py (Attention.forward)
  *
  * Conventions: every pointer is a DEVICE pointer (fp32 unless stated) borrowed for the duration of
  * the call; `stream` is a hipStream_t (NULL = default stream); work is enqueued asynchronously on it;
@@ -494,6 +496,26 @@ int cffm_dwconv_gelu_fwd(const float* h, const float* w, const float* b, float* 
 long cffm_dwconv_gelu_bwd_workspace_bytes(int M, int H, int W, int C);
 int cffm_dwconv_gelu_bwd(const float* h, const float* w, const float* b, const float* dout, float* dh, float* dw, float* db,
                          void* workspace, int M, int H, int W, int C, void* stream);
+
+/* ---- added under ABI 13, additive: the core of MiT's spatial-reduction attention (backbones/mix_transformer.py Attention.forward) ----
+ * Soft-max attention of N query rows against Nk key rows per (image, head), fp32, in the layouts the module's Linear layers produce:
+ *   q   [B][N][C]     C = heads * hd, head h = columns h*hd .. h*hd+hd-1                        (the output of self.q)
+ *   kv  [B][Nk][2C]   K of head h = columns h*hd .., V of head h = columns C + h*hd ..         (the output of self.kv)
+ *   out [B][N][C]     out[b,n,h*hd+c] = sum_k softmax_k(scale q_h[n] . k_h[k]) v_h[k][c]         (the reference's transpose(1,2).reshape)
+ *   lse [B][heads][N] scale max_k(q.k) + log sum_k exp(scale (q.k - max)); NULL in cffm_sra_attn_fwd = not wanted (inference)
+ * The score tensor never exists: keys are walked in tiles with an online soft-max, every product is the f32-input MFMA (fp32 operands, a
+ * k-ordered fp32 fmaf chain).  The backward recomputes the probabilities from q, kv and lse; dq [B][N][C] and both halves of dkv
+ * [B][Nk][2C] are written completely (the caller need not clear them); the dk / dv sums over the queries are partial slabs added in a
+ * fixed order (no atomics): the same bits run after run.  workspace: cffm_sra_attn_bwd_workspace_bytes bytes (< 0 for bad sizes),
+ * 16-byte aligned; every byte that is read is written by the same call.
+ * Limits: hd 32 or 64; B, N, Nk, heads >= 1 (no cap on Nk); B*heads <= 65535; B*N*C and B*Nk*2C below 2^31; scale positive and finite.
+ * Errors (nothing is enqueued, the outputs stay as they are): any of these limits, a null pointer (lse of the forward excepted) or one
+ * that is not 16-byte aligned.  No allocation, no host round trip: the calls can be captured into a HIP graph. */
+int cffm_sra_attn_fwd(const float* q, const float* kv, float* out, float* lse /* may be NULL: inference */,
+                      int B, int N, int Nk, int heads, int hd, float scale, void* stream);
+long cffm_sra_attn_bwd_workspace_bytes(int B, int N, int Nk, int heads, int hd);
+int cffm_sra_attn_bwd(const float* q, const float* kv, const float* out, const float* lse, const float* dout,
+                      float* dq, float* dkv, void* workspace, int B, int N, int Nk, int heads, int hd, float scale, void* stream);
 
 #ifdef __cplusplus
 }

@@ -135,6 +135,9 @@ SIGNATURES = {
     'cffm_dwconv_gelu_fwd': (ci, [vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     'cffm_dwconv_gelu_bwd_workspace_bytes': (cl, [ci, ci, ci, ci]),
     'cffm_dwconv_gelu_bwd': (ci, [vp] * 8 + [ci, ci, ci, ci, vp]),
+    'cffm_sra_attn_fwd': (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, vp]),
+    'cffm_sra_attn_bwd_workspace_bytes': (cl, [ci, ci, ci, ci, ci]),
+    'cffm_sra_attn_bwd': (ci, [vp] * 8 + [ci, ci, ci, ci, ci, cf, vp]),
 }
 
 

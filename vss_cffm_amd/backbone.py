@@ -7,8 +7,14 @@ attention + Mix-FFN with stochastic depth, and a LayerNorm; each stage hands a c
 The Mix-FFN is fc1 -> depthwise 3 x 3 Conv2d on the NCHW view -> GELU -> fc2.  With ``Mlp.dwconv_impl = 'hip'`` everything between the
 two Linear layers is ONE pass of libcffm_hip.so over the token rows (``ops.dwconv_gelu`` -> cffm_dwconv_gelu_fwd / _bwd): no NCHW view,
 no transpose copies, and two saved activations instead of three.  ``'torch'`` is the reference's op sequence in stock PyTorch: the A/B
-partner in the tests and what CPU tensors, other dtypes, other activations and dropout > 0 get.  Attention stays on PyTorch
-(matmul, softmax, matmul in the reference's order).
+partner in the tests and what CPU tensors, other dtypes, other activations and dropout > 0 get.
+
+The attention core -- everything between the q / kv Linear layers and proj -- is, with ``Attention.attn_impl = 'hip'``, one forward and
+one backward pass of the library (``ops.sra_attention`` -> cffm_sra_attn_fwd / _bwd): q and kv are read where the Linear layers left
+them, the score tensor [B, heads, N, Nk] never exists and one log-sum-exp per query is kept for the backward.  ``'torch'`` is the
+reference's reshape / permute, matmul, scale, softmax, matmul, transpose / reshape: the A/B partner in the tests and what CPU tensors,
+other dtypes, attention dropout > 0 and head sizes other than 32 / 64 get.  The `sr` convolution, its LayerNorm and the three Linear
+layers are stock PyTorch either way.
 """
 import math
 from functools import partial
@@ -18,7 +24,7 @@ import torch.nn as nn
 
 from . import _lib
 from .checkpoint import load_reference_checkpoint
-from .ops import dwconv_gelu
+from .ops import dwconv_gelu, sra_attention
 from .registry import BACKBONES
 
 
@@ -106,6 +112,9 @@ class Mlp(nn.Module):
 
 class Attention(nn.Module):
     """multi-head self-attention whose keys / values come from the map reduced by a strided `sr` convolution (sr_ratio > 1)"""
+    # 'hip': q k^T, scale, softmax, attn v in one kernel of libcffm_hip.so for fp32 GPU tensors (it raises when the library is missing);
+    # 'torch': the reference's op sequence (what everything else gets, and the A/B partner in the tests)
+    attn_impl = 'hip'
 
     def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, attn_drop=0., proj_drop=0., sr_ratio=1):
         super().__init__()
@@ -124,12 +133,23 @@ class Attention(nn.Module):
             self.norm = nn.LayerNorm(dim)
         self.apply(_init_weights)
 
+    def _fused(self, x):
+        return (self.attn_impl == 'hip' and (x.is_cuda or _lib._override is not None) and x.dtype == torch.float32
+                and self.attn_drop.p == 0 and x.shape[-1] // self.num_heads in (32, 64) and self.scale > 0)
+
+    def _reduced(self, x, H, W):
+        B, N, C = x.shape
+        return self.norm(self.sr(x.permute(0, 2, 1).reshape(B, C, H, W)).reshape(B, C, -1).permute(0, 2, 1))
+
     def forward(self, x, H, W):
         B, N, C = x.shape
+        if self._fused(x):
+            kv = self.kv(self._reduced(x, H, W) if self.sr_ratio > 1 else x)
+            return self.proj_drop(self.proj(sra_attention(self.q(x), kv, self.num_heads, self.scale)))
         hd = C // self.num_heads
         q = self.q(x).reshape(B, N, self.num_heads, hd).permute(0, 2, 1, 3)
         if self.sr_ratio > 1:
-            x = self.norm(self.sr(x.permute(0, 2, 1).reshape(B, C, H, W)).reshape(B, C, -1).permute(0, 2, 1))
+            x = self._reduced(x, H, W)
         k, v = self.kv(x).reshape(B, -1, 2, self.num_heads, hd).permute(2, 0, 3, 1, 4)
         attn = self.attn_drop(((q @ k.transpose(-2, -1)) * self.scale).softmax(dim=-1))
         return self.proj_drop(self.proj((attn @ v).transpose(1, 2).reshape(B, N, C)))

@@ -11,6 +11,7 @@
 #include "kmeans_kernels.h"
 #include "predict_kernels.h"
 #include "mixffn_kernels.h"
+#include "sra_kernels.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -2890,6 +2891,78 @@ int cffm_dwconv_gelu_bwd(const float* h, const float* w, const float* b, const f
     CFFM_LAUNCH(k_dwg_bwd2, ((unsigned)(nred + (G2.S * G2.C4 + 255) / 256)), (256), 0, st, (const float*)g, w, dh, (const f32x4*)part, dw, db, G2,
                 G1.S, nred);
     CHECK_LAUNCH("dwconv_gelu_bwd");
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------- spatial-reduction attention core (sra_kernels.h)
+}  // extern "C"
+static int sra_check(const char* who, int B, int N, int Nk, int heads, int hd, float scale) {
+    REQUIRE(hd == 32 || hd == 64, "%s: head size %d is not 32 or 64", who, hd);
+    REQUIRE(B >= 1 && N >= 1 && Nk >= 1 && heads >= 1, "%s: bad sizes B=%d N=%d Nk=%d heads=%d", who, B, N, Nk, heads);
+    REQUIRE(scale > 0.f && scale < INFINITY, "%s: scale %g must be positive and finite", who, (double)scale);
+    REQUIRE((long)B * heads <= 65535, "%s: B*heads = %ld is above 65535", who, (long)B * heads);
+    const long C = (long)heads * hd;
+    REQUIRE((long)B * N * C < (1L << 31) && 2L * B * Nk * C < (1L << 31),
+            "%s: B*N*C = %ld or B*Nk*2C = %ld is not below 2^31", who, (long)B * N * C, 2L * B * Nk * C);
+    return 0;
+}
+// query chunks of k_sra_bwd_dkv: enough workgroups to fill the device, at most 64 slabs; *tpc = 16-query tiles per chunk (a multiple of 4)
+static int sra_chunks(int B, int N, int Nk, int heads, int* tpc) {
+    const long groups = (long)B * heads * ((Nk + SRA_QB - 1) / SRA_QB), nqt = (N + 15) / 16;
+    const long want = std::max(1L, std::min(std::min(64L, nqt), (1024 + groups - 1) / groups));
+    *tpc = (int)(((nqt + want - 1) / want + 3) / 4 * 4);
+    return (int)((nqt + *tpc - 1) / *tpc);
+}
+static long sra_delta_floats(int B, int N, int heads) { return ((long)B * heads * N + 3) / 4 * 4; }
+// two query tiles per wave halve the K / V traffic; one when that leaves fewer than two workgroups per compute unit
+static bool sra_wide(int B, int N, int heads) { return (long)B * heads * ((N + 127) / 128) >= 512; }
+static bool sra_aligned(const void* p) { return p && (uintptr_t)p % 16 == 0; }
+extern "C" {
+int cffm_sra_attn_fwd(const float* q, const float* kv, float* out, float* lse, int B, int N, int Nk, int heads, int hd, float scale, void* stream) {
+    TRY(sra_check("sra_attn_fwd", B, N, Nk, heads, hd, scale));
+    REQUIRE(sra_aligned(q) && sra_aligned(kv) && sra_aligned(out) && (uintptr_t)lse % 16 == 0,
+            "sra_attn_fwd: q / kv / out must be non-null and q / kv / out / lse 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned gz = (unsigned)(B * heads);
+#define SRA_FWD(HD_, QW_) CFFM_LAUNCH((k_sra_fwd<HD_, QW_>), ((unsigned)((N + 64 * QW_ - 1) / (64 * QW_)), 1, gz), (256), 0, st, q, kv, out, lse, N, Nk, heads, scale)
+    if (sra_wide(B, N, heads)) { if (hd == 64) SRA_FWD(64, 2); else SRA_FWD(32, 2); }
+    else { if (hd == 64) SRA_FWD(64, 1); else SRA_FWD(32, 1); }
+#undef SRA_FWD
+    CHECK_LAUNCH("sra_attn_fwd");
+    return 0;
+}
+long cffm_sra_attn_bwd_workspace_bytes(int B, int N, int Nk, int heads, int hd) {
+    if (sra_check("sra_attn_bwd_workspace_bytes", B, N, Nk, heads, hd, 1.f)) return -1;
+    int tpc;
+    const int chunks = sra_chunks(B, N, Nk, heads, &tpc);
+    return 4 * (sra_delta_floats(B, N, heads) + (chunks > 1 ? 2L * chunks * B * Nk * heads * hd : 0L));
+}
+int cffm_sra_attn_bwd(const float* q, const float* kv, const float* out, const float* lse, const float* dout, float* dq, float* dkv,
+                      void* workspace, int B, int N, int Nk, int heads, int hd, float scale, void* stream) {
+    TRY(sra_check("sra_attn_bwd", B, N, Nk, heads, hd, scale));
+    REQUIRE(sra_aligned(q) && sra_aligned(kv) && sra_aligned(out) && sra_aligned(lse) && sra_aligned(dout) && sra_aligned(dq) && sra_aligned(dkv) &&
+            sra_aligned(workspace), "sra_attn_bwd: q / kv / out / lse / dout / dq / dkv / workspace must be non-null and 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned gz = (unsigned)(B * heads);
+    const double c = (double)scale * 1.4426950408889634;
+    const float chi = (float)c, clo = (float)(c - (double)chi);
+    int tpc;
+    const int chunks = sra_chunks(B, N, Nk, heads, &tpc);
+    float* delta = (float*)workspace;                            // [B][heads][N]
+    const long stride = 2L * B * Nk * heads * hd;                // floats of one slab [B][Nk][2C]
+    float* slab = chunks > 1 ? delta + sra_delta_floats(B, N, heads) : dkv;
+#define SRA_DQ(HD_, QW_) CFFM_LAUNCH((k_sra_bwd_dq<HD_, QW_>), ((unsigned)((N + 64 * QW_ - 1) / (64 * QW_)), 1, gz), (256), 0, st, q, kv, out, lse, dout, dq, delta, N, Nk, heads, scale, chi, clo)
+    if (sra_wide(B, N, heads)) { if (hd == 64) SRA_DQ(64, 2); else SRA_DQ(32, 2); }
+    else { if (hd == 64) SRA_DQ(64, 1); else SRA_DQ(32, 1); }
+#undef SRA_DQ
+#define SRA_DKV(HD_) CFFM_LAUNCH(k_sra_bwd_dkv<HD_>, ((unsigned)((Nk + SRA_QB - 1) / SRA_QB), (unsigned)chunks, gz), (256), 0, st, q, kv, lse, dout, (const float*)delta, slab, stride, tpc, N, Nk, heads, scale, chi, clo)
+    if (hd == 64) SRA_DKV(64); else SRA_DKV(32);
+#undef SRA_DKV
+    if (chunks > 1) {
+        const long n4 = stride / 4;
+        CFFM_LAUNCH(k_sra_dkv_sum, ((unsigned)std::min(2048L, (n4 + 255) / 256)), (256), 0, st, (const f32x4*)slab, (f32x4*)dkv, n4, n4, chunks);
+    }
+    CHECK_LAUNCH("sra_attn_bwd");
     return 0;
 }
 

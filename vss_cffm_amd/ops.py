@@ -1358,3 +1358,76 @@ def dwconv_gelu(h, weight, bias, H, W):
         raise _lib.CffmError('dwconv_gelu: h %s with H=%d W=%d needs weight [%d,1,3,3] and bias [%d], got %s / %s'
                              % (tuple(h.shape), H, W, c, c, tuple(weight.shape), tuple(bias.shape)))
     return _DwconvGeluFn.apply(h, weight, bias, H, W)
+
+
+# ---------------------------------------------------------------------------------------------- spatial-reduction attention core (MiT backbone)
+def _sra_forward(lib, q, kv, heads, scale, want_lse):
+    """q [B,N,C], kv [B,Nk,2C] contiguous -> (out [B,N,C], lse [B,heads,N] or None)"""
+    b, n, c = q.shape
+    nk = kv.shape[1]
+    out = torch.empty_like(q)
+    lse = torch.empty((b, heads, n), dtype=torch.float32, device=q.device) if want_lse else None
+    _lib.check(lib.cffm_sra_attn_fwd(_ptr(q), _ptr(kv), _ptr(out), _ptr(lse), b, n, nk, heads, c // heads, scale, _stream(q)), lib)
+    return out, lse
+
+
+def _sra_operand(t):
+    """contiguous and 16-byte aligned (a contiguous slice of a larger buffer may start anywhere)"""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class _SraAttnFn(torch.autograd.Function):
+    """softmax(scale q_h k_h^T) v_h per head on the Linear layers' own layouts (csrc/sra_kernels.h).  Saved: q, kv, out and one
+    log-sum-exp per (image, head, query) -- the probabilities are recomputed in the backward, whose workspace (delta + the partial dk / dv
+    slabs) lives only inside it."""
+
+    @staticmethod
+    def forward(ctx, q, kv, heads, scale):
+        lib = _lib.get()
+        # every input contiguous BEFORE the stream is looked up or anything is enqueued: a copy made later would be ordered against nothing
+        q, kv = _sra_operand(q), _sra_operand(kv)
+        out, lse = _sra_forward(lib, q, kv, heads, scale, True)
+        ctx.save_for_backward(q, kv, out, lse)
+        ctx.heads, ctx.scale = heads, scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.get()
+        q, kv, out, lse = ctx.saved_tensors
+        b, n, c = q.shape
+        nk, heads = kv.shape[1], ctx.heads
+        dout = _sra_operand(dout)
+        dq, dkv = torch.empty_like(q), torch.empty_like(kv)
+        nbytes = lib.cffm_sra_attn_bwd_workspace_bytes(b, n, nk, heads, c // heads)
+        if nbytes < 0:
+            raise _lib.CffmError('libcffm_hip: %s' % lib.cffm_last_error().decode())
+        ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device)
+        _lib.check(lib.cffm_sra_attn_bwd(_ptr(q), _ptr(kv), _ptr(out), _ptr(lse), _ptr(dout), _ptr(dq), _ptr(dkv), _ptr(ws), b, n, nk, heads,
+                                         c // heads, ctx.scale, _stream(q)), lib)
+        return dq, dkv, None, None
+
+
+def sra_attention(q, kv, num_heads, scale):
+    """The core of MiT's spatial-reduction attention (mix_transformer.py Attention.forward between the q / kv Linear layers and proj) in
+    one pass: q [B,N,C] and kv [B,Nk,2C] fp32 as the two Linear layers leave them (head h = columns h*hd .. of q; K = columns h*hd ..,
+    V = columns C + h*hd .. of kv; hd = C / num_heads, 32 or 64) -> softmax(scale q_h k_h^T) v_h as [B,N,C] in the reference's
+    transpose(1,2).reshape order.  The scores never exist.  Differentiable in q and kv (bit-reproducible); under no_grad, or when neither
+    requires grad, only the forward runs, without the log-sum-exp, and nothing is saved.  Launches on the current stream."""
+    if not isinstance(q, torch.Tensor) or not isinstance(kv, torch.Tensor) or q.dim() != 3 or kv.dim() != 3:
+        raise _lib.CffmError('sra_attention: q must be a [B,N,C] tensor and kv a [B,Nk,2C] tensor')
+    _require_device(q, 'sra_attention q')
+    _require_device(kv, 'sra_attention kv')
+    heads, scale = int(num_heads), float(scale)
+    b, n, c = q.shape
+    if heads < 1 or c % heads or c // heads not in (32, 64):
+        raise _lib.CffmError('sra_attention: C=%d with %d heads: the head size must be 32 or 64' % (c, heads))
+    if kv.shape[0] != b or kv.shape[2] != 2 * c or kv.device != q.device:
+        raise _lib.CffmError('sra_attention: q %s needs kv [%d,Nk,%d] on %s, got %s on %s'
+                             % (tuple(q.shape), b, 2 * c, q.device, tuple(kv.shape), kv.device))
+    if n < 1 or kv.shape[1] < 1:
+        raise _lib.CffmError('sra_attention: N=%d and Nk=%d must be at least 1' % (n, kv.shape[1]))
+    if torch.is_grad_enabled() and (q.requires_grad or kv.requires_grad):
+        return _SraAttnFn.apply(q, kv, heads, scale)
+    return _sra_forward(_lib.get(), _sra_operand(q.detach()), _sra_operand(kv.detach()), heads, scale, False)[0]
