@@ -20,6 +20,7 @@
  *   cffm_dwconv_gelu_fwd / _bwd      <->  Mlp's DWConv + GELU of the MiT backbone  backbones/mix_transformer.py:48-55, 358-369
  *   cffm_sra_attn_fwd / _bwd         <->  the attention core of the MiT backbone's Attention.forward (q k^T, scale, softmax, attn v)
  *                                                         backbones/mix_transformer.py (Attention.forward)
+ *   cffm_sr_ln_fwd / _bwd            <->  the `sr` Conv2d (kernel = stride = sr_ratio) + LayerNorm in front of kv, same forward
  *
  * Conventions: every pointer is a DEVICE pointer (fp32 unless stated) borrowed for the duration of
  * the call; `stream` is a hipStream_t (NULL = default stream); work is enqueued asynchronously on it;
@@ -516,6 +517,31 @@ int cffm_sra_attn_fwd(const float* q, const float* kv, float* out, float* lse /*
 long cffm_sra_attn_bwd_workspace_bytes(int B, int N, int Nk, int heads, int hd);
 int cffm_sra_attn_bwd(const float* q, const float* kv, const float* out, const float* lse, const float* dout,
                       float* dq, float* dkv, void* workspace, int B, int N, int Nk, int heads, int hd, float scale, void* stream);
+
+/* ---- added under ABI 13, additive: the spatial-reduction Conv2d + LayerNorm of MiT's Attention (sr_ratio > 1) on token rows ----
+ * What `self.norm(self.sr(x.permute(0, 2, 1).reshape(B, C, H, W)).reshape(B, C, -1).permute(0, 2, 1))` computes, as one GEMM with a
+ * LayerNorm epilogue (kernel = stride: the windows do not overlap):
+ *   x, dx    [B][H*W][C]       token rows (row-major pixels, channel fastest)
+ *   w, dw    [C][C][s][s]      the Conv2d's own weight layout (co, ci, ky, kx); b, db [C]; gamma, beta, dgamma, dbeta [C] (the LayerNorm)
+ *   Ho = H / s, Wo = W / s (rounded down), M = B*Ho*Wo
+ *   z        [M][C]            z[(b,oy,ox), co] = b[co] + sum_{ky,kx,ci} w[co,ci,ky,kx] x[b, (oy*s+ky)*W + ox*s+kx, ci]
+ *   stats    [M][2]            mean and rstd = 1 / sqrt(var + eps) of each row of z (variance of the centred values, biased)
+ *   out      [M][C]            (z - mean) * rstd * gamma + beta
+ * z and stats are outputs of the forward kept for the backward; both NULL = not wanted (inference).  Pixel rows >= Ho*s and columns >=
+ * Wo*s are never read; their dx is written as zero, so dx, dw, db, dgamma and dbeta are written completely (the caller need not clear
+ * them).  Every product is the f32-input MFMA (fp32 operands, an fp32 fmaf chain); all sums are taken in a fixed order (no atomics):
+ * the same bits run after run.  workspace: cffm_sr_ln_bwd_workspace_bytes bytes (< 0 for bad sizes), 16-byte aligned; every byte that
+ * is read is written by the same call.
+ * Limits: s 2, 4 or 8; C a multiple of 16 in 16..512; B >= 1, H >= s, W >= s; B*H*W*C below 2^31; eps finite and >= 0.
+ * Errors (nothing is enqueued, the outputs stay as they are): any of these limits, a null pointer (z and stats of the forward excepted,
+ * together), only one of z and stats, or a pointer that is not 16-byte aligned.  No allocation, no host round trip: the calls can be
+ * captured into a HIP graph. */
+int cffm_sr_ln_fwd(const float* x, const float* w, const float* b, const float* gamma, const float* beta, float* out,
+                   float* z /* may be NULL */, float* stats /* NULL with z */, int B, int H, int W, int C, int s, float eps, void* stream);
+long cffm_sr_ln_bwd_workspace_bytes(int B, int H, int W, int C, int s);
+int cffm_sr_ln_bwd(const float* x, const float* w, const float* gamma, const float* z, const float* stats, const float* dout, float* dx,
+                   float* dw, float* db, float* dgamma, float* dbeta, void* workspace, int B, int H, int W, int C, int s, float eps,
+                   void* stream);
 
 #ifdef __cplusplus
 }

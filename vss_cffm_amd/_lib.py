@@ -138,6 +138,9 @@ SIGNATURES = {
     'cffm_sra_attn_fwd': (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, vp]),
     'cffm_sra_attn_bwd_workspace_bytes': (cl, [ci, ci, ci, ci, ci]),
     'cffm_sra_attn_bwd': (ci, [vp] * 8 + [ci, ci, ci, ci, ci, cf, vp]),
+    'cffm_sr_ln_fwd': (ci, [vp] * 8 + [ci, ci, ci, ci, ci, cf, vp]),
+    'cffm_sr_ln_bwd_workspace_bytes': (cl, [ci, ci, ci, ci, ci]),
+    'cffm_sr_ln_bwd': (ci, [vp] * 12 + [ci, ci, ci, ci, ci, cf, vp]),
 }
 
 

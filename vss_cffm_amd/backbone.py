@@ -13,8 +13,14 @@ The attention core -- everything between the q / kv Linear layers and proj -- is
 one backward pass of the library (``ops.sra_attention`` -> cffm_sra_attn_fwd / _bwd): q and kv are read where the Linear layers left
 them, the score tensor [B, heads, N, Nk] never exists and one log-sum-exp per query is kept for the backward.  ``'torch'`` is the
 reference's reshape / permute, matmul, scale, softmax, matmul, transpose / reshape: the A/B partner in the tests and what CPU tensors,
-other dtypes, attention dropout > 0 and head sizes other than 32 / 64 get.  The `sr` convolution, its LayerNorm and the three Linear
-layers are stock PyTorch either way.
+other dtypes, attention dropout > 0 and head sizes other than 32 / 64 get.
+
+In front of kv, stages with sr_ratio > 1 reduce the map with the `sr` convolution (kernel = stride = sr_ratio) and a LayerNorm.  With
+``Attention.sr_impl = 'hip'`` both are one GEMM with a LayerNorm epilogue on the token rows (``ops.sr_reduce`` -> cffm_sr_ln_fwd / _bwd):
+no NCHW view, no transposes, the Conv2d weight read in its own layout.  ``'torch'`` is the reference's permute / reshape, Conv2d,
+reshape / permute, LayerNorm: the default (the fused pass is exact fp32 but, as measured, not faster at model level),
+the A/B partner in the tests and what CPU tensors, other dtypes and shapes outside the kernel's limits get.  `sr_impl` is independent
+of `attn_impl`.  The three Linear layers are stock PyTorch either way.
 """
 import math
 from functools import partial
@@ -24,7 +30,7 @@ import torch.nn as nn
 
 from . import _lib
 from .checkpoint import load_reference_checkpoint
-from .ops import dwconv_gelu, sra_attention
+from .ops import dwconv_gelu, sr_reduce, sr_reduce_supported, sra_attention
 from .registry import BACKBONES
 
 
@@ -115,6 +121,10 @@ class Attention(nn.Module):
     # 'hip': q k^T, scale, softmax, attn v in one kernel of libcffm_hip.so for fp32 GPU tensors (it raises when the library is missing);
     # 'torch': the reference's op sequence (what everything else gets, and the A/B partner in the tests)
     attn_impl = 'hip'
+    # 'hip': the `sr` convolution + LayerNorm as one pass of libcffm_hip.so over the token rows for fp32 GPU tensors inside the kernel's
+    # limits (it raises when the library is missing); 'torch': the reference's op sequence, what everything else gets -- and the
+    # default: as measured the fused pass does not make a mit_b1 training pass faster
+    sr_impl = 'torch'
 
     def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, attn_drop=0., proj_drop=0., sr_ratio=1):
         super().__init__()
@@ -137,8 +147,15 @@ class Attention(nn.Module):
         return (self.attn_impl == 'hip' and (x.is_cuda or _lib._override is not None) and x.dtype == torch.float32
                 and self.attn_drop.p == 0 and x.shape[-1] // self.num_heads in (32, 64) and self.scale > 0)
 
+    def _sr_fused(self, x, H, W):
+        # (decided by the tensors' dtype alone, as _fused: under torch.autocast the 'hip' pass stays fp32 where the Conv2d would not)
+        return (self.sr_impl == 'hip' and self.sr_ratio > 1 and (x.is_cuda or _lib._override is not None) and x.dtype == torch.float32
+                and self.sr.weight.dtype == torch.float32 and sr_reduce_supported(x.shape[0], H, W, x.shape[2], self.sr_ratio))
+
     def _reduced(self, x, H, W):
         B, N, C = x.shape
+        if self._sr_fused(x, H, W):
+            return sr_reduce(x, self.sr.weight, self.sr.bias, self.norm.weight, self.norm.bias, H, W, self.sr_ratio, self.norm.eps)
         return self.norm(self.sr(x.permute(0, 2, 1).reshape(B, C, H, W)).reshape(B, C, -1).permute(0, 2, 1))
 
     def forward(self, x, H, W):

@@ -12,6 +12,7 @@
 #include "predict_kernels.h"
 #include "mixffn_kernels.h"
 #include "sra_kernels.h"
+#include "srln_kernels.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -2963,6 +2964,81 @@ int cffm_sra_attn_bwd(const float* q, const float* kv, const float* out, const f
         CFFM_LAUNCH(k_sra_dkv_sum, ((unsigned)std::min(2048L, (n4 + 255) / 256)), (256), 0, st, (const f32x4*)slab, (f32x4*)dkv, n4, n4, chunks);
     }
     CHECK_LAUNCH("sra_attn_bwd");
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------- spatial-reduction conv + LayerNorm (srln_kernels.h)
+}  // extern "C"
+static int srln_check(const char* who, int B, int H, int W, int C, int s, float eps, SrGeom* G) {
+    REQUIRE(s == 2 || s == 4 || s == 8, "%s: s=%d is not 2, 4 or 8", who, s);
+    REQUIRE(C >= 16 && C <= SRLN_MAXC && C % 16 == 0, "%s: C=%d must be a multiple of 16 in 16..%d", who, C, SRLN_MAXC);
+    REQUIRE(B >= 1 && H >= s && W >= s, "%s: bad sizes B=%d H=%d W=%d (H and W at least s=%d)", who, B, H, W, s);
+    REQUIRE(eps >= 0.f && eps < INFINITY, "%s: eps %g must be finite and not negative", who, (double)eps);
+    REQUIRE((long)B * H * W * C < (1L << 31), "%s: B*H*W*C = %ld is not below 2^31", who, (long)B * H * W * C);
+    G->B = B; G->H = H; G->W = W; G->C = C; G->Ho = H / s; G->Wo = W / s; G->M = B * G->Ho * G->Wo;
+    return 0;
+}
+static bool srln_aligned(const void* p) { return p && (uintptr_t)p % 16 == 0; }
+static long srln_dz_floats(const SrGeom& G) { return (long)G.M * G.C; }                       // (a multiple of 16)
+static int srln_row_blocks(const SrGeom& G) { return (G.M + 15) / 16; }
+// column tiles per wave of k_srln_fwd: the largest of 5, 4, 2, 1 that divides C / 16
+static int srln_ncw(int C) { const int nc = C / 16; return nc % 5 == 0 ? 5 : nc % 4 == 0 ? 4 : nc % 2 == 0 ? 2 : 1; }
+template <int S>
+static void srln_launch_fwd(int ncw, unsigned grid, hipStream_t st, const float* x, const float* w, const float* b, const float* gamma,
+                            const float* beta, float* out, float* z, float* stats, SrGeom G, float eps) {
+#define SRLN_FWD(NCW_) CFFM_LAUNCH((k_srln_fwd<S, NCW_>), (grid), (512), 0, st, x, w, b, gamma, beta, out, z, stats, G, eps)
+    if (ncw == 5) SRLN_FWD(5); else if (ncw == 4) SRLN_FWD(4); else if (ncw == 2) SRLN_FWD(2); else SRLN_FWD(1);
+#undef SRLN_FWD
+}
+template <int S>
+static void srln_launch_bwd(hipStream_t st, const float* x, const float* w, const float* gamma, const float* z, const float* stats,
+                            const float* dout, float* dx, float* dw, float* db, float* dgamma, float* dbeta, float* dz, float* part, SrGeom G) {
+    constexpr int S2 = S * S, PQ = S2 < 16 ? S2 / 4 : 4;
+    const int nrb = srln_row_blocks(G), C = G.C;
+    const long units = (long)nrb * (C / 16) * (S2 / (4 * PQ));
+    CFFM_LAUNCH(k_srln_bwd_rows<S>, ((unsigned)nrb), (256), 0, st, z, stats, gamma, dout, dz, part, dx, G);
+    CFFM_LAUNCH(k_srln_colsum, ((unsigned)((3 * C + 255) / 256)), (256), 0, st, (const float*)part, dgamma, dbeta, db, nrb, C);
+    CFFM_LAUNCH(k_srln_bwd_dx<S>, ((unsigned)((units + 3) / 4)), (256), 0, st, (const float*)dz, w, dx, G, units);
+    CFFM_LAUNCH(k_srln_bwd_dw<S>, ((unsigned)(S2 / 4), (unsigned)(C / 16), (unsigned)(C / 16)), (512), 0, st, (const float*)dz, x, dw, G);
+}
+extern "C" {
+int cffm_sr_ln_fwd(const float* x, const float* w, const float* b, const float* gamma, const float* beta, float* out, float* z, float* stats,
+                   int B, int H, int W, int C, int s, float eps, void* stream) {
+    SrGeom G;
+    TRY(srln_check("sr_ln_fwd", B, H, W, C, s, eps, &G));
+    REQUIRE(srln_aligned(x) && srln_aligned(w) && srln_aligned(b) && srln_aligned(gamma) && srln_aligned(beta) && srln_aligned(out) &&
+            (uintptr_t)z % 16 == 0 && (uintptr_t)stats % 16 == 0,
+            "sr_ln_fwd: x / w / b / gamma / beta / out must be non-null and all pointers 16-byte aligned");
+    REQUIRE(!z == !stats, "sr_ln_fwd: z and stats must both be given or both be null");
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned grid = (unsigned)srln_row_blocks(G);
+    const int ncw = srln_ncw(C);
+    if (s == 2) srln_launch_fwd<2>(ncw, grid, st, x, w, b, gamma, beta, out, z, stats, G, eps);
+    else if (s == 4) srln_launch_fwd<4>(ncw, grid, st, x, w, b, gamma, beta, out, z, stats, G, eps);
+    else srln_launch_fwd<8>(ncw, grid, st, x, w, b, gamma, beta, out, z, stats, G, eps);
+    CHECK_LAUNCH("sr_ln_fwd");
+    return 0;
+}
+long cffm_sr_ln_bwd_workspace_bytes(int B, int H, int W, int C, int s) {
+    SrGeom G;
+    if (srln_check("sr_ln_bwd_workspace_bytes", B, H, W, C, s, 0.f, &G)) return -1;
+    return 4 * (srln_dz_floats(G) + 3L * srln_row_blocks(G) * C);
+}
+int cffm_sr_ln_bwd(const float* x, const float* w, const float* gamma, const float* z, const float* stats, const float* dout, float* dx,
+                   float* dw, float* db, float* dgamma, float* dbeta, void* workspace, int B, int H, int W, int C, int s, float eps,
+                   void* stream) {
+    SrGeom G;
+    TRY(srln_check("sr_ln_bwd", B, H, W, C, s, eps, &G));
+    REQUIRE(srln_aligned(x) && srln_aligned(w) && srln_aligned(gamma) && srln_aligned(z) && srln_aligned(stats) && srln_aligned(dout) &&
+            srln_aligned(dx) && srln_aligned(dw) && srln_aligned(db) && srln_aligned(dgamma) && srln_aligned(dbeta) && srln_aligned(workspace),
+            "sr_ln_bwd: x / w / gamma / z / stats / dout / dx / dw / db / dgamma / dbeta / workspace must be non-null and 16-byte aligned");
+    float* dz = (float*)workspace;                               // [M][C]
+    float* part = dz + srln_dz_floats(G);                        // [row blocks][3][C]
+    hipStream_t st = (hipStream_t)stream;
+    if (s == 2) srln_launch_bwd<2>(st, x, w, gamma, z, stats, dout, dx, dw, db, dgamma, dbeta, dz, part, G);
+    else if (s == 4) srln_launch_bwd<4>(st, x, w, gamma, z, stats, dout, dx, dw, db, dgamma, dbeta, dz, part, G);
+    else srln_launch_bwd<8>(st, x, w, gamma, z, stats, dout, dx, dw, db, dgamma, dbeta, dz, part, G);
+    CHECK_LAUNCH("sr_ln_bwd");
     return 0;
 }
 

@@ -10,6 +10,7 @@ import ctypes as C
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib, geometry
 
@@ -1431,3 +1432,89 @@ def sra_attention(q, kv, num_heads, scale):
     if torch.is_grad_enabled() and (q.requires_grad or kv.requires_grad):
         return _SraAttnFn.apply(q, kv, heads, scale)
     return _sra_forward(_lib.get(), _sra_operand(q.detach()), _sra_operand(kv.detach()), heads, scale, False)[0]
+
+
+# ---------------------------------------------------------------------------------------------- spatial-reduction conv + LayerNorm (MiT backbone)
+# The limits of cffm_sr_ln_fwd / _bwd, a copy of srln_check and SRLN_MAXC in csrc/cffm_hip.hip / srln_kernels.h (stated in
+# include/cffm_hip.h): change both together.  tests/test_sr_ln.py::run_refusals walks every limit through both copies.
+SR_RATIOS = (2, 4, 8)
+SR_MAX_C = 512
+
+
+def sr_reduce_supported(B, H, W, C, sr_ratio):
+    """whether [B, H*W, C] rows with this reduction ratio are inside the limits of the library's kernels"""
+    return (sr_ratio in SR_RATIOS and C % 16 == 0 and 16 <= C <= SR_MAX_C and B >= 1 and H >= sr_ratio and W >= sr_ratio
+            and B * H * W * C < 2 ** 31)
+
+
+def _sr_forward(lib, x, weight, bias, ln_weight, ln_bias, H, W, s, eps, want_saved):
+    """contiguous, aligned operands -> (out [B,Ho*Wo,C], z or None, stats or None)"""
+    b, _, c = x.shape
+    nk = (H // s) * (W // s)
+    out = torch.empty((b, nk, c), dtype=torch.float32, device=x.device)
+    z = torch.empty_like(out) if want_saved else None
+    stats = torch.empty((b * nk, 2), dtype=torch.float32, device=x.device) if want_saved else None
+    _lib.check(lib.cffm_sr_ln_fwd(_ptr(x), _ptr(weight), _ptr(bias), _ptr(ln_weight), _ptr(ln_bias), _ptr(out), _ptr(z), _ptr(stats),
+                                  b, H, W, c, s, eps, _stream(x)), lib)
+    return out, z, stats
+
+
+class _SrReduceFn(torch.autograd.Function):
+    """LayerNorm(Conv2d(C, C, s, s)(x as NCHW)) on token rows (csrc/srln_kernels.h).  Saved: x, the weights, and the M = B Ho Wo rows
+    before the LayerNorm with their (mean, rstd); the backward's workspace (dz + the partial column sums) lives only inside it."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, ln_weight, ln_bias, H, W, s, eps):
+        lib = _lib.get()
+        # every input contiguous BEFORE the stream is looked up or anything is enqueued: a copy made later would be ordered against nothing
+        x, weight, bias, ln_weight, ln_bias = (_sra_operand(t) for t in (x, weight, bias, ln_weight, ln_bias))
+        out, z, stats = _sr_forward(lib, x, weight, bias, ln_weight, ln_bias, H, W, s, eps, True)
+        ctx.save_for_backward(x, weight, ln_weight, z, stats)
+        ctx.dims = (H, W, s, eps)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        # (one library call computes all five gradients, also when only some are asked for; those not asked for are dropped)
+        lib = _lib.get()
+        x, weight, ln_weight, z, stats = ctx.saved_tensors
+        H, W, s, eps = ctx.dims
+        b, _, c = x.shape
+        dout = _sra_operand(dout)
+        dx, dw = torch.empty_like(x), torch.empty_like(weight)
+        db, dgamma, dbeta = (torch.empty(c, dtype=torch.float32, device=x.device) for _ in range(3))
+        nbytes = lib.cffm_sr_ln_bwd_workspace_bytes(b, H, W, c, s)
+        if nbytes < 0:
+            raise _lib.CffmError('libcffm_hip: %s' % lib.cffm_last_error().decode())
+        ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
+        _lib.check(lib.cffm_sr_ln_bwd(_ptr(x), _ptr(weight), _ptr(ln_weight), _ptr(z), _ptr(stats), _ptr(dout), _ptr(dx), _ptr(dw), _ptr(db),
+                                      _ptr(dgamma), _ptr(dbeta), _ptr(ws), b, H, W, c, s, eps, _stream(x)), lib)
+        return tuple(g if need else None for g, need in zip((dx, dw, db, dgamma, dbeta), ctx.needs_input_grad)) + (None,) * 4
+
+
+def sr_reduce(x, weight, bias, ln_weight, ln_bias, H, W, sr_ratio, eps=1e-5):
+    """The spatial reduction in front of MiT's kv Linear (mix_transformer.py Attention.forward, sr_ratio > 1) in one pass: x [B, H*W, C]
+    fp32 token rows, weight [C,C,s,s] and bias [C] of Conv2d(C, C, kernel_size=s, stride=s), ln_weight / ln_bias [C] of the LayerNorm
+    -> LayerNorm(conv(x as NCHW)) as token rows [B, (H//s)*(W//s), C].  No NCHW view, no transposes; the weight is read in the Conv2d's
+    own layout.  Differentiable in all five tensors (bit-reproducible; the dx of pixel rows / columns beyond the last full window is 0);
+    under no_grad, or when nothing requires grad, only the forward runs and nothing is saved.  s in 2, 4, 8; C a multiple of 16, at most
+    512; H, W >= s.  Launches on the current stream."""
+    ts = (x, weight, bias, ln_weight, ln_bias)
+    if not all(isinstance(t, torch.Tensor) for t in ts) or x.dim() != 3:
+        raise _lib.CffmError('sr_reduce: x must be a [B, H*W, C] tensor, the weights tensors')
+    for t, what in zip(ts, ('x', 'weight', 'bias', 'ln_weight', 'ln_bias')):
+        _require_device(t, 'sr_reduce ' + what)
+    H, W, s, eps = int(H), int(W), int(sr_ratio), float(eps)
+    b, n, c = x.shape
+    if n != H * W or tuple(weight.shape) != (c, c, s, s) or any(tuple(t.shape) != (c,) for t in ts[2:]):
+        raise _lib.CffmError('sr_reduce: x %s with H=%d W=%d s=%d needs weight [%d,%d,%d,%d] and bias / ln_weight / ln_bias [%d], got %s'
+                             % (tuple(x.shape), H, W, s, c, c, s, s, c, [tuple(t.shape) for t in ts[1:]]))
+    if any(t.device != x.device for t in ts[1:]):
+        raise _lib.CffmError('sr_reduce: all tensors must be on %s' % (x.device,))
+    if not sr_reduce_supported(b, H, W, c, s) or not 0 <= eps < float('inf'):
+        raise _lib.CffmError('sr_reduce: B=%d H=%d W=%d C=%d s=%d eps=%g outside the limits (s in 2, 4, 8; C a multiple of 16 in 16..%d; '
+                             'H, W >= s; B*H*W*C < 2^31; eps finite, >= 0)' % (b, H, W, c, s, eps, SR_MAX_C))
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        return _SrReduceFn.apply(x, weight, bias, ln_weight, ln_bias, H, W, s, eps)
+    return _sr_forward(_lib.get(), *(_sra_operand(t.detach()) for t in ts), H, W, s, eps, False)[0]
