@@ -543,6 +543,53 @@ int cffm_sr_ln_bwd(const float* x, const float* w, const float* gamma, const flo
                    float* dw, float* db, float* dgamma, float* dbeta, void* workspace, int B, int H, int W, int C, int s, float eps,
                    void* stream);
 
+/* ---- added under ABI 13, additive: LayerNorm of token rows at any width, and one MiT stage's inference forward per call ----
+ * LayerNorm over the C channels of fp32 token rows, C a multiple of 4 in 16..512 (csrc/mitln_kernels.h): a row is held in registers, the
+ * mean is taken first and the variance from the centred values, rstd = 1 / sqrt(var + eps); fixed summation order, no atomics: the same
+ * bits run after run.  Inference only (nothing is saved).
+ *   cffm_ln_rows        out[M][C] = LN(x[M][C])
+ *   cffm_nchw_ln_rows   x_nchw [B][C][H][W] -> out_rows [B][H*W][C], normalised: OverlapPatchEmbed's flatten(2).transpose(1, 2) + norm
+ *   cffm_ln_rows_nchw   x_rows [B][H*W][C] -> out_nchw [B][C][H][W], normalised: a stage's norm + reshape(B, H, W, C).permute(0, 3, 1, 2)
+ * Errors (nothing is enqueued, the outputs stay as they are): C outside the limits, M / B / H / W < 1, M*C or B*C*H*W >= 2^31, eps
+ * negative or not finite, a null pointer or one that is not 16-byte aligned.  No workspace, no allocation, no host round trip. */
+int cffm_ln_rows(const float* x, const float* gamma, const float* beta, float* out, long M, int C, float eps, void* stream);
+int cffm_nchw_ln_rows(const float* x_nchw, const float* gamma, const float* beta, float* out_rows, int B, int C, int H, int W, float eps,
+                      void* stream);
+int cffm_ln_rows_nchw(const float* x_rows, const float* gamma, const float* beta, float* out_nchw, int B, int C, int H, int W, float eps,
+                      void* stream);
+
+/* One stage of a Mix Transformer (backbones/mix_transformer.py forward_features, one iteration of its loop) in eval mode, behind the
+ * patch embedding's convolution: conv_nchw [B,C,H,W] (patch_embed.proj's output) -> out_nchw [B,C,H,W] (what the stage hands to the head):
+ *   cffm_nchw_ln_rows (patch_embed.norm);
+ *   per block: LN (norm1) | q GEMM | sr conv + LN (sr_ratio > 1: cffm_sr_ln_fwd's kernel) | kv GEMM | attention (cffm_sra_attn_fwd's
+ *     kernel, no lse) | proj GEMM + bias + residual | LN (norm2) | fc1 GEMM | depthwise 3x3 + GELU (cffm_dwconv_gelu_fwd's kernel) |
+ *     fc2 GEMM + bias + residual;
+ *   cffm_ln_rows_nchw (norm_i).
+ * The Linear layers are the library's three-pass bf16-split GEMMs (fp32 operands split into bf16 hi + lo, fp32 accumulation).
+ * Device pointers, each tensor in the nn.Module's own layout (Linear [out][in], sr [C][C][s][s], dwconv [hidden][1][3][3]); q_b / kv_b
+ * may be NULL (qkv_bias=False); sr_w / sr_b / srn_g / srn_b are NULL if and only if sr_ratio == 1.  No prepared copies are made or kept.
+ * Everything is enqueued on `stream` alone: no side streams, no allocation, no host synchronisation -- the call can be captured into a
+ * HIP graph as a single chain.  ws: cffm_mit_stage_infer_ws_floats(cfg) floats (it depends on the cfg, not on depth), 16-byte aligned;
+ * every byte of it that is read is written by the same call.
+ * Limits: head size C / heads 32 or 64; C a multiple of 16 in 16..512; hidden a multiple of 4; sr_ratio 1, 2, 4 or 8 and H, W >= sr_ratio;
+ * B*heads <= 65535; B*H*W*max(2C, hidden) below 2^30 (the GEMMs address an operand with 32-bit byte offsets); scale positive and finite;
+ * every eps finite and >= 0.  Errors (nothing is enqueued, the output stays as it is; cffm_mit_stage_infer_ws_floats returns < 0): any of
+ * these limits, a null pointer where one is required, a pointer that is not 16-byte aligned, conv_nchw == out_nchw. */
+typedef struct {
+    const float *n1_g, *n1_b, *q_w, *q_b, *kv_w, *kv_b, *sr_w, *sr_b, *srn_g, *srn_b, *proj_w, *proj_b,
+                *n2_g, *n2_b, *fc1_w, *fc1_b, *dw_w, *dw_b, *fc2_w, *fc2_b;
+} cffm_mit_block_params;
+typedef struct {
+    int B, H, W, C, heads, hidden, sr_ratio, depth;
+    float scale;                                    /* the attention's q.k scale */
+    float eps_embed, eps_block, eps_sr, eps_out;    /* patch_embed.norm | norm1 and norm2 of every block | attn.norm | norm_i */
+} cffm_mit_stage_cfg;
+long cffm_mit_stage_infer_ws_floats(const cffm_mit_stage_cfg* c);          /* < 0: unsupported sizes */
+int cffm_mit_stage_infer(const cffm_mit_stage_cfg* c, const cffm_mit_block_params* blocks /* host [depth] */,
+                         const float* embed_g, const float* embed_b, const float* out_g, const float* out_b,
+                         const float* conv_nchw /* [B,C,H,W]: patch_embed.proj's output */, float* out_nchw /* [B,C,H,W] */,
+                         float* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,7 +37,20 @@ class GtcPtrs(C.Structure):
                                   'fc1_w', 'fc1_b', 'fc2_w', 'fc2_b')]
 
 
+class MitBlockPtrs(C.Structure):
+    """cffm_mit_block_params"""
+    _fields_ = [(n, vp) for n in ('n1_g', 'n1_b', 'q_w', 'q_b', 'kv_w', 'kv_b', 'sr_w', 'sr_b', 'srn_g', 'srn_b', 'proj_w', 'proj_b',
+                                  'n2_g', 'n2_b', 'fc1_w', 'fc1_b', 'dw_w', 'dw_b', 'fc2_w', 'fc2_b')]
+
+
+class MitStageCfg(C.Structure):
+    """cffm_mit_stage_cfg"""
+    _fields_ = ([(n, ci) for n in ('B', 'H', 'W', 'C', 'heads', 'hidden', 'sr_ratio', 'depth')]
+                + [(n, cf) for n in ('scale', 'eps_embed', 'eps_block', 'eps_sr', 'eps_out')])
+
+
 GP, BP = C.POINTER(Geom), C.POINTER(BlockPtrs)
+MBP, MCP = C.POINTER(MitBlockPtrs), C.POINTER(MitStageCfg)
 GTP = C.POINTER(GtcPtrs)
 P4 = vp * 4
 
@@ -141,6 +154,11 @@ SIGNATURES = {
     'cffm_sr_ln_fwd': (ci, [vp] * 8 + [ci, ci, ci, ci, ci, cf, vp]),
     'cffm_sr_ln_bwd_workspace_bytes': (cl, [ci, ci, ci, ci, ci]),
     'cffm_sr_ln_bwd': (ci, [vp] * 12 + [ci, ci, ci, ci, ci, cf, vp]),
+    'cffm_ln_rows': (ci, [vp, vp, vp, vp, cl, ci, cf, vp]),
+    'cffm_nchw_ln_rows': (ci, [vp, vp, vp, vp, ci, ci, ci, ci, cf, vp]),
+    'cffm_ln_rows_nchw': (ci, [vp, vp, vp, vp, ci, ci, ci, ci, cf, vp]),
+    'cffm_mit_stage_infer_ws_floats': (cl, [MCP]),
+    'cffm_mit_stage_infer': (ci, [MCP, MBP, vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 

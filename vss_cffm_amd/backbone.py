@@ -21,6 +21,12 @@ no NCHW view, no transposes, the Conv2d weight read in its own layout.  ``'torch
 reshape / permute, LayerNorm: the default (the fused pass is exact fp32 but, as measured, not faster at model level),
 the A/B partner in the tests and what CPU tensors, other dtypes and shapes outside the kernel's limits get.  `sr_impl` is independent
 of `attn_impl`.  The three Linear layers are stock PyTorch either way.
+
+For inference, ``MixVisionTransformer.stage_impl = 'hip'`` runs everything of a stage behind ``patch_embed.proj`` -- the embedding's
+LayerNorm, every block, the stage's LayerNorm and the change to an NCHW map -- as ONE library call (``ops.mit_stage_infer`` ->
+cffm_mit_stage_infer), the Linear layers as the library's bf16-split GEMMs.  ``'torch'`` (the default) is the path described above.  A
+stage takes the call only when nothing would be differentiated and it is inside the library's limits (`_stage_fused`); any other stage
+takes the path above, stage by stage and silently.  `dwconv_impl`, `attn_impl` and `sr_impl` have no say in the stage call.
 """
 import math
 from functools import partial
@@ -30,7 +36,7 @@ import torch.nn as nn
 
 from . import _lib
 from .checkpoint import load_reference_checkpoint
-from .ops import dwconv_gelu, sr_reduce, sr_reduce_supported, sra_attention
+from .ops import dwconv_gelu, mit_stage_cfg, mit_stage_infer, mit_stage_supported, mit_stage_tensors, sr_reduce, sr_reduce_supported, sra_attention
 from .registry import BACKBONES
 
 
@@ -209,6 +215,11 @@ class OverlapPatchEmbed(nn.Module):
 
 
 class MixVisionTransformer(nn.Module):
+    # 'hip': under no_grad (or with nothing that requires grad) each stage behind its patch-embedding convolution is one call of
+    # libcffm_hip.so for fp32 GPU tensors inside the library's limits (it raises when the library is missing); 'torch': the modules'
+    # own forward, what everything else gets -- and the default: whether the call is faster is measured, not assumed
+    stage_impl = 'torch'
+
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dims=[64, 128, 256, 512], num_heads=[1, 2, 4, 8],
                  mlp_ratios=[4, 4, 4, 4], qkv_bias=False, qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.,
                  norm_layer=nn.LayerNorm, depths=[3, 4, 6, 3], sr_ratios=[8, 4, 2, 1]):
@@ -262,10 +273,67 @@ class MixVisionTransformer(nn.Module):
     def no_weight_decay(self):
         return {'pos_embed1', 'pos_embed2', 'pos_embed3', 'pos_embed4', 'cls_token'}
 
+    def _stage_fused(self, i, x):
+        """whether stage i takes the one-call inference path for this input (the convolution's output shape decides the sizes)"""
+        pe, blocks, norm = getattr(self, 'patch_embed%d' % i), getattr(self, 'block%d' % i), getattr(self, 'norm%d' % i)
+        if self.stage_impl != 'hip' or not (x.is_cuda or _lib._override is not None) or x.dtype != torch.float32 or len(blocks) == 0:
+            return False
+        if type(pe.norm) is not nn.LayerNorm or type(norm) is not nn.LayerNorm:
+            return False
+        b0 = blocks[0]
+        for blk in blocks:
+            a, m = blk.attn, blk.mlp
+            if type(blk.norm1) is not nn.LayerNorm or type(blk.norm2) is not nn.LayerNorm or blk.norm1.eps != b0.norm1.eps or blk.norm2.eps != b0.norm1.eps:
+                return False
+            if a.sr_ratio > 1 and (type(a.norm) is not nn.LayerNorm or a.norm.eps != b0.attn.norm.eps):
+                return False
+            if (a.num_heads, a.scale, a.sr_ratio, m.fc1.out_features) != (b0.attn.num_heads, b0.attn.scale, b0.attn.sr_ratio, b0.mlp.fc1.out_features):
+                return False
+            if type(m.act) is not nn.GELU or getattr(m.act, 'approximate', 'none') != 'none':
+                return False
+            if self.training and (a.attn_drop.p or a.proj_drop.p or m.drop.p or getattr(blk.drop_path, 'drop_prob', 0.)):
+                return False
+        norms = [pe.norm, norm] + [n for blk in blocks for n in (blk.norm1, blk.norm2)] + [blk.attn.norm for blk in blocks if blk.attn.sr_ratio > 1]
+        if any(not n.elementwise_affine or n.bias is None for n in norms):
+            return False
+        ts = [t for t in mit_stage_tensors(blocks, pe.norm, norm) if t is not None]
+        if any(t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous() or t.data_ptr() % 16 for t in ts):
+            return False
+        if any(t is None for t in (b0.attn.proj.bias, b0.mlp.fc1.bias, b0.mlp.fc2.bias)):
+            return False
+        conv = pe.proj
+        if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in ts + list(conv.parameters()))):
+            return False
+        hw = [(x.shape[2 + d] + 2 * conv.padding[d] - conv.dilation[d] * (conv.kernel_size[d] - 1) - 1) // conv.stride[d] + 1 for d in (0, 1)]
+        return mit_stage_supported(mit_stage_cfg((x.shape[0], conv.out_channels, hw[0], hw[1]), blocks, pe.norm, norm))
+
+    def _stage_ws(self, i, y):
+        """the stage call's workspace: allocated once per (stage, device, cfg), kept on the module as a plain attribute (no buffer, no
+        state_dict entry); the only state of the 'hip' path"""
+        blocks = getattr(self, 'block%d' % i)
+        cfg = mit_stage_cfg(y.shape, blocks, getattr(self, 'patch_embed%d' % i).norm, getattr(self, 'norm%d' % i))
+        key = (i, y.device) + tuple(getattr(cfg, f) for f, _ in cfg._fields_ if f != 'depth')
+        cache = self.__dict__.setdefault('_stage_workspaces', {})
+        if key not in cache:
+            need = _lib.get().cffm_mit_stage_infer_ws_floats(cfg)
+            if need < 0:
+                raise _lib.CffmError('libcffm_hip: %s' % _lib.get().cffm_last_error().decode())
+            for k in [k for k in cache if k[0] == i and k[1] == y.device]:      # one workspace per stage and device: the last shape's
+                del cache[k]
+            cache[key] = torch.empty(need, dtype=torch.float32, device=y.device)
+        return cache[key]
+
     def forward_features(self, x):
         B = x.shape[0]
         outs = []
         for i in range(1, 5):
+            if self._stage_fused(i, x):
+                pe = getattr(self, 'patch_embed%d' % i)
+                with torch.no_grad():
+                    y = pe.proj(x)
+                    x = mit_stage_infer(y, pe.norm, getattr(self, 'block%d' % i), getattr(self, 'norm%d' % i), ws=self._stage_ws(i, y))
+                outs.append(x)
+                continue
             x, H, W = getattr(self, 'patch_embed%d' % i)(x)
             for blk in getattr(self, 'block%d' % i):
                 x = blk(x, H, W)

@@ -13,6 +13,7 @@
 #include "mixffn_kernels.h"
 #include "sra_kernels.h"
 #include "srln_kernels.h"
+#include "mitln_kernels.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -2863,12 +2864,16 @@ static DwgGeom dwg_plan(int M, int H, int W, int C, int xr, long lanes, int per_
 #define DWG_FWD_LANES (2048L * 256)     // forward and dh: up to 2048 workgroups of 256 lanes
 #define DWG_BWD1_LANES (1024L * 256)    // first backward pass: up to 1024 workgroups, each leaving a 10 KB slab of partial sums
 static bool dwg_aligned(const void* p) { return p && (uintptr_t)p % 16 == 0; }
+// (checked arguments -> the launch: shared with the MiT stage call)
+static void dwg_fwd_launch(const float* h, const float* w, const float* b, float* out, int M, int H, int W, int C, hipStream_t st) {
+    const DwgGeom G = dwg_plan(M, H, W, C, DWG_XR, DWG_FWD_LANES, 1);
+    CFFM_LAUNCH(k_dwg_fwd, ((unsigned)((G.S * G.C4 + 255) / 256)), (256), 0, st, h, w, b, out, G);
+}
 extern "C" {
 int cffm_dwconv_gelu_fwd(const float* h, const float* w, const float* b, float* out, int M, int H, int W, int C, void* stream) {
     TRY(dwg_check("dwconv_gelu_fwd", M, H, W, C));
     REQUIRE(dwg_aligned(h) && dwg_aligned(w) && dwg_aligned(b) && dwg_aligned(out), "dwconv_gelu_fwd: h / w / b / out must be non-null and 16-byte aligned");
-    const DwgGeom G = dwg_plan(M, H, W, C, DWG_XR, DWG_FWD_LANES, 1);
-    CFFM_LAUNCH(k_dwg_fwd, ((unsigned)((G.S * G.C4 + 255) / 256)), (256), 0, (hipStream_t)stream, h, w, b, out, G);
+    dwg_fwd_launch(h, w, b, out, M, H, W, C, (hipStream_t)stream);
     CHECK_LAUNCH("dwconv_gelu_fwd");
     return 0;
 }
@@ -2918,17 +2923,20 @@ static long sra_delta_floats(int B, int N, int heads) { return ((long)B * heads 
 // two query tiles per wave halve the K / V traffic; one when that leaves fewer than two workgroups per compute unit
 static bool sra_wide(int B, int N, int heads) { return (long)B * heads * ((N + 127) / 128) >= 512; }
 static bool sra_aligned(const void* p) { return p && (uintptr_t)p % 16 == 0; }
-extern "C" {
-int cffm_sra_attn_fwd(const float* q, const float* kv, float* out, float* lse, int B, int N, int Nk, int heads, int hd, float scale, void* stream) {
-    TRY(sra_check("sra_attn_fwd", B, N, Nk, heads, hd, scale));
-    REQUIRE(sra_aligned(q) && sra_aligned(kv) && sra_aligned(out) && (uintptr_t)lse % 16 == 0,
-            "sra_attn_fwd: q / kv / out must be non-null and q / kv / out / lse 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
+// (checked arguments -> the launch: shared with the MiT stage call)
+static void sra_fwd_launch(const float* q, const float* kv, float* out, float* lse, int B, int N, int Nk, int heads, int hd, float scale, hipStream_t st) {
     const unsigned gz = (unsigned)(B * heads);
 #define SRA_FWD(HD_, QW_) CFFM_LAUNCH((k_sra_fwd<HD_, QW_>), ((unsigned)((N + 64 * QW_ - 1) / (64 * QW_)), 1, gz), (256), 0, st, q, kv, out, lse, N, Nk, heads, scale)
     if (sra_wide(B, N, heads)) { if (hd == 64) SRA_FWD(64, 2); else SRA_FWD(32, 2); }
     else { if (hd == 64) SRA_FWD(64, 1); else SRA_FWD(32, 1); }
 #undef SRA_FWD
+}
+extern "C" {
+int cffm_sra_attn_fwd(const float* q, const float* kv, float* out, float* lse, int B, int N, int Nk, int heads, int hd, float scale, void* stream) {
+    TRY(sra_check("sra_attn_fwd", B, N, Nk, heads, hd, scale));
+    REQUIRE(sra_aligned(q) && sra_aligned(kv) && sra_aligned(out) && (uintptr_t)lse % 16 == 0,
+            "sra_attn_fwd: q / kv / out must be non-null and q / kv / out / lse 16-byte aligned");
+    sra_fwd_launch(q, kv, out, lse, B, N, Nk, heads, hd, scale, (hipStream_t)stream);
     CHECK_LAUNCH("sra_attn_fwd");
     return 0;
 }
@@ -3001,6 +3009,15 @@ static void srln_launch_bwd(hipStream_t st, const float* x, const float* w, cons
     CFFM_LAUNCH(k_srln_bwd_dx<S>, ((unsigned)((units + 3) / 4)), (256), 0, st, (const float*)dz, w, dx, G, units);
     CFFM_LAUNCH(k_srln_bwd_dw<S>, ((unsigned)(S2 / 4), (unsigned)(C / 16), (unsigned)(C / 16)), (512), 0, st, (const float*)dz, x, dw, G);
 }
+// (checked arguments -> the launch: shared with the MiT stage call)
+static void srln_fwd_launch(int s, hipStream_t st, const float* x, const float* w, const float* b, const float* gamma, const float* beta, float* out,
+                            float* z, float* stats, const SrGeom& G, float eps) {
+    const unsigned grid = (unsigned)srln_row_blocks(G);
+    const int ncw = srln_ncw(G.C);
+    if (s == 2) srln_launch_fwd<2>(ncw, grid, st, x, w, b, gamma, beta, out, z, stats, G, eps);
+    else if (s == 4) srln_launch_fwd<4>(ncw, grid, st, x, w, b, gamma, beta, out, z, stats, G, eps);
+    else srln_launch_fwd<8>(ncw, grid, st, x, w, b, gamma, beta, out, z, stats, G, eps);
+}
 extern "C" {
 int cffm_sr_ln_fwd(const float* x, const float* w, const float* b, const float* gamma, const float* beta, float* out, float* z, float* stats,
                    int B, int H, int W, int C, int s, float eps, void* stream) {
@@ -3010,12 +3027,7 @@ int cffm_sr_ln_fwd(const float* x, const float* w, const float* b, const float* 
             (uintptr_t)z % 16 == 0 && (uintptr_t)stats % 16 == 0,
             "sr_ln_fwd: x / w / b / gamma / beta / out must be non-null and all pointers 16-byte aligned");
     REQUIRE(!z == !stats, "sr_ln_fwd: z and stats must both be given or both be null");
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned grid = (unsigned)srln_row_blocks(G);
-    const int ncw = srln_ncw(C);
-    if (s == 2) srln_launch_fwd<2>(ncw, grid, st, x, w, b, gamma, beta, out, z, stats, G, eps);
-    else if (s == 4) srln_launch_fwd<4>(ncw, grid, st, x, w, b, gamma, beta, out, z, stats, G, eps);
-    else srln_launch_fwd<8>(ncw, grid, st, x, w, b, gamma, beta, out, z, stats, G, eps);
+    srln_fwd_launch(s, (hipStream_t)stream, x, w, b, gamma, beta, out, z, stats, G, eps);
     CHECK_LAUNCH("sr_ln_fwd");
     return 0;
 }
@@ -3039,6 +3051,165 @@ int cffm_sr_ln_bwd(const float* x, const float* w, const float* gamma, const flo
     else if (s == 4) srln_launch_bwd<4>(st, x, w, gamma, z, stats, dout, dx, dw, db, dgamma, dbeta, dz, part, G);
     else srln_launch_bwd<8>(st, x, w, gamma, z, stats, dout, dx, dw, db, dgamma, dbeta, dz, part, G);
     CHECK_LAUNCH("sr_ln_bwd");
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------- LayerNorm of token rows at any width + one MiT stage per call (mitln_kernels.h)
+}  // extern "C"
+static bool mln_aligned(const void* p) { return p && (uintptr_t)p % 16 == 0; }
+static int mln_check(const char* who, int C, float eps) {
+    REQUIRE(C >= 16 && C <= 512 && C % 4 == 0, "%s: C=%d must be a multiple of 4 in 16..512", who, C);
+    REQUIRE(eps >= 0.f && eps < INFINITY, "%s: eps %g must be finite and not negative", who, (double)eps);
+    return 0;
+}
+static int mln_check_map(const char* who, int B, int C, int H, int W, float eps) {
+    TRY(mln_check(who, C, eps));
+    REQUIRE(B >= 1 && H >= 1 && W >= 1, "%s: bad sizes B=%d H=%d W=%d", who, B, H, W);
+    REQUIRE((long)B * C * H * W < (1L << 31), "%s: B*C*H*W = %ld is not below 2^31", who, (long)B * C * H * W);
+    return 0;
+}
+// which: 0 rows -> rows (nimg unused) | 1 NCHW -> rows | 2 rows -> NCHW
+template <int PW, int V>
+static void mln_go(int which, hipStream_t st, const float* x, const float* g, const float* b, float* out, long M, int nimg, const MlnGeom& G, float eps) {
+    if (which == 0) {
+        constexpr int RPB = 4 * (64 / PW);
+        CFFM_LAUNCH((k_ln_rows<PW, V>), ((unsigned)std::min(4096L, (M + RPB - 1) / RPB)), (256), 0, st, x, g, b, out, M, G, eps);
+    } else if (which == 1) {
+        CFFM_LAUNCH((k_nchw_ln_rows<PW, V>), ((unsigned)(nimg * G.tiles)), (256), (size_t)G.TP * G.LD * sizeof(float), st, x, g, b, out, G, eps);
+    } else {
+        CFFM_LAUNCH((k_ln_rows_nchw<PW, V>), ((unsigned)(nimg * G.tiles)), (256), (size_t)G.TP * G.LD * sizeof(float), st, x, g, b, out, G, eps);
+    }
+}
+// (checked arguments -> the launch)
+static void mln_launch(int which, hipStream_t st, const float* x, const float* g, const float* b, float* out, long M, int nimg, int C, int HW, float eps) {
+    const MlnGeom G = mln_geom(C, HW);
+    if (G.C4 > 64) return mln_go<64, 2>(which, st, x, g, b, out, M, nimg, G, eps);
+    switch (mln_pw(C)) {
+        case 4: return mln_go<4, 1>(which, st, x, g, b, out, M, nimg, G, eps);
+        case 8: return mln_go<8, 1>(which, st, x, g, b, out, M, nimg, G, eps);
+        case 16: return mln_go<16, 1>(which, st, x, g, b, out, M, nimg, G, eps);
+        case 32: return mln_go<32, 1>(which, st, x, g, b, out, M, nimg, G, eps);
+        default: return mln_go<64, 1>(which, st, x, g, b, out, M, nimg, G, eps);
+    }
+}
+
+// workspace of one stage call (floats).  The residual stream alternates between xa and xb inside a block (xa -> proj + residual -> xb ->
+// fc2 + residual -> xa), so every block reads and leaves its rows in xa, whatever the depth.  z: the LayerNorm outputs and, once q and kv
+// are made from it, the attention output.  q | r (the reduced map) | kv are dead when fc1 runs: they share their room with h.
+struct MitWs { long xa, xb, z, q, r, kv, h, a, total; long M; int N, Nk; };
+static int mit_cfg_check(const char* who, const cffm_mit_stage_cfg* c, MitWs* Wo) {
+    REQUIRE(c, "%s: null cfg", who);
+    REQUIRE(c->B >= 1 && c->H >= 1 && c->W >= 1 && c->depth >= 1 && c->heads >= 1,
+            "%s: bad sizes B=%d H=%d W=%d depth=%d heads=%d", who, c->B, c->H, c->W, c->depth, c->heads);
+    REQUIRE(c->C >= 16 && c->C <= 512 && c->C % 16 == 0, "%s: C=%d must be a multiple of 16 in 16..512", who, c->C);
+    REQUIRE(c->C % c->heads == 0 && (c->C / c->heads == 32 || c->C / c->heads == 64), "%s: C=%d with %d heads: the head size must be 32 or 64",
+            who, c->C, c->heads);
+    REQUIRE(c->hidden >= 4 && c->hidden % 4 == 0, "%s: hidden=%d must be a multiple of 4, at least 4", who, c->hidden);
+    const int s = c->sr_ratio;
+    REQUIRE(s == 1 || s == 2 || s == 4 || s == 8, "%s: sr_ratio=%d is not 1, 2, 4 or 8", who, s);
+    REQUIRE(c->H >= s && c->W >= s, "%s: H=%d and W=%d must be at least sr_ratio=%d", who, c->H, c->W, s);
+    const float eps[4] = {c->eps_embed, c->eps_block, c->eps_sr, c->eps_out};
+    for (int i = 0; i < 4; ++i) REQUIRE(eps[i] >= 0.f && eps[i] < INFINITY, "%s: eps %g must be finite and not negative", who, (double)eps[i]);
+    MitWs W;
+    W.N = c->H * c->W;
+    W.Nk = s > 1 ? (c->H / s) * (c->W / s) : W.N;
+    const long N = (long)c->H * c->W;
+    W.M = (long)c->B * N;
+    const long widest = std::max(2L * c->C, (long)c->hidden);
+    // (the GEMMs address an operand through a buffer descriptor: 32-bit byte offsets)
+    REQUIRE(N < (1L << 31) && W.M < (1L << 31) && W.M * widest < (1L << 30), "%s: B*H*W*max(2C, hidden) = %ld is not below 2^30", who, W.M * widest);
+    TRY(sra_check(who, c->B, W.N, W.Nk, c->heads, c->C / c->heads, c->scale));
+    TRY(dwg_check(who, c->B, c->H, c->W, c->hidden));
+    if (s > 1) {
+        SrGeom G;
+        TRY(srln_check(who, c->B, c->H, c->W, c->C, s, c->eps_sr, &G));
+    }
+    const long MC = W.M * c->C, KC = (long)c->B * W.Nk * c->C;
+    long p = 0;
+    W.xa = p; p += up(MC);
+    W.xb = p; p += up(MC);
+    W.z = p; p += up(MC);
+    W.h = p; W.q = p;
+    W.r = W.q + up(MC);
+    W.kv = W.r + (s > 1 ? up(KC) : 0);
+    p += std::max(up(W.M * c->hidden), W.kv + up(2 * KC) - W.q);
+    W.a = p; p += up(W.M * c->hidden);
+    W.total = p;
+    if (Wo) *Wo = W;
+    return 0;
+}
+extern "C" {
+int cffm_ln_rows(const float* x, const float* gamma, const float* beta, float* out, long M, int C, float eps, void* stream) {
+    TRY(mln_check("ln_rows", C, eps));
+    REQUIRE(M >= 1 && M * C < (1L << 31), "ln_rows: M=%ld rows of C=%d: M must be at least 1 and M*C below 2^31", M, C);
+    REQUIRE(mln_aligned(x) && mln_aligned(gamma) && mln_aligned(beta) && mln_aligned(out), "ln_rows: x / gamma / beta / out must be non-null and 16-byte aligned");
+    mln_launch(0, (hipStream_t)stream, x, gamma, beta, out, M, 0, C, 1, eps);
+    CHECK_LAUNCH("ln_rows");
+    return 0;
+}
+int cffm_nchw_ln_rows(const float* x_nchw, const float* gamma, const float* beta, float* out_rows, int B, int C, int H, int W, float eps, void* stream) {
+    TRY(mln_check_map("nchw_ln_rows", B, C, H, W, eps));
+    REQUIRE(mln_aligned(x_nchw) && mln_aligned(gamma) && mln_aligned(beta) && mln_aligned(out_rows),
+            "nchw_ln_rows: x_nchw / gamma / beta / out_rows must be non-null and 16-byte aligned");
+    mln_launch(1, (hipStream_t)stream, x_nchw, gamma, beta, out_rows, (long)B * H * W, B, C, H * W, eps);
+    CHECK_LAUNCH("nchw_ln_rows");
+    return 0;
+}
+int cffm_ln_rows_nchw(const float* x_rows, const float* gamma, const float* beta, float* out_nchw, int B, int C, int H, int W, float eps, void* stream) {
+    TRY(mln_check_map("ln_rows_nchw", B, C, H, W, eps));
+    REQUIRE(mln_aligned(x_rows) && mln_aligned(gamma) && mln_aligned(beta) && mln_aligned(out_nchw),
+            "ln_rows_nchw: x_rows / gamma / beta / out_nchw must be non-null and 16-byte aligned");
+    mln_launch(2, (hipStream_t)stream, x_rows, gamma, beta, out_nchw, (long)B * H * W, B, C, H * W, eps);
+    CHECK_LAUNCH("ln_rows_nchw");
+    return 0;
+}
+
+long cffm_mit_stage_infer_ws_floats(const cffm_mit_stage_cfg* c) {
+    MitWs W;
+    return mit_cfg_check("mit_stage_infer_ws_floats", c, &W) ? -1 : W.total;
+}
+int cffm_mit_stage_infer(const cffm_mit_stage_cfg* c, const cffm_mit_block_params* blocks, const float* embed_g, const float* embed_b,
+                         const float* out_g, const float* out_b, const float* conv_nchw, float* out_nchw, float* ws, void* stream) {
+    MitWs W;
+    TRY(mit_cfg_check("mit_stage_infer", c, &W));
+    REQUIRE(blocks, "mit_stage_infer: null block parameters");
+    REQUIRE(mln_aligned(embed_g) && mln_aligned(embed_b) && mln_aligned(out_g) && mln_aligned(out_b) && mln_aligned(conv_nchw) &&
+            mln_aligned(out_nchw) && mln_aligned(ws),
+            "mit_stage_infer: embed_g / embed_b / out_g / out_b / conv_nchw / out_nchw / ws must be non-null and 16-byte aligned");
+    REQUIRE(conv_nchw != out_nchw, "mit_stage_infer: input and output must not alias");
+    const int s = c->sr_ratio;
+    for (int i = 0; i < c->depth; ++i) {
+        const cffm_mit_block_params& p = blocks[i];
+        const float* need[] = {p.n1_g, p.n1_b, p.q_w, p.kv_w, p.proj_w, p.proj_b, p.n2_g, p.n2_b, p.fc1_w, p.fc1_b, p.dw_w, p.dw_b, p.fc2_w, p.fc2_b};
+        for (const float* t : need) REQUIRE(mln_aligned(t), "mit_stage_infer: block %d: a parameter is null or not 16-byte aligned", i);
+        REQUIRE((uintptr_t)p.q_b % 16 == 0 && (uintptr_t)p.kv_b % 16 == 0, "mit_stage_infer: block %d: q_b / kv_b not 16-byte aligned", i);
+        const float* sr[] = {p.sr_w, p.sr_b, p.srn_g, p.srn_b};
+        for (const float* t : sr)
+            REQUIRE(s > 1 ? mln_aligned(t) : !t, "mit_stage_infer: block %d: sr_w / sr_b / srn_g / srn_b must be %s", i,
+                    s > 1 ? "non-null and 16-byte aligned (sr_ratio > 1)" : "null (sr_ratio == 1)");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int B = c->B, H = c->H, Wd = c->W, C = c->C, hid = c->hidden, N = W.N, Nk = W.Nk, M = (int)W.M, Mk = B * Nk;
+    float *xa = ws + W.xa, *xb = ws + W.xb, *z = ws + W.z, *q = ws + W.q, *r = ws + W.r, *kv = ws + W.kv, *h = ws + W.h, *a = ws + W.a;
+    SrGeom SG = {};
+    if (s > 1) TRY(srln_check("mit_stage_infer", B, H, Wd, C, s, c->eps_sr, &SG));
+    mln_launch(1, st, conv_nchw, embed_g, embed_b, xa, W.M, B, C, N, c->eps_embed);
+    for (int i = 0; i < c->depth; ++i) {
+        const cffm_mit_block_params& p = blocks[i];
+        mln_launch(0, st, xa, p.n1_g, p.n1_b, z, W.M, 0, C, 1, c->eps_block);
+        bool bad = gemm_split_launch<false, false>(z, p.q_w, q, M, C, C, C, C, C, 1, st, p.q_b);
+        if (s > 1) srln_fwd_launch(s, st, z, p.sr_w, p.sr_b, p.srn_g, p.srn_b, r, nullptr, nullptr, SG, c->eps_sr);
+        bad = bad || gemm_split_launch<false, false>(s > 1 ? r : z, p.kv_w, kv, Mk, 2 * C, C, C, C, 2 * C, 1, st, p.kv_b);
+        sra_fwd_launch(q, kv, z, nullptr, B, N, Nk, c->heads, C / c->heads, c->scale, st);
+        bad = bad || gemm_split_launch<false, false, 2>(z, p.proj_w, xb, M, C, C, C, C, C, 1, st, p.proj_b, xa);
+        mln_launch(0, st, xb, p.n2_g, p.n2_b, z, W.M, 0, C, 1, c->eps_block);
+        bad = bad || gemm_split_launch<false, false>(z, p.fc1_w, h, M, hid, C, C, C, hid, 1, st, p.fc1_b);
+        dwg_fwd_launch(h, p.dw_w, p.dw_b, a, B, H, Wd, hid, st);
+        bad = bad || gemm_split_launch<false, false, 2>(a, p.fc2_w, xa, M, C, hid, hid, hid, C, 1, st, p.fc2_b, xb);
+        REQUIRE(!bad, "mit_stage_infer: gemm failed");
+    }
+    mln_launch(2, st, xa, out_g, out_b, out_nchw, W.M, B, C, N, c->eps_out);
+    CHECK_LAUNCH("mit_stage_infer");
     return 0;
 }
 

@@ -1518,3 +1518,162 @@ def sr_reduce(x, weight, bias, ln_weight, ln_bias, H, W, sr_ratio, eps=1e-5):
     if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
         return _SrReduceFn.apply(x, weight, bias, ln_weight, ln_bias, H, W, s, eps)
     return _sr_forward(_lib.get(), *(_sra_operand(t.detach()) for t in ts), H, W, s, eps, False)[0]
+
+
+# ---------------------------------------------------------------------------------------------- LayerNorm of token rows + one MiT stage per call (inference)
+# The limits of cffm_ln_rows / cffm_nchw_ln_rows / cffm_ln_rows_nchw and of cffm_mit_stage_infer: copies of mln_check and mit_cfg_check
+# in csrc/cffm_hip.hip (stated in include/cffm_hip.h); change both together.  tests/test_mit_stage.py walks them through both copies.
+LN_MIN_C, LN_MAX_C = 16, 512
+
+
+def _infer_only(ts, what):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise _lib.CffmError('%s is inference only: call it under torch.no_grad() or with tensors that do not require grad' % what)
+
+
+def _ln_operands(what, x, weight, bias, c):
+    for t, name in ((x, 'x'), (weight, 'weight'), (bias, 'bias')):
+        if not isinstance(t, torch.Tensor):
+            raise _lib.CffmError('%s: %s must be a tensor' % (what, name))
+        _require_device(t, '%s %s' % (what, name))
+    if tuple(weight.shape) != (c,) or tuple(bias.shape) != (c,) or weight.device != x.device or bias.device != x.device:
+        raise _lib.CffmError('%s: weight and bias must be [%d] tensors on %s' % (what, c, x.device))
+    if c % 4 or not LN_MIN_C <= c <= LN_MAX_C:
+        raise _lib.CffmError('%s: C=%d must be a multiple of 4 in %d..%d' % (what, c, LN_MIN_C, LN_MAX_C))
+    _infer_only((x, weight, bias), what)
+    return tuple(_sra_operand(t.detach()) for t in (x, weight, bias))
+
+
+def _ln_out(what, out, shape, x):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=x.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != tuple(shape) or out.device != x.device or not out.is_contiguous():
+        raise _lib.CffmError('%s: out must be a contiguous fp32 %s tensor on %s' % (what, tuple(shape), x.device))
+    return out
+
+
+def ln_rows(x, weight, bias, eps=1e-5, out=None):
+    """F.layer_norm(x, (C,), weight, bias, eps) of fp32 token rows x [..., C], C a multiple of 4 in 16..512, in one pass with the row in
+    registers (``cffm_ln_rows``).  Inference only: it raises when an input requires grad while grad mode is on."""
+    if not isinstance(x, torch.Tensor) or x.dim() < 1:
+        raise _lib.CffmError('ln_rows: x must be a [..., C] tensor')
+    c = x.shape[-1]
+    xs, w, b = _ln_operands('ln_rows', x, weight, bias, c)
+    if xs.numel() == 0:
+        raise _lib.CffmError('ln_rows: x is empty')
+    out = _ln_out('ln_rows', out, x.shape, xs)
+    lib = _lib.get()
+    _lib.check(lib.cffm_ln_rows(_ptr(xs), _ptr(w), _ptr(b), _ptr(out), xs.numel() // c, c, float(eps), _stream(xs)), lib)
+    return out
+
+
+def nchw_ln_rows(x, weight, bias, eps=1e-5, out=None):
+    """F.layer_norm(x.flatten(2).transpose(1, 2), (C,), weight, bias, eps) of an fp32 map x [B,C,H,W] -> token rows [B, H*W, C], without the
+    transposed copy (``cffm_nchw_ln_rows``).  Inference only."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise _lib.CffmError('nchw_ln_rows: x must be a [B,C,H,W] tensor')
+    b_, c, h, w_ = x.shape
+    xs, w, b = _ln_operands('nchw_ln_rows', x, weight, bias, c)
+    out = _ln_out('nchw_ln_rows', out, (b_, h * w_, c), xs)
+    lib = _lib.get()
+    _lib.check(lib.cffm_nchw_ln_rows(_ptr(xs), _ptr(w), _ptr(b), _ptr(out), b_, c, h, w_, float(eps), _stream(xs)), lib)
+    return out
+
+
+def ln_rows_nchw(x, weight, bias, H, W, eps=1e-5, out=None):
+    """F.layer_norm(x, (C,), weight, bias, eps).reshape(B, H, W, C).permute(0, 3, 1, 2).contiguous() of fp32 token rows x [B, H*W, C] -> the
+    map [B,C,H,W] (``cffm_ln_rows_nchw``).  Inference only."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != int(H) * int(W):
+        raise _lib.CffmError('ln_rows_nchw: x must be a [B, H*W, C] tensor')
+    b_, _, c = x.shape
+    xs, w, b = _ln_operands('ln_rows_nchw', x, weight, bias, c)
+    out = _ln_out('ln_rows_nchw', out, (b_, c, int(H), int(W)), xs)
+    lib = _lib.get()
+    _lib.check(lib.cffm_ln_rows_nchw(_ptr(xs), _ptr(w), _ptr(b), _ptr(out), b_, c, int(H), int(W), float(eps), _stream(xs)), lib)
+    return out
+
+
+MIT_HEAD_SIZES = (32, 64)
+MIT_SR_RATIOS = (1, 2, 4, 8)
+
+
+def mit_stage_cfg(shape, blocks, embed_norm, out_norm):
+    """cffm_mit_stage_cfg of a stage: `shape` = (B, C, H, W) of the patch-embedding convolution's output, `blocks` the stage's Block
+    modules (all of one configuration), the two LayerNorms around them"""
+    b, c, h, w = (int(v) for v in shape)
+    a, m = blocks[0].attn, blocks[0].mlp
+    return _lib.MitStageCfg(B=b, H=h, W=w, C=c, heads=int(a.num_heads), hidden=int(m.fc1.out_features), sr_ratio=int(a.sr_ratio),
+                            depth=len(blocks), scale=float(a.scale), eps_embed=float(embed_norm.eps), eps_block=float(blocks[0].norm1.eps),
+                            eps_sr=float(a.norm.eps) if a.sr_ratio > 1 else 0.0, eps_out=float(out_norm.eps))
+
+
+def mit_stage_supported(cfg):
+    """whether this stage is inside the limits of cffm_mit_stage_infer"""
+    c, heads, s = cfg.C, cfg.heads, cfg.sr_ratio
+    m = cfg.B * cfg.H * cfg.W
+    eps = (cfg.eps_embed, cfg.eps_block, cfg.eps_sr, cfg.eps_out)
+    return (cfg.B >= 1 and cfg.H >= 1 and cfg.W >= 1 and cfg.depth >= 1 and heads >= 1 and c % 16 == 0 and LN_MIN_C <= c <= LN_MAX_C
+            and c % heads == 0 and c // heads in MIT_HEAD_SIZES and cfg.hidden >= 4 and cfg.hidden % 4 == 0 and s in MIT_SR_RATIOS
+            and cfg.H >= s and cfg.W >= s and cfg.B * heads <= 65535 and m * max(2 * c, cfg.hidden) < 2 ** 30
+            and 0 < cfg.scale < float('inf') and all(0 <= e < float('inf') for e in eps))
+
+
+def mit_stage_tensors(blocks, embed_norm, out_norm):
+    """the parameters cffm_mit_stage_infer reads, in the order of cffm_mit_block_params per block, then embed gamma / beta, out gamma /
+    beta (None where the module has none: q / kv without bias, no `sr` at sr_ratio 1)"""
+    ts = []
+    for blk in blocks:
+        a, m = blk.attn, blk.mlp
+        sr = (a.sr.weight, a.sr.bias, a.norm.weight, a.norm.bias) if a.sr_ratio > 1 else (None,) * 4
+        ts += [blk.norm1.weight, blk.norm1.bias, a.q.weight, a.q.bias, a.kv.weight, a.kv.bias, *sr, a.proj.weight, a.proj.bias,
+               blk.norm2.weight, blk.norm2.bias, m.fc1.weight, m.fc1.bias, m.dwconv.dwconv.weight, m.dwconv.dwconv.bias, m.fc2.weight, m.fc2.bias]
+    return ts + [embed_norm.weight, embed_norm.bias, out_norm.weight, out_norm.bias]
+
+
+_MIT_FIELDS = [f for f, _ in _lib.MitBlockPtrs._fields_]
+_MIT_OPTIONAL = {'q_b', 'kv_b', 'sr_w', 'sr_b', 'srn_g', 'srn_b'}
+
+
+def mit_stage_infer(conv_out, embed_norm, blocks, out_norm, ws=None, out=None):
+    """One MiT stage in eval mode behind its patch embedding's convolution, as one library call (``cffm_mit_stage_infer``): conv_out
+    [B,C,H,W] fp32 (``patch_embed.proj``'s output), `embed_norm` = ``patch_embed.norm``, `blocks` = the stage's Block modules, `out_norm` =
+    the stage's final LayerNorm -> the stage's NCHW map [B,C,H,W].  The parameters are read where they lie (fp32, contiguous, 16-byte
+    aligned; nothing is copied or cached).  ``ws`` / ``out``: optional caller-owned workspace (``cffm_mit_stage_infer_ws_floats`` floats)
+    and result, e.g. the static buffers of a captured graph.  Inference only: drop-path, dropout and autograd are not part of it, and it
+    raises when an input or a parameter requires grad while grad mode is on.  Launches on the current stream."""
+    lib = _lib.get()
+    if not isinstance(conv_out, torch.Tensor) or conv_out.dim() != 4:
+        raise _lib.CffmError('mit_stage_infer: conv_out must be a [B,C,H,W] tensor')
+    _require_device(conv_out, 'mit_stage_infer conv_out')
+    blocks = list(blocks)
+    if not blocks:
+        raise _lib.CffmError('mit_stage_infer: a stage needs at least one block')
+    dev = conv_out.device
+    tensors = mit_stage_tensors(blocks, embed_norm, out_norm)
+    _infer_only([conv_out] + tensors, 'mit_stage_infer')
+    n = len(_MIT_FIELDS)
+    for i, t in enumerate(tensors):
+        name = _MIT_FIELDS[i % n] if i < n * len(blocks) else 'stage norm'
+        if t is None:
+            if name not in _MIT_OPTIONAL:
+                raise _lib.CffmError('mit_stage_infer: parameter %s is missing' % name)
+            continue
+        _require_device(t, 'mit_stage_infer parameter')
+        if t.device != dev or not t.is_contiguous():
+            raise _lib.CffmError('mit_stage_infer: parameter %s must be contiguous and on %s' % (name, dev))
+    cfg = mit_stage_cfg(conv_out.shape, blocks, embed_norm, out_norm)
+    need = lib.cffm_mit_stage_infer_ws_floats(C.byref(cfg))
+    if need < 0:
+        raise _lib.CffmError('libcffm_hip: %s' % lib.cffm_last_error().decode())
+    x = _sra_operand(conv_out.detach())
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.float32, device=dev)
+    elif ws.dtype != torch.float32 or ws.numel() < need or ws.device != dev or not ws.is_contiguous():
+        raise _lib.CffmError('mit_stage_infer workspace: %d contiguous fp32 values on %s expected' % (need, dev))
+    out = _ln_out('mit_stage_infer', out, x.shape, x)
+    structs = (_lib.MitBlockPtrs * len(blocks))()
+    for i in range(len(blocks)):
+        for f, t in zip(_MIT_FIELDS, tensors[i * n:(i + 1) * n]):
+            setattr(structs[i], f, t.data_ptr() if t is not None else None)
+    _lib.check(lib.cffm_mit_stage_infer(C.byref(cfg), structs, *(_ptr(t) for t in tensors[-4:]), _ptr(x), _ptr(out), _ptr(ws), _stream(x)), lib)
+    return out
