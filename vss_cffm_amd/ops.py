@@ -7,6 +7,7 @@ which this package never imports).
 """
 import contextlib
 import ctypes as C
+import weakref
 
 import numpy as np
 import torch
@@ -47,24 +48,19 @@ def _stream(t):
     return C.c_void_p(0)
 
 
-def _branch(lib, st, i):
-    """library stream i (0..3) ordered behind everything issued on `st` so far (cffm_branch_begin); everything a branch touches must stay
-    referenced until _join(lib, st)"""
-    return C.c_void_p(lib.cffm_branch_begin(st, i))
-
-
-def _mark(lib, st):
-    """remember this point of `st` for _take: the caller launches its own (longest) chain first, the branches afterwards (under stream
-    capture the first-launched dependant of a node keeps the node's hardware queue)"""
+@contextlib.contextmanager
+def _branches(lib, st):
+    """`with _branches(lib, st) as take:` -- stage calls side by side: entry marks this point of `st` (cffm_branch_mark), take(i) is library
+    stream i (0..3) ordered behind the mark, the exit -- also when a stage call raises -- makes `st` continue behind every branch
+    (cffm_branch_join).  The caller launches its own (longest) chain on `st` first and takes the branches afterwards: under stream capture the
+    first-launched dependant of a node keeps the node's hardware queue.  A branch waits for the MARK only and the caching allocator knows nothing
+    of these streams, so a region is prepare -> scope -> finish: whatever torch enqueues on `st` or allocates (.contiguous(), _to_rows, empty /
+    zeros, zero_()) comes BEFORE the scope, inside are library calls only, and every tensor they touch stays referenced until it closes."""
     lib.cffm_branch_mark(st)
-
-
-def _take(lib, st, i):
-    return C.c_void_p(lib.cffm_branch_take(st, i))
-
-
-def _join(lib, st):
-    lib.cffm_branch_join(st)
+    try:
+        yield lambda i: C.c_void_p(lib.cffm_branch_take(st, i))
+    finally:
+        lib.cffm_branch_join(st)
 
 
 class _WGrad(C.Structure):
@@ -91,22 +87,15 @@ def _require_int64(t, what):
 _geom_cache = {}
 
 
-@contextlib.contextmanager
-def _padded_grad_slices(lib):
-    """The gradients handed to the library inside this block are 16-byte-aligned slices of ONE flat buffer: the library zeroes the
-    padding behind the odd-sized ones itself (include/cffm_hip.h cffm_grad_slices_padded).  Switched on only around these calls: a
-    caller of the C ABI with gradient tensors of their own (tests/test_emu_kernels.py block API) must not have 3 floats written
-    behind them."""
+def _checked_padded(lib, fn, *args):
+    """A layer backward whose gradients are 16-byte-aligned slices of ONE flat buffer (_flat_grads): the library zeroes the padding behind
+    the odd-sized ones itself (include/cffm_hip.h cffm_grad_slices_padded).  Switched on only around this call: a caller of the C ABI with
+    gradient tensors of their own (tests/test_emu_kernels.py block API) must not have 3 floats written behind them."""
     lib.cffm_grad_slices_padded(1)
     try:
-        yield
+        _lib.check(fn(*args), lib)
     finally:
         lib.cffm_grad_slices_padded(0)
-
-
-def _checked_padded(lib, fn, *args):
-    with _padded_grad_slices(lib):
-        _lib.check(fn(*args), lib)
 
 
 def make_geom(lib, b, h0, w0):
@@ -172,6 +161,41 @@ block_grad_hook = None
 current_backward_params = None
 
 
+def _check_stack(x):                # the layer's NCHW input: a clip stack [B,4,256,H,W]
+    _require_device(x, 'cffm layer input')
+    if x.dim() != 5 or x.shape[2] != 256:
+        raise _lib.CffmError('expected x [B,T,256,H,W], got %s' % (tuple(x.shape),))
+    if x.shape[1] != 4:
+        raise IndexError('CFFM block needs T == 4 frames (3 reference + target), got T=%d' % x.shape[1])
+
+
+def _check_rows(x_rows, h0, w0):    # the layer's input on token rows: [B,4,H*W,256]
+    _require_device(x_rows, 'cffm layer input')
+    if x_rows.dim() != 4 or x_rows.shape[1] != 4 or x_rows.shape[2] != h0 * w0 or x_rows.shape[3] != 256:
+        raise _lib.CffmError('expected x_rows [B,4,%d,256], got %s' % (h0 * w0, tuple(x_rows.shape)))
+
+
+def _layer_geom(lib, b, h0, w0, dev):       # -> geometry, (key_src, q_dst, inv_ptr, inv_idx) of a layer call
+    return make_geom(lib, b, h0, w0), device_tables(h0, w0, dev)
+
+
+def _layer_buffers(lib, g, depth, dev):     # -> `saved`, `scratch` of a forward that a backward follows
+    return (torch.empty(lib.cffm_layer_saved_floats(C.byref(g), depth), dtype=torch.float32, device=dev),
+            torch.empty(lib.cffm_layer_scratch_floats(C.byref(g)), dtype=torch.float32, device=dev))
+
+
+def _flat_grads(params, dev, zero=False):
+    """One allocation for every parameter gradient -> (flat, views of it shaped like `params`, floats per block): 16-byte aligned slices, block
+    i's are flat[i * per_block:(i + 1) * per_block].  The <= 12-byte padding gaps between slices travel through the gradient all-reduce with
+    them and must not carry NaN / Inf bit patterns of recycled memory: the library zeroes them inside the backward of the pooling Linears -- the
+    only tensors with a gap behind them -- see cffm_grad_slices_padded in include/cffm_hip.h (a zero-fill of the whole 6.8 MB buffer was a 7 us
+    kernel in front of the backward, an index_fill_ of the gaps a 4.7 us one).  `zero`: for slices read before their block's backward (LayerPieces)."""
+    sizes = [(p.numel() + 3) // 4 * 4 for p in params]
+    flat = (torch.zeros if zero else torch.empty)(sum(sizes), dtype=torch.float32, device=dev)
+    grads = [c[:p.numel()].view(p.shape) if c.numel() != p.numel() else c.view(p.shape) for c, p in zip(flat.split(sizes), params)]
+    return flat, grads, sum(sizes[:NPB])
+
+
 class LayerPieces:
     """The layer's forward and backward as explicit pieces over STATIC buffers, without autograd: what a data-parallel training
     loop replays from HIP graphs when it wants the gradient exchange of block i to overlap the backward of block i - 1 --
@@ -186,19 +210,14 @@ class LayerPieces:
             raise _lib.CffmError('expected x [B,4,256,H,W], got %s' % (tuple(x.shape),))
         self.lib, self.x, self.depth, self.params = lib, x.contiguous(), depth, list(params)
         b, _, _, h0, w0 = x.shape
-        self.g = make_geom(lib, b, h0, w0)
-        self.tables = device_tables(h0, w0, x.device)
         dev = x.device
-        self.saved = torch.empty(lib.cffm_layer_saved_floats(C.byref(self.g), depth), dtype=torch.float32, device=dev)
-        self.scratch = torch.empty(lib.cffm_layer_scratch_floats(C.byref(self.g)), dtype=torch.float32, device=dev)
+        self.g, self.tables = _layer_geom(lib, b, h0, w0, dev)
+        self.saved, self.scratch = _layer_buffers(lib, self.g, depth, dev)
         self.y = torch.empty(b, 256, h0, w0, dtype=torch.float32, device=dev)
         self.dx = torch.empty(b, 4, 256, h0, w0, dtype=torch.float32, device=dev)
-        self.sizes = [(p.numel() + 3) // 4 * 4 for p in self.params]
-        self.flat = torch.zeros(sum(self.sizes), dtype=torch.float32, device=dev)
-        self.grads = [c[:p.numel()].view(p.shape) for c, p in zip(self.flat.split(self.sizes), self.params)]
+        self.flat, self.grads, self.per_block = _flat_grads(self.params, dev, zero=True)
         self.pstructs = block_structs(self.params, depth)
         self.gstructs = block_structs(self.grads, depth)
-        self.per_block = sum(self.sizes[:NPB])
 
     def block_slice(self, i):
         return self.flat[i * self.per_block:(i + 1) * self.per_block]
@@ -233,21 +252,15 @@ class _LayerFullFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, depth, *params):
         lib = _lib.get()
-        _require_device(x, 'cffm layer input')
-        if x.dim() != 5 or x.shape[2] != 256:
-            raise _lib.CffmError('expected x [B,T,256,H,W], got %s' % (tuple(x.shape),))
-        if x.shape[1] != 4:
-            raise IndexError('CFFM block needs T == 4 frames (3 reference + target), got T=%d' % x.shape[1])
+        _check_stack(x)
         assert len(params) == NPB * depth
         b, _, _, h0, w0 = x.shape
         x = x.contiguous()
         for p in params:
             if not p.is_contiguous() or p.dtype != torch.float32:
                 raise _lib.CffmError('cffm layer parameters must be contiguous float32')
-        g = make_geom(lib, b, h0, w0)
-        key_src, q_dst, inv_ptr, inv_idx = device_tables(h0, w0, x.device)
-        saved = torch.empty(lib.cffm_layer_saved_floats(C.byref(g), depth), dtype=torch.float32, device=x.device)
-        scratch = torch.empty(lib.cffm_layer_scratch_floats(C.byref(g)), dtype=torch.float32, device=x.device)
+        g, (key_src, q_dst, inv_ptr, inv_idx) = _layer_geom(lib, b, h0, w0, x.device)
+        saved, scratch = _layer_buffers(lib, g, depth, x.device)
         y = torch.empty(b, 4, 256, h0, w0, dtype=torch.float32, device=x.device)
         _lib.check(lib.cffm_layer_forward_full(C.byref(g), depth, block_structs(params, depth), _ptr(x), _ptr(y), _ptr(key_src), _ptr(q_dst),
                                                _ptr(saved), _ptr(scratch), _stream(x)), lib)
@@ -264,19 +277,10 @@ class _LayerFullFn(torch.autograd.Function):
         b, h0, w0 = ctx.geom_args
         g = make_geom(lib, b, h0, w0)
         dy = dy.contiguous()
-        # one allocation for every parameter gradient (16-byte aligned slices), returned as views
-        sizes = [(p.numel() + 3) // 4 * 4 for p in params]
-        # (the <= 12-byte padding gaps between slices travel through the gradient all-reduce with them and must not carry NaN / Inf
-        # bit patterns of recycled memory: the library zeroes them inside the backward of the pooling Linears -- the only tensors
-        # with a gap behind them -- see cffm_grad_slices_padded in include/cffm_hip.h; a zero-fill of the whole 6.8 MB buffer was a
-        # 7 us kernel on the chain in front of the backward, an index_fill_ of the gaps still a 4.7 us one)
-        flat = torch.empty(sum(sizes), dtype=torch.float32, device=dy.device)
-        grads = [c[:p.numel()].view(p.shape) if c.numel() != p.numel() else c.view(p.shape)
-                 for c, p in zip(flat.split(sizes), params)]
+        flat, grads, per = _flat_grads(params, dy.device)              # torch.empty: the library zeroes the alignment gaps
         dx = torch.empty(b, 4, 256, h0, w0, dtype=torch.float32, device=dy.device)
         pstructs, gstructs = block_structs(params, depth), block_structs(grads, depth)
         hook = block_grad_hook
-        per = sum(sizes[:NPB])
         global current_backward_params
         current_backward_params = params
         try:
@@ -326,32 +330,29 @@ class _SegFuseFn(torch.autograd.Function):
             _require_device(c, 'segformer_fuse operand')
         n, _, H, W = feats[0].shape
         st, dev = _stream(feats[0]), feats[0].device
-        toks, zs, keep = [], [], []
         for c, a in zip(feats, mats):
             if c.dim() != 4 or c.shape[0] != n or a.shape != (256, c.shape[1]):
                 raise _lib.CffmError('segformer_fuse: feature %s does not fit matrix %s' % (tuple(c.shape), tuple(a.shape)))
-        # every scale is an independent chain NCHW -> token rows -> Linear: the 1/4-scale one (three quarters of the bytes) on the caller's
-        # stream, the others on branches beside it (one stream: 107 us of a replayed head step for 64 us of the largest chain)
-        _mark(lib, st)
-        for i in range(k):
-            c, a = feats[i].contiguous(), mats[i]
-            ci, p = c.shape[1], c.shape[2] * c.shape[3]
-            t = torch.empty(n * p, ci, dtype=torch.float32, device=dev)        # token rows [N*h*w, C_i]
-            z = torch.empty(n * p, 256, dtype=torch.float32, device=dev)
-            if n * p:
-                s = _take(lib, st, i) if i else st
-                _lib.check(lib.cffm_transpose(_ptr(c), _ptr(t), n, ci, p, ci * p, ci * p, s), lib)
-                _lib.check(lib.cffm_linear_fwd(_ptr(t), _ptr(a), _ptr(z), n * p, 256, ci, s), lib)
-            toks.append(t)
-            zs.append(z)
-            keep.append(c)
-        _join(lib, st)
+        # prepare: plain-NCHW copies of strided features (on the caller's stream: in front of the mark), token rows [N*h*w, C_i], products
+        cs, d = [c.contiguous() for c in feats], d.contiguous()
+        pix = [c.shape[2] * c.shape[3] for c in cs]
+        toks = [torch.empty(n * p, c.shape[1], dtype=torch.float32, device=dev) for c, p in zip(cs, pix)]
+        zs = [torch.empty(n * p, 256, dtype=torch.float32, device=dev) for p in pix]
         hs = (C.c_int * 3)(*([c.shape[2] for c in feats[1:]] + [1] * (4 - k)))
         ws = (C.c_int * 3)(*([c.shape[3] for c in feats[1:]] + [1] * (4 - k)))
         zp = (C.c_void_p * 3)(*([z.data_ptr() for z in zs[1:]] + [None] * (4 - k)))
+        # every scale is an independent chain NCHW -> token rows -> Linear: the 1/4-scale one (three quarters of the bytes) on the caller's
+        # stream, the others on branches beside it (one stream: 107 us of a replayed head step for 64 us of the largest chain)
+        with _branches(lib, st) as take:
+            for i, (c, a, t, z, p) in enumerate(zip(cs, mats, toks, zs, pix)):
+                if n * p:
+                    ci = c.shape[1]
+                    s = take(i) if i else st
+                    _lib.check(lib.cffm_transpose(_ptr(c), _ptr(t), n, ci, p, ci * p, ci * p, s), lib)
+                    _lib.check(lib.cffm_linear_fwd(_ptr(t), _ptr(a), _ptr(z), n * p, 256, ci, s), lib)
         y = zs[0]                                                             # updated in place: nothing else needs it
         if n * H * W:
-            _lib.check(lib.cffm_segfuse_fwd(_ptr(y), _ptr(d.contiguous()), zp, hs, ws, k - 1, n, H, W, st), lib)
+            _lib.check(lib.cffm_segfuse_fwd(_ptr(y), _ptr(d), zp, hs, ws, k - 1, n, H, W, st), lib)
         ctx.save_for_backward(*toks, *mats)
         ctx.shapes = [tuple(c.shape) for c in feats]
         # channels-last memory: torch's BatchNorm runs faster on it than on plain NCHW (head step 4.6 vs 5.8 ms)
@@ -378,46 +379,44 @@ class _SegFuseFn(torch.autograd.Function):
         # Behind the adjoint of the resizes everything is independent: branch 1 = the k weight gradients as ONE grouped launch and the
         # column sum of g (both use the library's scratch: one after the other on one branch); the input gradients (Linear + back to NCHW)
         # of the 1/4-scale map on the caller's stream, of the small maps on branches 2 / 3.  (One stream: 213 + 34 us of a replayed step.)
+        # prepare: every result and temporary, zero-filled where no stage call will write it, and the weight-gradient groups
+        pix = [s_[2] * s_[3] for s_ in shapes]
         dmats = [new(256, s_[1]) for s_ in shapes]
-        live = [i for i, s_ in enumerate(shapes) if n * s_[2] * s_[3]]
+        live = [i for i in range(k) if n * pix[i]]
         for i in range(k):
             if i not in live:
                 dmats[i].zero_()
-        _mark(lib, st)
-        dfeats, keep = [None] * k, []
+        if not rows:
+            dd.zero_()
+        dts = [new(n * p, s_[1]) if ctx.needs_input_grad[1 + i] else None for i, (s_, p) in enumerate(zip(shapes, pix))]
+        dfeats = [new(*s_) if ctx.needs_input_grad[1 + i] else None for i, s_ in enumerate(shapes)]
+        # the weight gradients as the arguments of two grouped calls: the 1/4-scale map's | the other scales'
+        groups = [[_WGrad(dzs[i].data_ptr(), toks[i].data_ptr(), dmats[i].data_ptr(), n * pix[i], 256, shapes[i][1]) for i in sel if i in live] for sel in ([0], range(1, k))]
+        groups = [(_WGrad * len(q))(*q) for q in groups]
+
+        def wgrads(pr, sx):
+            if len(pr):
+                _lib.check(lib.cffm_linear_bwd_weight_group(pr, len(pr), sx), lib)
 
         def dx_chain(i, sx):
-            s_, a, dz = shapes[i], mats[i], dzs[i]
-            ci, p = s_[1], s_[2] * s_[3]
-            if ctx.needs_input_grad[1 + i]:
-                dt, dc = new(n * p, ci), new(*s_)
-                if n * p:
-                    _lib.check(lib.cffm_linear_bwd_input(_ptr(dz), _ptr(a), _ptr(dt), n * p, 256, ci, sx), lib)
-                    _lib.check(lib.cffm_transpose(_ptr(dt), _ptr(dc), n, p, ci, ci * p, ci * p, sx), lib)
-                dfeats[i] = dc
-                keep.append(dt)
-        dx_chain(0, st)                                            # the 1/4-scale chain first: it keeps the caller's stream (and its queue)
-        if rows:
-            # branch 1: the 1/4-scale weight gradient (three quarters of the rows); branch 2: the other scales' (one grouped call: the
-            # library groups what its grouped kernel takes and runs the rest one by one) and the column sum of g; branch 3: the small
-            # scales' input gradients.  (Weight gradients and column sums take their scratch from the branch's own pool.)
-            def wgrads(sel, sx):
-                sel = [i for i in sel if i in live]
-                if sel:
-                    pr = (_WGrad * len(sel))(*[_WGrad(dzs[i].data_ptr(), toks[i].data_ptr(), dmats[i].data_ptr(), n * shapes[i][2] * shapes[i][3], 256,
-                                                      shapes[i][1]) for i in sel])
-                    _lib.check(lib.cffm_linear_bwd_weight_group(pr, len(sel), sx), lib)
-            wgrads([0], _take(lib, st, 1))
-            s2 = _take(lib, st, 2)
-            _lib.check(lib.cffm_colsum(_ptr(g), rows, 256, _ptr(dd), s2), lib)
-            wgrads(range(1, k), s2)
-        else:
-            dd.zero_()
-        if k > 1:
-            s3 = _take(lib, st, 3)
-            for i in range(1, k):
-                dx_chain(i, s3)
-        _join(lib, st)
+            ci, p = shapes[i][1], pix[i]
+            if dts[i] is not None and n * p:
+                _lib.check(lib.cffm_linear_bwd_input(_ptr(dzs[i]), _ptr(mats[i]), _ptr(dts[i]), n * p, 256, ci, sx), lib)
+                _lib.check(lib.cffm_transpose(_ptr(dts[i]), _ptr(dfeats[i]), n, p, ci, ci * p, ci * p, sx), lib)
+        with _branches(lib, st) as take:
+            dx_chain(0, st)                                        # the 1/4-scale chain first: it keeps the caller's stream (and its queue)
+            if rows:
+                # branch 1: the 1/4-scale weight gradient (three quarters of the rows); branch 2: the other scales' (one grouped call: the
+                # library groups what its grouped kernel takes and runs the rest one by one) and the column sum of g; branch 3: the small
+                # scales' input gradients.  (Weight gradients and column sums take their scratch from the branch's own pool.)
+                wgrads(groups[0], take(1))
+                s2 = take(2)
+                _lib.check(lib.cffm_colsum(_ptr(g), rows, 256, _ptr(dd), s2), lib)
+                wgrads(groups[1], s2)
+            if k > 1:
+                s3 = take(3)
+                for i in range(1, k):
+                    dx_chain(i, s3)
         return (dd,) + tuple(dfeats) + tuple(dmats)
 
 
@@ -525,7 +524,6 @@ class _Conv1x1Fn(torch.autograd.Function):
             for i in range(clips):
                 if per:
                     _lib.check(lib.cffm_linear_bias_fwd(C.c_void_p(rows.data_ptr() + 4 * i * per * c), _ptr(wm), _ptr(b), _ptr(buf[i]), per, o, c, _stream(x)), lib)
-            ctx.room = buf
             return buf[:, :t].permute(0, 1, 4, 2, 3)
         y = torch.empty(n, h, w, o, dtype=torch.float32, device=x.device)
         _lib.check(lib.cffm_linear_bias_fwd(_ptr(rows), _ptr(wm), _ptr(b), _ptr(y), n * h * w, o, c, _stream(x)), lib)
@@ -555,33 +553,30 @@ class _Conv1x1Fn(torch.autograd.Function):
             blocks = [(_to_rows(lib, dy.reshape(n, o, h, w) if dy.dim() == 5 else dy), 0, m)]
         dx = dwm = db = None
         live = [(blk, r0, nr) for blk, r0, nr in blocks if nr]
-        # weight + bias gradient on a branch (ONE grouped launch over the blocks, then their column sums: both use the library's scratch, so
-        # one after the other), the input gradient beside them on the caller's stream
-        wparts, bparts = [], []
-        _mark(lib, st)
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty(n, h, w, c, dtype=torch.float32, device=dy.device)
-            for blk, r0, nr in live:
-                _lib.check(lib.cffm_linear_bwd_input(_ptr(blk), _ptr(wm), C.c_void_p(dx.data_ptr() + 4 * r0 * c), nr, o, c, st), lib)
-            if ctx.x_plain and m:
-                dxp = torch.empty(n, c, h, w, dtype=torch.float32, device=dy.device)
-                _lib.check(lib.cffm_transpose(_ptr(dx), _ptr(dxp), n, h * w, c, c * h * w, c * h * w, st), lib)
-                dx = dxp
-            else:
-                dx = dx.permute(0, 3, 1, 2)
-        if (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) and live:
-            # weight gradient of block j on branch 1 + j % 2, the column sums on branch 3 (each with the scratch pool of its branch)
-            if ctx.needs_input_grad[1]:
-                wparts = [torch.empty(o, c, dtype=torch.float32, device=dy.device) for _ in live]
-                sw = [_take(lib, st, 1), _take(lib, st, 2)] if len(live) > 1 else [_take(lib, st, 1)]
+        # prepare: the input gradient on rows (and in plain NCHW for a plain input), one weight / bias partial per block of rows
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dy.device)
+        dxr = new(n, h, w, c) if ctx.needs_input_grad[0] else None
+        dxp = new(n, c, h, w) if (dxr is not None and ctx.x_plain and m) else None
+        wparts = [new(o, c) for _ in live] if ctx.needs_input_grad[1] else []
+        bparts = [new(o) for _ in live] if ctx.needs_input_grad[2] else []
+        # the input gradient on the caller's stream; beside it the weight gradient of block j on branch 1 + j % 2 and the column sums on
+        # branch 3 (both use the library's scratch: each from the pool of its branch)
+        with _branches(lib, st) as take:
+            if dxr is not None:
+                for blk, r0, nr in live:
+                    _lib.check(lib.cffm_linear_bwd_input(_ptr(blk), _ptr(wm), C.c_void_p(dxr.data_ptr() + 4 * r0 * c), nr, o, c, st), lib)
+                if dxp is not None:
+                    _lib.check(lib.cffm_transpose(_ptr(dxr), _ptr(dxp), n, h * w, c, c * h * w, c * h * w, st), lib)
+            if wparts:
+                sw = [take(1), take(2)] if len(live) > 1 else [take(1)]
                 for j, ((blk, r0, nr), t) in enumerate(zip(live, wparts)):
                     _lib.check(lib.cffm_linear_bwd_weight(_ptr(blk), C.c_void_p(rows.data_ptr() + 4 * r0 * c), _ptr(t), nr, o, c, sw[j % len(sw)]), lib)
-            if ctx.needs_input_grad[2]:
-                bparts = [torch.empty(o, dtype=torch.float32, device=dy.device) for _ in live]
-                sb = _take(lib, st, 3)
+            if bparts:
+                sb = take(3)
                 for (blk, r0, nr), t in zip(live, bparts):
                     _lib.check(lib.cffm_colsum(_ptr(blk), nr, o, _ptr(t), sb), lib)
-        _join(lib, st)
+        if dxr is not None:                        # (dxr, the transpose's source, stays referenced behind the join)
+            dx = dxp if dxp is not None else dxr.permute(0, 3, 1, 2)
         if ctx.needs_input_grad[1]:
             dwm = wparts[0] if wparts else torch.zeros(o, c, dtype=torch.float32, device=dy.device)
             for t in wparts[1:]:
@@ -599,7 +594,15 @@ def conv1x1(x, weight, bias, clips=0, extra=0):
     GEMM on token rows; returns [N,O,H,W] in channels-last memory, or [clips, N/clips, O, H, W] (same memory) when `clips` is given.
     `extra` (with `clips`): the rows are written into a [clips, N/clips + extra, H, W, O] buffer, so that `cat_into` can append the clip-level
     maps (cffm_head.py:150 `torch.cat([x, x2], 1)`) without copying these."""
-    return _Conv1x1Fn.apply(x, weight, bias, int(clips), int(extra))
+    y = _Conv1x1Fn.apply(x, weight, bias, int(clips), int(extra))
+    if clips and extra:
+        _ROOMS[y.untyped_storage()] = (y.storage_offset(), y.shape, y.stride(), int(extra))
+    return y
+
+
+# storage of a conv1x1(..., clips, extra=e) buffer whose room is still free -> (offset, shape, strides of its front view, e).  Keyed weakly on
+# the storage object (one per buffer, whichever tensor asks for it): an entry neither keeps its buffer alive nor outlives it.
+_ROOMS = weakref.WeakKeyDictionary()
 
 
 class _CatIntoFn(torch.autograd.Function):
@@ -630,6 +633,25 @@ def _join_deferred():
         lib = _lib.get()
         lib.cffm_defer_join(_stream(_DEFERRED[0][0]))
         del _DEFERRED[:]
+
+
+@contextlib.contextmanager
+def _deferred(lib, st, keep):
+    """`with _deferred(lib, st, keep) as sd:` (inside a backward pass) -- stage calls on the library's deferred stream sd, ordered behind `st` as
+    it stands (cffm_defer_begin).  No join on exit: `st` continues at once, whoever reads the results calls _join_deferred() first, and the end of
+    the backward pass joins in any case.  `keep` -- every tensor the stage calls touch, allocated BEFORE the scope as for _branches -- is registered
+    before the first stage call and released by the join; when a stage call raises, the join happens here.  The end-of-pass callback is queued every
+    time (joining nothing is a no-op): a pass that died after deferring never ran its own, and the next join -- at the latest the end of the next pass that defers -- releases what it left."""
+    sd = C.c_void_p(lib.cffm_defer_begin(st))
+    if sd.value != st.value:
+        _DEFERRED.append(keep)
+        torch.autograd.Variable._execution_engine.queue_callback(_join_deferred)
+    try:
+        yield sd
+    except BaseException:
+        if sd.value != st.value:
+            _join_deferred()
+        raise
 
 
 class _LateGradFn(torch.autograd.Function):
@@ -698,43 +720,35 @@ class _FrameLogitsCatFn(torch.autograd.Function):
         if not all(g5[i].is_contiguous() for i in range(clips)):
             g5 = g5.contiguous()
         per, st, dev = t * h * w, _stream(rows), rows.device
+        # prepare: the results (zero where no stage call will write them), one partial per further clip, the plain-NCHW input gradient
+        new = torch.empty if per else torch.zeros
         dx = torch.empty(n, h, w, c, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-        dwm = torch.zeros(o, c, dtype=torch.float32, device=dev) if (ctx.needs_input_grad[1] and not per) else (torch.empty(o, c, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None)
-        db = torch.zeros(o, dtype=torch.float32, device=dev) if (ctx.needs_input_grad[2] and not per) else (torch.empty(o, dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None)
-        keep = [rows, wm, g5, dx, dwm, db]
+        dwm = new(o, c, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        db = new(o, dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
+        tws = [dwm] + [torch.empty_like(dwm) for _ in range(1, clips)] if (dwm is not None and per) else []
+        tbs = [db] + [torch.empty_like(db) for _ in range(1, clips)] if (db is not None and per) else []
+        dxp = torch.empty(n, c, h, w, dtype=torch.float32, device=dev) if (dx is not None and ctx.x_plain and per) else None
         if per:
-            sd = C.c_void_p(lib.cffm_defer_begin(st))
             blk = [g5[i, :t] for i in range(clips)]
-            if dx is not None:
+            with _deferred(lib, st, [rows, wm, g5, dx] + tws + tbs) as sd:
+                if dx is not None:
+                    for i in range(clips):
+                        _lib.check(lib.cffm_linear_bwd_input(_ptr(blk[i]), _ptr(wm), C.c_void_p(dx.data_ptr() + 4 * i * per * c), per, o, c, sd), lib)
                 for i in range(clips):
-                    _lib.check(lib.cffm_linear_bwd_input(_ptr(blk[i]), _ptr(wm), C.c_void_p(dx.data_ptr() + 4 * i * per * c), per, o, c, sd), lib)
-            for i in range(clips):
-                xi = C.c_void_p(rows.data_ptr() + 4 * i * per * c)
-                if dwm is not None:
-                    tw = dwm if i == 0 else torch.empty_like(dwm)
-                    _lib.check(lib.cffm_linear_bwd_weight(_ptr(blk[i]), xi, _ptr(tw), per, o, c, sd), lib)
-                    if i:
-                        _lib.check(lib.cffm_add_inplace(_ptr(dwm), _ptr(tw), o * c, sd), lib)
-                        keep.append(tw)
-                if db is not None:
-                    tb = db if i == 0 else torch.empty_like(db)
-                    _lib.check(lib.cffm_colsum(_ptr(blk[i]), per, o, _ptr(tb), sd), lib)
-                    if i:
-                        _lib.check(lib.cffm_add_inplace(_ptr(db), _ptr(tb), o, sd), lib)
-                        keep.append(tb)
-            if sd.value != st.value:
-                if not _DEFERRED:
-                    torch.autograd.Variable._execution_engine.queue_callback(_join_deferred)
-                _DEFERRED.append(keep)
-        dfused = None
-        if dx is not None:
-            if ctx.x_plain and per:                     # (plain NCHW input: the heads' rows path hands channels-last memory, this is the general case)
-                _join_deferred()
-                dxp = torch.empty(n, c, h, w, dtype=torch.float32, device=dev)
-                _lib.check(lib.cffm_transpose(_ptr(dx), _ptr(dxp), n, h * w, c, c * h * w, c * h * w, st), lib)
-                dfused = dxp
-            else:
-                dfused = dx.permute(0, 3, 1, 2)
+                    xi = C.c_void_p(rows.data_ptr() + 4 * i * per * c)
+                    if tws:
+                        _lib.check(lib.cffm_linear_bwd_weight(_ptr(blk[i]), xi, _ptr(tws[i]), per, o, c, sd), lib)
+                        if i:
+                            _lib.check(lib.cffm_add_inplace(_ptr(dwm), _ptr(tws[i]), o * c, sd), lib)
+                    if tbs:
+                        _lib.check(lib.cffm_colsum(_ptr(blk[i]), per, o, _ptr(tbs[i]), sd), lib)
+                        if i:
+                            _lib.check(lib.cffm_add_inplace(_ptr(db), _ptr(tbs[i]), o, sd), lib)
+        dfused = dx.permute(0, 3, 1, 2) if dx is not None else None
+        if dxp is not None:                             # (plain NCHW input: the heads' rows path hands channels-last memory, this is the general case)
+            _join_deferred()
+            _lib.check(lib.cffm_transpose(_ptr(dx), _ptr(dxp), n, h * w, c, c * h * w, c * h * w, st), lib)
+            dfused = dxp
         return dfused, (dwm.view(o, c, 1, 1) if dwm is not None else None), db, g[:, t:], None
 
 
@@ -744,19 +758,18 @@ def frame_logits_cat(fused, weight, bias, x2, clips):
 
 
 def cat_room(x, extra):
-    """True when x [B,T,K,h,w] is the front of a buffer with room for `extra` more maps per clip (conv1x1(..., extra=...))"""
-    if x.dim() != 5:
-        return False
-    b, t, k, h, w = x.shape
-    per = h * w * k
-    try:
-        ok = x.stride() == ((t + extra) * per, per, 1, w * k, k) and x.untyped_storage().nbytes() >= 4 * (x.storage_offset() + b * (t + extra) * per)
-    except Exception:       # noqa: BLE001
-        ok = False
-    return bool(ok)
+    """True when x is what conv1x1(..., clips=B, extra=e) handed out -- the front [B,T,K,h,w] of a [B,T+e,h,w,K] buffer -- or an alias of it
+    (detach(): same buffer, offset, shape and strides), with `extra` <= e and the room not yet filled.  By the buffer's entry in _ROOMS, not by
+    strides alone: a [:, :T] slice of any rows buffer has the same strides with live data behind it.  Everything else is torch.cat's job."""
+    room = _ROOMS.get(x.untyped_storage())
+    return room is not None and room[:3] == (x.storage_offset(), x.shape, x.stride()) and 0 < extra <= room[3]
 
 
 def cat_into(x, x2):
+    """torch.cat([x, x2], 1) into the room behind x (cat_room(x, x2.shape[1]) must hold); fills the room, so its entry goes"""
+    if x2.dim() != 5 or not cat_room(x, x2.shape[1]) or x2.shape[0] != x.shape[0] or x2.shape[2:] != x.shape[2:]:
+        raise _lib.CffmError('cat_into: no room for %s behind %s (ops.cat_room)' % (tuple(x2.shape), tuple(x.shape)))
+    del _ROOMS[x.untyped_storage()]
     return _CatIntoFn.apply(x, x2)
 
 
@@ -768,16 +781,12 @@ class _LayerRowsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_rows, h0, w0, depth, *params):
         lib = _lib.get()
-        _require_device(x_rows, 'cffm layer input')
-        if x_rows.dim() != 4 or x_rows.shape[1] != 4 or x_rows.shape[2] != h0 * w0 or x_rows.shape[3] != 256:
-            raise _lib.CffmError('expected x_rows [B,4,%d,256], got %s' % (h0 * w0, tuple(x_rows.shape)))
+        _check_rows(x_rows, h0, w0)
         assert len(params) == NPB * depth
         x_rows = x_rows.contiguous()
         b = x_rows.shape[0]
-        g = make_geom(lib, b, h0, w0)
-        key_src, q_dst, inv_ptr, inv_idx = device_tables(h0, w0, x_rows.device)
-        saved = torch.empty(lib.cffm_layer_saved_floats(C.byref(g), depth), dtype=torch.float32, device=x_rows.device)
-        scratch = torch.empty(lib.cffm_layer_scratch_floats(C.byref(g)), dtype=torch.float32, device=x_rows.device)
+        g, (key_src, q_dst, inv_ptr, inv_idx) = _layer_geom(lib, b, h0, w0, x_rows.device)
+        saved, scratch = _layer_buffers(lib, g, depth, x_rows.device)
         y = torch.empty(b, h0 * w0, 256, dtype=torch.float32, device=x_rows.device)
         _lib.check(lib.cffm_layer_forward_rows(C.byref(g), depth, block_structs(params, depth), _ptr(x_rows), _ptr(y), _ptr(key_src),
                                                _ptr(q_dst), _ptr(saved), _ptr(scratch), _stream(x_rows)), lib)
@@ -794,9 +803,7 @@ class _LayerRowsFn(torch.autograd.Function):
         b, h0, w0 = ctx.geom_args
         g = make_geom(lib, b, h0, w0)
         dy = dy.contiguous()
-        sizes = [(p.numel() + 3) // 4 * 4 for p in params]
-        flat = torch.empty(sum(sizes), dtype=torch.float32, device=dy.device)       # (the library zeroes the alignment gaps: see _LayerFullFn.backward)
-        grads = [c[:p.numel()].view(p.shape) for c, p in zip(flat.split(sizes), params)]
+        _, grads, _ = _flat_grads(params, dy.device)                   # torch.empty: the library zeroes the alignment gaps
         dx = torch.empty(b, 4, h0 * w0, 256, dtype=torch.float32, device=dy.device)
         _checked_padded(lib, lib.cffm_layer_backward_rows, C.byref(g), depth, block_structs(params, depth), block_structs(grads, depth), _ptr(x_rows),
                                                 _ptr(dy), _ptr(dx), _ptr(key_src), _ptr(q_dst), _ptr(inv_ptr), _ptr(inv_idx), _ptr(saved),
@@ -853,17 +860,12 @@ def cffm_layer_infer(x, depth, params, prepared, ws=None, out=None):
     """cffm_layer without autograd: x [B,4,256,H,W] -> [B,4,256,H,W] (frames 0..2 are the input frames).  ``ws`` / ``out``: optional
     caller-owned workspace (``cffm_layer_infer_ws_floats`` floats) and result tensor, e.g. static buffers of a captured graph."""
     lib = _lib.get()
-    _require_device(x, 'cffm layer input')
-    if x.dim() != 5 or x.shape[2] != 256:
-        raise _lib.CffmError('expected x [B,T,256,H,W], got %s' % (tuple(x.shape),))
-    if x.shape[1] != 4:
-        raise IndexError('CFFM block needs T == 4 frames (3 reference + target), got T=%d' % x.shape[1])
+    _check_stack(x)
     if len(params) != NPB * depth:         # (dtype / device / contiguity were checked when `prepared` was built from them)
         raise _lib.CffmError('expected %d parameter tensors for depth %d, got %d' % (NPB * depth, depth, len(params)))
     b, _, _, h0, w0 = x.shape
     x = x.detach().contiguous()
-    g = make_geom(lib, b, h0, w0)
-    key_src, q_dst = device_tables(h0, w0, x.device)[:2]
+    g, (key_src, q_dst, *_) = _layer_geom(lib, b, h0, w0, x.device)
     ws, out = _infer_buffers(lib, g, depth, prepared, ws, out, (b, 4, 256, h0, w0), x.device)
     _lib.check(lib.cffm_layer_infer_full(C.byref(g), depth, block_structs(params, depth), _ptr(prepared), _ptr(x), _ptr(out), _ptr(key_src),
                                          _ptr(q_dst), _ptr(ws), _stream(x)), lib)
@@ -873,15 +875,12 @@ def cffm_layer_infer(x, depth, params, prepared, ws=None, out=None):
 def cffm_layer_rows_infer(x_rows, h0, w0, depth, params, prepared, ws=None, out=None):
     """cffm_layer_rows without autograd: x_rows [B,4,H*W,256] -> the new target frame [B,H*W,256]."""
     lib = _lib.get()
-    _require_device(x_rows, 'cffm layer input')
-    if x_rows.dim() != 4 or x_rows.shape[1] != 4 or x_rows.shape[2] != h0 * w0 or x_rows.shape[3] != 256:
-        raise _lib.CffmError('expected x_rows [B,4,%d,256], got %s' % (h0 * w0, tuple(x_rows.shape)))
+    _check_rows(x_rows, h0, w0)
     if len(params) != NPB * depth:
         raise _lib.CffmError('expected %d parameter tensors for depth %d, got %d' % (NPB * depth, depth, len(params)))
     x_rows = x_rows.detach().contiguous()
     b = x_rows.shape[0]
-    g = make_geom(lib, b, h0, w0)
-    key_src, q_dst = device_tables(h0, w0, x_rows.device)[:2]
+    g, (key_src, q_dst, *_) = _layer_geom(lib, b, h0, w0, x_rows.device)
     ws, out = _infer_buffers(lib, g, depth, prepared, ws, out, (b, h0 * w0, 256), x_rows.device)
     _lib.check(lib.cffm_layer_infer_rows(C.byref(g), depth, block_structs(params, depth), _ptr(prepared), _ptr(x_rows), _ptr(out), _ptr(key_src),
                                          _ptr(q_dst), _ptr(ws), _stream(x_rows)), lib)
