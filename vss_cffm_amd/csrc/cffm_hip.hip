@@ -147,10 +147,7 @@ int cffm_profile_sample_every(int period) {
 // stream / in this graph -- bench.py reports it next to the roofline kernel's interval (22.6 us between events vs 19.7 us in
 // rocprofv3's kernel trace; the empty pair measures 5-6 us, so it is not simply additive and is not subtracted)
 int cffm_profile_null_pair(void* stream) {
-#ifndef CFFM_EMU
     PROF(ST_NULL_PAIR);
-#endif
-    (void)stream;
     return 0;
 }
 // on = 0: the library's side streams are not used until switched on again -- every kernel of a block backward then runs on the caller's
@@ -293,60 +290,35 @@ long cffm_layer_scratch_floats(const cffm_geom* g) { return scratch_layout(g).to
 
 
 // ------------------------------------------------------------------------------------------- internal scratch
+// Every library-owned buffer is a DevBuf: it only grows, to exactly what is asked; the old buffer is freed behind a device
+// synchronisation (work in flight may still use it); NULL, and nothing held, when the allocation fails.
+struct DevBuf {
+    float* p = nullptr;
+    size_t floats = 0;
+    float* grow(size_t nfloats) {
+        if (nfloats <= floats) return p;
+        if (p) { (void)hipDeviceSynchronize(); (void)hipFree(p); }
+        if (hipMalloc((void**)&p, nfloats * sizeof(float)) != hipSuccess) p = nullptr;
+        floats = p ? nfloats : 0;
+        return p;
+    }
+};
 // Small library-owned device buffer for the block-partial records of the two-stage reductions
 // (grows on demand; stream-ordered reuse, one stream at a time as the ABI's threading rule says).
 // One pool per stream a stage call can arrive on: the caller's (0), the four branches of cffm_branch_begin / _take (1..4) and the deferred
 // branch of cffm_defer_begin (5) -- stage calls
 // that need scratch (split-K slabs of the weight gradients, column-sum records) may then run on different branches at the same time.
 // ScratchFor selects the pool for the duration of a public stage call from its `stream` argument; everything else uses pool 0.
-static float* g_scr[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-static size_t g_scr_floats[6] = {0, 0, 0, 0, 0, 0};
+static DevBuf g_scr[6];
 static int g_scr_sel = 0;
-extern "C++" __attribute__((visibility("hidden"))) float* lib_scratch(size_t nfloats) {
-    float*& buf = g_scr[g_scr_sel];
-    size_t& have = g_scr_floats[g_scr_sel];
-    if (nfloats <= have) return buf;
-#ifdef CFFM_EMU
-    free(buf);
-    buf = (float*)malloc(nfloats * sizeof(float));
-#else
-    if (buf) { (void)hipDeviceSynchronize(); (void)hipFree(buf); }
-    if (hipMalloc((void**)&buf, nfloats * sizeof(float)) != hipSuccess) buf = nullptr;
-#endif
-    have = buf ? nfloats : 0;
-    return buf;
-}
+extern "C++" __attribute__((visibility("hidden"))) float* lib_scratch(size_t nfloats) { return g_scr[g_scr_sel].grow(nfloats); }
 // second scratch buffer, for work issued on the library's side stream (runs concurrently with users of lib_scratch)
-static float* g_scr2 = nullptr;
-static size_t g_scr2_floats = 0;
-static float* lib_scratch2(size_t nfloats) {
-    if (nfloats <= g_scr2_floats) return g_scr2;
-#ifdef CFFM_EMU
-    free(g_scr2);
-    g_scr2 = (float*)malloc(nfloats * sizeof(float));
-#else
-    if (g_scr2) { (void)hipDeviceSynchronize(); (void)hipFree(g_scr2); }
-    if (hipMalloc((void**)&g_scr2, nfloats * sizeof(float)) != hipSuccess) g_scr2 = nullptr;
-#endif
-    g_scr2_floats = g_scr2 ? nfloats : 0;
-    return g_scr2;
-}
+static DevBuf g_scr2;
+static float* lib_scratch2(size_t nfloats) { return g_scr2.grow(nfloats); }
 // third scratch buffer: the per-group bias-gradient tiles of the attention backward (read by a side-stream kernel while the
 // caller's stream goes on using lib_scratch)
-static float* g_scr3 = nullptr;
-static size_t g_scr3_floats = 0;
-static float* lib_scratch3(size_t nfloats) {
-    if (nfloats <= g_scr3_floats) return g_scr3;
-#ifdef CFFM_EMU
-    free(g_scr3);
-    g_scr3 = (float*)malloc(nfloats * sizeof(float));
-#else
-    if (g_scr3) { (void)hipDeviceSynchronize(); (void)hipFree(g_scr3); }
-    if (hipMalloc((void**)&g_scr3, nfloats * sizeof(float)) != hipSuccess) g_scr3 = nullptr;
-#endif
-    g_scr3_floats = g_scr3 ? nfloats : 0;
-    return g_scr3;
-}
+static DevBuf g_scr3;
+static float* lib_scratch3(size_t nfloats) { return g_scr3.grow(nfloats); }
 // ---- side stream of the block backward -----------------------------------------------------------------------------------
 // Everything of a block backward that only produces PARAMETER gradients feeds nothing inside the chain (only the optimizer reads
 // it): the four weight-gradient GEMMs, the bias-gradient tile sum + scatter, the q|k|v bias column sum, the record reductions and
@@ -358,7 +330,6 @@ static float* lib_scratch3(size_t nfloats) {
 struct SideStream {
     bool on = false;
     int ns = 1;                 // side streams in use: 1 launched eagerly, 4 under stream capture and for the caller's branches
-#ifndef CFFM_EMU
     hipStream_t st[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t fork[4] = {nullptr, nullptr, nullptr, nullptr}, join[2] = {nullptr, nullptr}, order = nullptr, tail_order = nullptr;
     // deferred join of a block backward (layer_backward_impl): what the NEXT block has to wait for
@@ -367,33 +338,22 @@ struct SideStream {
     const float* dw_dout[2] = {nullptr, nullptr};   // the `dout` a pending weight-gradient group still reads
     int par = 0;                // scratch set of the block backward being issued
     unsigned used = 0;          // side streams forked since the last full join
-#endif
 };
 static SideStream g_side;
-#ifndef CFFM_EMU
 static struct { hipStream_t st = nullptr; hipEvent_t fork = nullptr, done = nullptr; bool used = false; int state = -1; } g_defer;   // cffm_defer_begin
-#endif
 struct ScratchFor {       // RAII: pool of the branch `stream` is (cffm_branch_begin / _take, cffm_defer_begin), else the caller's pool
     explicit ScratchFor(void* stream) {
         g_scr_sel = 0;
-#ifndef CFFM_EMU
         for (int i = 0; i < 4; ++i)
             if (stream && (hipStream_t)stream == g_side.st[i]) g_scr_sel = i + 1;
         if (stream && (hipStream_t)stream == g_defer.st) g_scr_sel = 5;
-#endif
-        (void)stream;
     }
     ~ScratchFor() { g_scr_sel = 0; }
 };
 static int stream_is_capturing(hipStream_t st) {
-#ifdef CFFM_EMU
-    (void)st;
-    return 0;
-#else
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return 0; }
     return cs == hipStreamCaptureStatusActive ? 1 : 0;
-#endif
 }
 // `main`: the caller's stream.  Launched eagerly ONE side stream measured best (0.877 vs 0.929 ms per step with two); under stream
 // capture more (two: 0.882-0.895 vs 0.902-0.906 replayed: branches that do not queue behind each other give the graph executor more
@@ -403,7 +363,6 @@ static bool side_init(hipStream_t main) {
     static int state = -1;
     if (state < 0) {
         state = 0;
-#ifndef CFFM_EMU
         auto mk = [](hipStream_t* st_) { return hipStreamCreateWithFlags(st_, hipStreamNonBlocking) == hipSuccess; };
         if (mk(&g_side.st[0]) && mk(&g_side.st[1]) && mk(&g_side.st[2]) && mk(&g_side.st[3])) {
             bool ok = hipEventCreateWithFlags(&g_side.order, hipEventDisableTiming) == hipSuccess &&
@@ -417,7 +376,6 @@ static bool side_init(hipStream_t main) {
             state = ok ? 1 : 0;
         }
         (void)hipGetLastError();
-#endif
     }
     g_side.on = state == 1 && !g_side_off;
     g_side.ns = stream_is_capturing(main) ? 4 : 1;
@@ -450,7 +408,7 @@ static int dw_one_group(hipStream_t st) {
     if (forced >= 0) return forced;
 #ifdef CFFM_EMU
     (void)st;
-    return 1;
+    return 1;     // (the emulator tests walk the grouped form; the split form is reached with CFFM_DW_GROUP=split)
 #else
     return stream_is_capturing(st);
 #endif
@@ -460,14 +418,8 @@ static int dw_one_group(hipStream_t st) {
 // same-queue succession costs ~1.5 (round-3 timeline: the chain hopped queues at every fork because the side work was launched first).
 // So a fork is split: side_fork_mark() records the point on `main`, the chain's next kernel is launched, and only then
 // side_fork_take() makes the side stream wait for the mark and hands it out.
-static void side_fork_mark(hipStream_t main, int i) {
-#ifndef CFFM_EMU
-    if (g_side.on) (void)hipEventRecord(g_side.fork[i], main);
-#endif
-    (void)main; (void)i;
-}
+static bool side_fork_mark(hipStream_t main, int i) { return g_side.on && hipEventRecord(g_side.fork[i], main) == hipSuccess; }
 static hipStream_t side_fork_take(hipStream_t main, int i) {
-#ifndef CFFM_EMU
     const int idx = g_side.ns >= 4 ? (i & 3) : 0;
     hipStream_t s = g_side.st[idx];
     if (g_side.on && hipStreamWaitEvent(s, g_side.fork[i], 0) == hipSuccess) {
@@ -475,46 +427,26 @@ static hipStream_t side_fork_take(hipStream_t main, int i) {
         return s;
     }
     (void)hipGetLastError();
-#endif
-    (void)i;
     return main;
 }
-static hipStream_t side_fork(hipStream_t main, int i) {
-#ifndef CFFM_EMU
-    const int idx = g_side.ns >= 4 ? (i & 3) : 0;
-    hipStream_t s = g_side.st[idx];
-    if (g_side.on && hipEventRecord(g_side.fork[i], main) == hipSuccess && hipStreamWaitEvent(s, g_side.fork[i], 0) == hipSuccess) {
-        g_side.used |= 1u << idx;
-        return s;
-    }
+static hipStream_t side_fork(hipStream_t main, int i) {     // (a mark that failed is not taken)
+    if (side_fork_mark(main, i)) return side_fork_take(main, i);
     (void)hipGetLastError();
-#endif
-    (void)i;
     return main;
 }
 // what is issued on `later` from here on runs after what has been issued on `earlier` (two different side streams)
 static void side_order(hipStream_t earlier, hipStream_t later) {
-#ifndef CFFM_EMU
     if (earlier != later && hipEventRecord(g_side.order, earlier) == hipSuccess) (void)hipStreamWaitEvent(later, g_side.order, 0);
-#endif
-    (void)earlier; (void)later;
 }
 static void side_mark(hipStream_t side, hipStream_t main, int i) {   // end of branch i
-#ifndef CFFM_EMU
     if (side != main) (void)hipEventRecord(g_side.join[i], side);
-#endif
-    (void)side; (void)main; (void)i;
 }
 static void side_join(hipStream_t side, hipStream_t main, int i) {   // `main` continues after branch i
-#ifndef CFFM_EMU
     if (side != main) (void)hipStreamWaitEvent(main, g_side.join[i], 0);
-#endif
-    (void)side; (void)main; (void)i;
 }
 
 // `main` continues after everything issued on any side stream since the last full join
 static void side_join_all(hipStream_t main) {
-#ifndef CFFM_EMU
     for (int i = 0; i < 4; ++i)
         if ((g_side.used >> i) & 1u) {
             if (hipEventRecord(g_side.join_all[i], g_side.st[i]) == hipSuccess) (void)hipStreamWaitEvent(main, g_side.join_all[i], 0);
@@ -522,8 +454,6 @@ static void side_join_all(hipStream_t main) {
     g_side.used = 0;
     g_side.bias_pending[0] = g_side.bias_pending[1] = g_side.dw_pending[0] = g_side.dw_pending[1] = g_side.tail_pending[0] = g_side.tail_pending[1] = false;
     (void)hipGetLastError();
-#endif
-    (void)main;
 }
 // ---- branches for the CALLER (ABI 10): independent stage calls of the head's rows path side by side -------------------------------
 // The head around the hot path (rows f.1 / f.2 of SURVEY 8: embedding per scale, composed weights, classifiers) is a sequence of stage
@@ -540,20 +470,14 @@ static void side_join_all(hipStream_t main) {
 // its own -- longest -- chain on `stream` first and only then takes the branches (cffm_branch_take) for the shorter ones.
 // cffm_branch_begin = mark + take of one branch at the current point.
 int cffm_branch_mark(void* stream) {
-#ifndef CFFM_EMU
     hipStream_t main = (hipStream_t)stream;
     if (!side_init(main)) return 0;
     g_side.ns = 4;
     for (int i = 0; i < 4; ++i)
         if (hipEventRecord(g_side.fork[i], main) != hipSuccess) { (void)hipGetLastError(); return 0; }
     return 1;
-#else
-    (void)stream;
-    return 0;
-#endif
 }
 void* cffm_branch_take(void* stream, int i) {
-#ifndef CFFM_EMU
     if (i < 0 || i > 3 || !g_side.on) return stream;
     hipStream_t s = g_side.st[i];
     if (hipStreamWaitEvent(s, g_side.fork[i], 0) == hipSuccess) {
@@ -561,24 +485,15 @@ void* cffm_branch_take(void* stream, int i) {
         return (void*)s;
     }
     (void)hipGetLastError();
-#endif
-    (void)i;
     return stream;
 }
 void* cffm_branch_begin(void* stream, int i) {
     hipStream_t main = (hipStream_t)stream;
-#ifndef CFFM_EMU
     if (i < 0 || i > 3 || !side_init(main)) return stream;
     g_side.ns = 4;
-    hipStream_t s = g_side.st[i];
-    if (hipEventRecord(g_side.fork[i], main) == hipSuccess && hipStreamWaitEvent(s, g_side.fork[i], 0) == hipSuccess) {
-        g_side.used |= 1u << i;
-        return (void*)s;
-    }
+    if (hipEventRecord(g_side.fork[i], main) == hipSuccess) return cffm_branch_take(stream, i);
     (void)hipGetLastError();
-#endif
-    (void)i;
-    return (void*)main;
+    return stream;
 }
 int cffm_branch_join(void* stream) {
     side_join_all((hipStream_t)stream);
@@ -591,7 +506,6 @@ int cffm_branch_join(void* stream) {
 // ordered behind everything issued on `stream` so far; cffm_defer_join(stream): `stream` continues behind it (a no-op when nothing is
 // pending).  Everything the deferred work touches must stay alive, and nothing on `stream` may read its results, until the join.
 void* cffm_defer_begin(void* stream) {
-#ifndef CFFM_EMU
     hipStream_t main = (hipStream_t)stream;
     if (g_side_off) return stream;
     if (g_defer.state < 0) {
@@ -605,38 +519,22 @@ void* cffm_defer_begin(void* stream) {
         return (void*)g_defer.st;
     }
     (void)hipGetLastError();
-#endif
     return stream;
 }
 int cffm_defer_join(void* stream) {
-#ifndef CFFM_EMU
     if (g_defer.used) {
         if (hipEventRecord(g_defer.done, g_defer.st) == hipSuccess) (void)hipStreamWaitEvent((hipStream_t)stream, g_defer.done, 0);
         g_defer.used = false;
         (void)hipGetLastError();
     }
-#endif
-    (void)stream;
     return 0;
 }
 // event helpers of the deferred join (no-ops when the work ran on `main` itself)
 static void side_record(hipStream_t side, hipStream_t main, void* ev) {
-#ifndef CFFM_EMU
     if (side != main) (void)hipEventRecord((hipEvent_t)ev, side);
-#endif
-    (void)side; (void)main; (void)ev;
 }
-static void side_wait(hipStream_t main, void* ev) {
-#ifndef CFFM_EMU
-    (void)hipStreamWaitEvent(main, (hipEvent_t)ev, 0);
-#endif
-    (void)main; (void)ev;
-}
-#ifndef CFFM_EMU
+static void side_wait(hipStream_t main, void* ev) { (void)hipStreamWaitEvent(main, (hipEvent_t)ev, 0); }
 static void dw_group_launched(hipStream_t side) { (void)hipEventRecord(g_side.dw_done[g_side.par], side); }
-#else
-static void dw_group_launched(hipStream_t) {}
-#endif
 
 static void seg_add(RedSegs& r, int off, int width, float* out, int accumulate) {
     if (!out) return;
@@ -647,11 +545,8 @@ static void seg_add(RedSegs& r, int off, int width, float* out, int accumulate) 
 // library-owned record buffer -- and run as ONE launch at the end of the scope; outside a scope they launch at once.
 // Two record buffers, used alternately by consecutive scopes (block backwards): the reduction of block i (side stream) may still
 // read its records while block i - 1 already writes its own (deferred join, see block_backward_impl)
-static float* g_redbuf[2] = {nullptr, nullptr};
-static size_t g_red_floats_[2] = {0, 0};
+static DevBuf g_redbuf[2];
 static int g_red_parity = 0;
-#define g_red g_redbuf[g_red_parity]
-#define g_red_floats g_red_floats_[g_red_parity]
 static struct { bool active; size_t bump; RedJobs jobs; } g_rq = {false, 0, {}};
 static void redq_launch(RedJobs& J, hipStream_t st) {
     if (J.njob == 1) {
@@ -673,24 +568,15 @@ struct RedScope {
 static float* red_scratch(size_t nfloats, hipStream_t st) {
     if (!g_rq.active) return lib_scratch(nfloats);
     nfloats = (nfloats + 63) / 64 * 64;
-    if (g_rq.bump + nfloats > g_red_floats) {
-#ifndef CFFM_EMU
+    DevBuf& red = g_redbuf[g_red_parity];
+    if (g_rq.bump + nfloats > red.floats) {
         (void)hipDeviceSynchronize();   // (growth happens in the first step only) the records queued so far may have been written on another stream
-#endif
         redq_flush(st);   // queued jobs read the old buffer
         const size_t want = 2 * (g_rq.bump + nfloats);
-#ifdef CFFM_EMU
-        free(g_red);
-        g_red = (float*)malloc(want * sizeof(float));
-#else
-        if (g_red) { (void)hipDeviceSynchronize(); (void)hipFree(g_red); }
-        if (hipMalloc((void**)&g_red, want * sizeof(float)) != hipSuccess) g_red = nullptr;
-#endif
-        g_red_floats = g_red ? want : 0;
         g_rq.bump = 0;
-        if (!g_red) return nullptr;
+        if (!red.grow(want)) return nullptr;
     }
-    float* p = g_red + g_rq.bump;
+    float* p = red.p + g_rq.bump;
     g_rq.bump += nfloats;
     return p;
 }
@@ -706,6 +592,7 @@ static void reduce_records(const float* part, int nblk, int stride, int total, c
     J.blk_end[j] = (j ? J.blk_end[j - 1] : 0) + (total + 63) / 64;
 }
 
+static bool aligned16(const void* p) { return p && (uintptr_t)p % 16 == 0; }     // what the vector loads of a kernel ask of a tensor
 static unsigned ew_grid(long n4) {
     long b = (n4 + 255) / 256;
     return (unsigned)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
@@ -782,14 +669,8 @@ template <int D>
 static int ln_pool_bwd_ref_d(const cffm_geom* g, const float* x_ref, long ref_bs, const CffaRefBlocks& Bk, const float* mean, const float* rstd,
                              float* dx_ref, long dref_bs, int accum, hipStream_t st) {
     constexpr int lds = cffa_ref_lds(D);
-#ifndef CFFM_EMU
-    static bool granted = false;
-    if (!granted && lds > 64 * 1024) {
-        if (hipFuncSetAttribute((const void*)k_ln_pool_bwd_ref<D, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_ln_pool_bwd_ref<D, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -1;
-        granted = true;
-    }
-#endif
+    static int lds_have = 0;
+    if (lds > 64 * 1024 && !lds_grant(lds_have, {{(const void*)k_ln_pool_bwd_ref<D, false>, lds}, {(const void*)k_ln_pool_bwd_ref<D, true>, lds}})) return -1;
     if (accum) CFFM_LAUNCH((k_ln_pool_bwd_ref<D, true>), ((unsigned)cffa_rows(g)), (LNB_THREADS), lds, st, to_geo(g), x_ref, ref_bs, Bk, mean, rstd, dx_ref, dref_bs);
     else CFFM_LAUNCH((k_ln_pool_bwd_ref<D, false>), ((unsigned)cffa_rows(g)), (LNB_THREADS), lds, st, to_geo(g), x_ref, ref_bs, Bk, mean, rstd, dx_ref, dref_bs);
     return 0;
@@ -838,24 +719,11 @@ static void cffa_jobs(RedJobs& J, const float* rec, long rows, float* dgamma, fl
 // Library-owned state of the CFFA backward, one SLOT per block of the layer: the block's token-row gradient dzall (written by the q|k|v
 // input-gradient GEMM, its pooled-cell rows are read again by the reference pass at the end of the range), the records of its target
 // and reference workgroups, its pooling-matrix gradient.
-static float* g_scr4 = nullptr;
-static size_t g_scr4_floats = 0;
-static float* lib_scratch4(size_t nfloats) {
-    if (nfloats <= g_scr4_floats) return g_scr4;
-#ifdef CFFM_EMU
-    free(g_scr4);
-    g_scr4 = (float*)malloc(nfloats * sizeof(float));
-#else
-    if (g_scr4) { (void)hipDeviceSynchronize(); (void)hipFree(g_scr4); }
-    if (hipMalloc((void**)&g_scr4, nfloats * sizeof(float)) != hipSuccess) g_scr4 = nullptr;
-#endif
-    g_scr4_floats = g_scr4 ? nfloats : 0;
-    return g_scr4;
-}
+static DevBuf g_scr4;
 struct CffaSlot { float* dzall; float* rec; float* dM; };
 static int cffa_slot(const cffm_geom* g, int slot, int nslots, CffaSlot* o) {
     const long a = up((long)g->B * g->RC * CFFM_C), b = up(2 * cffa_rows(g) * LNP_RSTRIDE), c = up(CFFM_NCELL * CFFM_WA);
-    float* base = lib_scratch4((size_t)(a + b + c) * nslots);
+    float* base = g_scr4.grow((size_t)(a + b + c) * nslots);
     REQUIRE(base && slot >= 0 && slot < nslots, "cffa: scratch allocation failed");
     float* p = base + (a + b + c) * slot;
     o->dzall = p; o->rec = p + a; o->dM = p + a + b;
@@ -964,14 +832,8 @@ static int attn_bwd_fused(const cffm_geom* g, const void* qkv16, const int* key_
     float* dbp = lib_scratch3((size_t)2 * ng * nb);      // two sets: see scratch_layout (alt)
     REQUIRE(dbp, "attn_bwd: scratch allocation failed");
     dbp += (size_t)(par ? 1 : 0) * ng * nb;
-#ifndef CFFM_EMU
-    static bool granted = false;
-    if (!granted) {
-        REQUIRE(hipFuncSetAttribute((const void*)k_cfm_attn_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_BK_LDS) == hipSuccess,
-                "attn_bwd: LDS grant failed");
-        granted = true;
-    }
-#endif
+    static int lds_have = 0;
+    REQUIRE(lds_grant(lds_have, {{(const void*)k_cfm_attn_bwd, ATT_BK_LDS}}), "attn_bwd: LDS grant failed");
     CFFM_LAUNCH(k_cfm_attn_bwd, (CFFM_HEADS, ng), (ATT_BK_THREADS), ATT_BK_LDS, (hipStream_t)stream, to_geo(g), (const h16*)qkv16, key_src, q_dst, bias,
                 ao, dao, lse, dqkv, dbp, dkv_part, per);
     CHECK_LAUNCH("attn_bwd");
@@ -1149,13 +1011,8 @@ int cffm_gtc_attn_fwd(const float* q_raw, const float* q_b, const float* kv_raw,
                       int B, int T, int K, void* stream) {
     PROF(ST_GTC_FWD);
     REQUIRE(K >= 1 && K <= 256, "gtc_attn_fwd: K=%d outside 1..256", K);
-#ifndef CFFM_EMU
-    static bool granted = false;
-    if (!granted) {
-        REQUIRE(hipFuncSetAttribute((const void*)k_gtc_attn_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, gtf_lds(256)) == hipSuccess, "gtc_attn_fwd: LDS grant failed");
-        granted = true;
-    }
-#endif
+    static int lds_have = 0;
+    REQUIRE(lds_grant(lds_have, {{(const void*)k_gtc_attn_fwd, gtf_lds(256)}}), "gtc_attn_fwd: LDS grant failed");
     if (K <= 128) {
         // the matrix-pipe form (three-pass bf16 split): ~512 workgroups of four waves, each wave a run of 16-token tiles
         const int tiles = (T + 15) / 16;
@@ -1201,14 +1058,9 @@ int cffm_gtc_attn_bwd(const float* q_raw, const float* q_b, const float* kv_raw,
         float* Dbuf = scr;
         float* rec = scr + nD;
         f32x4* fr = (f32x4*)(scr + nD + nrecf);
-#ifndef CFFM_EMU
-        static bool granted_m = false;
-        if (!granted_m) {
-            REQUIRE(hipFuncSetAttribute((const void*)k_gtc_attn_bwd_dkv_mfma<3>, hipFuncAttributeMaxDynamicSharedMemorySize, gtm_bwd_lds(4)) == hipSuccess &&
-                    hipFuncSetAttribute((const void*)k_gtc_attn_bwd_dkv_mfma<4>, hipFuncAttributeMaxDynamicSharedMemorySize, gtm_bwd_lds(4)) == hipSuccess, "gtc_attn_bwd: LDS grant failed");
-            granted_m = true;
-        }
-#endif
+        static int lds_have_m = 0;
+        REQUIRE(lds_grant(lds_have_m, {{(const void*)k_gtc_attn_bwd_dkv_mfma<3>, gtm_bwd_lds(4)}, {(const void*)k_gtc_attn_bwd_dkv_mfma<4>, gtm_bwd_lds(4)}}),
+                "gtc_attn_bwd: LDS grant failed");
 #define GTM_BWD(U_)                                                                                                                                              \
         do {                                                                                                                                                 \
             const f32x4* fq = U_ > 1 ? (const f32x4*)fr : nullptr;        /* U = 1: the kernels make their own copy (gtm_pack_local) */                        \
@@ -1226,13 +1078,8 @@ int cffm_gtc_attn_bwd(const float* q_raw, const float* q_b, const float* kv_raw,
     const int per = gtb_tok(K) * GTB_CHUNKS, nwg = (T + per - 1) / per;
     float* rec = lib_scratch((size_t)B * CFFM_HEADS * nwg * K * 64);       // one [K][64] record per workgroup: k_gtc_dkv_sum adds them in order
     REQUIRE(rec, "gtc_attn_bwd: scratch allocation failed");
-#ifndef CFFM_EMU
-    static bool granted = false;
-    if (!granted) {
-        REQUIRE(hipFuncSetAttribute((const void*)k_gtc_attn_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess, "gtc_attn_bwd: LDS grant failed");
-        granted = true;
-    }
-#endif
+    static int lds_have = 0;
+    REQUIRE(lds_grant(lds_have, {{(const void*)k_gtc_attn_bwd, 160 * 1024}}), "gtc_attn_bwd: LDS grant failed");
     CFFM_LAUNCH(k_gtc_attn_bwd, (nwg, CFFM_HEADS, B), (256), (size_t)gtb_lds(K), st, q_raw, q_b, kv_raw, kv_b, o, dout, lse, dq_raw, rec, T, K);
     CFFM_LAUNCH(k_gtc_dkv_sum, (K, CFFM_HEADS, B), (64), 0, st, (const float*)rec, nwg, K, dkv);
     CHECK_LAUNCH("gtc_attn_bwd");
@@ -1247,16 +1094,8 @@ int cffm_gtc_attn_bwd(const float* q_raw, const float* q_b, const float* kv_raw,
 #endif
 #define MLP_D 4
 static int mlp_lds_grant() {
-#ifndef CFFM_EMU
-    static bool granted = false;
-    if (!granted) {
-        if (hipFuncSetAttribute((const void*)k_mlp_fwd<MLP_MT, MLP_D>, hipFuncAttributeMaxDynamicSharedMemorySize, PNL_FUSED_LDS(MLP_MT)) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_mlp_bwd<MLP_MT, MLP_D>, hipFuncAttributeMaxDynamicSharedMemorySize, PNL_FUSED_LDS(MLP_MT)) != hipSuccess)
-            return -1;
-        granted = true;
-    }
-#endif
-    return 0;
+    static int lds_have = 0;
+    return lds_grant(lds_have, {{(const void*)k_mlp_fwd<MLP_MT, MLP_D>, PNL_FUSED_LDS(MLP_MT)}, {(const void*)k_mlp_bwd<MLP_MT, MLP_D>, PNL_FUSED_LDS(MLP_MT)}}) ? 0 : -1;
 }
 // q|k|v Linear and its input gradient as row-panel GEMMs (weights in fragment order): rows per workgroup (32 or 48) chosen so that
 // the grid wastes the least of its last round on 256 CUs
@@ -1269,13 +1108,8 @@ template <int MT, int NTW, bool A_PRE, int EPI>
 static int panel_gemm_launch(const float* A, int lda, long M, int K, const float* wf, float* Cout, int ldc, const float* bias, void* aux,
                              hipStream_t st, float* colrec = nullptr, float* a_t = nullptr) {
     auto kern = k_panel_gemm<MT, NTW, 2, 4, A_PRE, EPI>;
-#ifndef CFFM_EMU
-    static bool granted = false;
-    if (!granted) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, PNL_LDS(MT)) != hipSuccess) return -1;
-        granted = true;
-    }
-#endif
+    static int lds_have = 0;
+    if (!lds_grant(lds_have, {{(const void*)kern, PNL_LDS(MT)}})) return -1;
     CFFM_LAUNCH(kern, ((unsigned)((M + 16 * MT - 1) / (16 * MT))), (PNL_THREADS), PNL_LDS(MT), st, A, lda, (int)M, K, (const f32x4*)wf, Cout, ldc, bias, aux, colrec, (f32x4*)a_t);
     return 0;
 }
@@ -1484,13 +1318,8 @@ int cffm_gtc_block_backward(const cffm_gtc_params* p, const cffm_gtc_grads* g, c
     const GtcWs W = gtc_ws_layout(nt, nk);
     float* wn = ws + W.wn;
     TRY(gtc_pack(p, wn, 1, stream));
-#ifdef CFFM_EMU
-    memset(g->qkv_w + 256 * 256, 0, sizeof(float) * 512 * 256);
-    memset(g->qkv_b + 256, 0, sizeof(float) * 512);
-#else
     REQUIRE(hipMemsetAsync(g->qkv_w + 256 * 256, 0, sizeof(float) * 512 * 256, st) == hipSuccess &&
             hipMemsetAsync(g->qkv_b + 256, 0, sizeof(float) * 512, st) == hipSuccess, "gtc_block_backward: memset failed");
-#endif
     RedScope reductions(st);      // the bias / norm record reductions below run as ONE launch (finish())
     // x2 = x1 + Mlp(LN2(x1)), x1 = x + o Wpc^T + bpc: the fused input-gradient chain of the base block
     TRY(cffm_mlp_bwd_tfrag(dout, ws + W.hraw, p->fc1_b, ws + W.x1, ws + W.mean2, ws + W.rstd2, p->norm2_w, wn + 2 * 256 * 256 + CFFM_HID * 256,
@@ -1636,7 +1465,6 @@ static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, c
 // of ln_pool_bwd (event fork[3]), but the launches happen only after the chain's next kernel has been launched (tail_flush), so that
 // under stream capture the chain's kernel is ln_pool_bwd's FIRST dependant and keeps its place on the graph's first stream (the graph
 // executor hands every further dependant of a node the next stream, see side_fork_mark).
-#ifndef CFFM_EMU
 static struct { bool has; RedJobs jobs; int parity; } g_tail = {false, {}, 0};
 // (the LAST block's tail of a layer backward is not launched here: the optimizer is what waits for those gradients, so they ride in the
 // CFFA's final reduction launch on the caller's stream, in front of everything else that follows the last ln_pool_bwd -- layer_backward_impl)
@@ -1655,14 +1483,9 @@ static int tail_flush(hipStream_t st) {
     }
     return 0;
 }
-#else
-static int tail_flush(hipStream_t) { return 0; }
-#endif
 static void tail_reset() {      // entry of a layer backward: nothing of a previous (failed) call is left to launch or to wait for
-#ifndef CFFM_EMU
     g_tail.has = false;
     for (int i = 0; i < 2; ++i) g_side.dw_pending[i] = g_side.bias_pending[i] = g_side.tail_pending[i] = false;   // (a call that returned normally ended in side_join_all)
-#endif
 }
 int cffm_block_backward(const cffm_geom* g, const cffm_block_params* p, const cffm_block_grads* gr,
                         const float* x_ref, long ref_bs, const float* x_tgt, long tgt_bs, const int* key_src,
@@ -1708,7 +1531,6 @@ static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, c
     hipStream_t st = (hipStream_t)stream;
     hipStream_t sa = st;
     side_init(st);
-#ifndef CFFM_EMU
     if (g_side.tail_pending[g_red_parity]) {    // the reduction that last read this scope's record buffer (two blocks ago)
         side_wait(st, g_side.tail_done[g_red_parity]);
         g_side.tail_pending[g_red_parity] = false;
@@ -1718,7 +1540,6 @@ static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, c
         side_wait(st, g_side.dw_done[par]);
         g_side.dw_pending[par] = false;
     }
-#endif
     const int one_group = dw_one_group(st);
     if (!one_group) {
         // the grouped form (chosen under stream capture) needs larger partial slabs than the split form: size the side scratch for it
@@ -1782,12 +1603,10 @@ static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, c
     int ng;
     {
         PROF(ST_ATTN_BWD);
-#ifndef CFFM_EMU
         if (g_side.bias_pending[par]) {   // the bias-gradient tile sum of two blocks ago still owns this set's tile buffer / dbiasT
             side_wait(st, g_side.bias_done[par]);
             g_side.bias_pending[par] = false;
         }
-#endif
         TRY(attn_bwd_fused(g, ws + L.qkv, key_src, q_dst, (const h16*)(ws + L.bias), ws + L.ao, dao, ws + L.lse, dqkv, scratch + S.dkvp, &dbp, &ng, par, stream));
         TRY(attn_bwd_gather(g, inv_ptr, inv_idx, scratch + S.dkvp, dqkv, stream));
     }
@@ -1851,12 +1670,10 @@ static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, c
     const bool side_late = stream_dw && one_group;
     if (!side_late) TRY(side_b());
     if (!side_late && (!one_group || dx_tgt == dout)) side_join(sa, st, 0);    // fc2's weight gradient has read dout before an in-place ln_pool_bwd overwrites it
-#ifndef CFFM_EMU
     if (g_side.dw_pending[par ^ 1] && g_side.dw_dout[par ^ 1] == dx_tgt) {   // (depth >= 3: the block before still reads its dout = our dx_tgt)
         side_wait(st, g_side.dw_done[par ^ 1]);
         g_side.dw_pending[par ^ 1] = false;
     }
-#endif
     // CFFA, target frame: dx_tgt for the next block + this block's target records.  The reference frames of every block of the range
     // follow in ONE pass at its end (cffa_finish): they need this block's pooled-cell rows of dzall and nothing else.
     TRY(ln_pool_bwd_tgt(g, x_tgt, tgt_bs, p->norm1_w, p->norm1_b, ws + L.M, ws + L.mean1, ws + L.rstd1, dzall, dx1, dx_tgt, dtgt_bs, cffa.rec,
@@ -1864,7 +1681,6 @@ static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, c
     if (side_late) TRY(side_b());
     // the record reductions (every block-partial record of this backward except the CFFA's is written by now):
     // parameter gradients only -> side stream (branch 3); the caller's stream then waits for the side stream once
-#ifndef CFFM_EMU
     if (defer && sb != st && s1 != st && g_side.on) {
         if (g_tail.has) TRY(tail_flush(st));    // (an earlier block's tail nobody has launched yet: before its slot is reused)
         side_fork_mark(st, 3);
@@ -1878,13 +1694,11 @@ static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, c
         g_side.bias_pending[par] = true;
         return 0;
     }
-#endif
     hipStream_t s3 = side_fork(st, 3);
     if (sb != st && s3 != st) side_order(sb, s3);     // (behind the block's side work, as in tail_flush)
     if (s1 != st && s3 != st && s1 != s3) side_order(s1, s3);   // (four side streams: branch 1 joins through branch 3)
     reductions.finish_on(s3);
     CHECK_LAUNCH("block_backward reductions");
-#ifndef CFFM_EMU
     if (defer && sb != st && s3 != st) {
         // (no wait for the weight-gradient GEMMs: the next block works in the other scratch set; whoever reuses THIS set, or writes
         //  the `dout` they read, waits for dw_done[par] then)
@@ -1896,8 +1710,6 @@ static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, c
         g_side.tail_pending[g_red_parity] = true;
         return 0;
     }
-#endif
-    (void)defer;
     side_mark(s3, st, 1);
     side_join(s3, st, 1);    // the caller's stream owns every gradient (and the scratch operands) again
     if (sb != st && sb != s3) { side_mark(sb, st, 0); side_join(sb, st, 0); }   // ... on both side streams
@@ -2061,10 +1873,8 @@ static int span_taps(int in, int out) {
 }
 static int upce_lds(const void* kernel, size_t bytes, const char* who) {
     if (bytes > 160 * 1024) return fail(-1, "%s: the low-resolution tile needs %zu bytes of LDS", who, bytes);
-#ifndef CFFM_EMU
-    if (bytes > 65536 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-        return fail(-2, "%s: cannot reserve %zu bytes of LDS", who, bytes);
-#endif
+    int have = 0;      // (the size changes with the geometry: asked at every call)
+    if (bytes > 65536 && !lds_grant(have, {{kernel, (int)bytes}})) return fail(-2, "%s: cannot reserve %zu bytes of LDS", who, bytes);
     return 0;
 }
 long cffm_upce_blocks(int M, int H, int W) {
@@ -2362,12 +2172,8 @@ int cffm_layer_forward_rows(const cffm_geom* g, int depth, const cffm_block_para
         const long tgt_bs = (i == 0) ? 4 * img : img;
         TRY(block_forward_impl(g, &params[i], x_rows, 4 * img, tgt, tgt_bs, key_src, q_dst, ws, scratch, stream));
     }
-#ifdef CFFM_EMU
-    memcpy(y_rows, blk0 + (long)(depth - 1) * L.total + L.x2, (size_t)g->B * img * sizeof(float));
-#else
     REQUIRE(hipMemcpyAsync(y_rows, blk0 + (long)(depth - 1) * L.total + L.x2, (size_t)g->B * img * sizeof(float), hipMemcpyDeviceToDevice,
                            (hipStream_t)stream) == hipSuccess, "layer_forward_rows: copy failed");
-#endif
     return 0;
 }
 // dy_rows [B,HW,256] -> dx_rows [B,4,HW,256] and every parameter gradient; x_rows as given to cffm_layer_forward_rows
@@ -2396,12 +2202,10 @@ int cffm_layer_backward_rows(const cffm_geom* g, int depth, const cffm_block_par
     }
     // the reference frames of every block in one pass + the CFFA parameter gradients, then the last block's parameter-gradient tail
     RedJobs* tail_jobs = nullptr;
-#ifndef CFFM_EMU
     if (g_tail.has) {     // the last block's record reductions ride in the CFFA's final reduction launch
         g_tail.has = false;
         tail_jobs = &g_tail.jobs;
     }
-#endif
     TRY(cffa_finish(g, depth, params, grads, depth - 1, 0, blk0, L.total, x_rows, 4 * img, dx_rows, 4 * img, 0, stream, tail_jobs));
     side_join_all((hipStream_t)stream);
     return 0;
@@ -2443,9 +2247,7 @@ static int layer_forward_impl(const cffm_geom* g, int depth, const cffm_block_pa
         g_prep_join.pending = sd != st;      // joined behind the first block's ln_pool_fwd (block_forward_impl)
         g_prep_join.side = sd;
     }
-#ifndef CFFM_EMU
     g_side.used = 0;   // (that was this call's only side branch, joined here)
-#endif
     for (int i = 0; i < depth; ++i) {
         float* ws = blk0 + (long)i * L.total;
         const float* tgt = (i == 0) ? xs + 3 * img : blk0 + (long)(i - 1) * L.total + L.x2;
@@ -2505,17 +2307,9 @@ long cffm_layer_prepared_floats(int depth) { return depth < 1 ? -1 : depth * pre
 long cffm_layer_infer_ws_floats(const cffm_geom* g) { return (!g || g->B < 1 || g->HW < 1 || g->RC < 1) ? -1 : infer_ws_layout(g).total; }
 
 static int infer_lds_grant() {
-#ifndef CFFM_EMU
-    static bool granted = false;
-    if (!granted) {
-        if (hipFuncSetAttribute((const void*)k_mlp_fwd<MLP_MT, MLP_D, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PNL_FUSED_LDS(MLP_MT)) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_panel_gemm<2, 6, 2, 4, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, PNL_LDS(2)) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_panel_gemm<3, 6, 2, 4, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, PNL_LDS(3)) != hipSuccess)
-            return -1;
-        granted = true;
-    }
-#endif
-    return 0;
+    static int lds_have = 0;
+    return lds_grant(lds_have, {{(const void*)k_mlp_fwd<MLP_MT, MLP_D, true>, PNL_FUSED_LDS(MLP_MT)}, {(const void*)k_panel_gemm<2, 6, 2, 4, true, 3>, PNL_LDS(2)},
+                                {(const void*)k_panel_gemm<3, 6, 2, 4, true, 3>, PNL_LDS(3)}}) ? 0 : -1;
 }
 // Panel height of the inference Mlp kernel.  The training choice (MLP_MT = 2: 32 rows) leaves more than half of the 256 CUs idle when a
 // call has under 4096 rows (B = 1 on the 60 x 60 grid: 113 workgroups); 16-row panels then still fit one round (225 workgroups).  Measured
@@ -2673,12 +2467,10 @@ static int layer_backward_impl(const cffm_geom* g, int depth, const cffm_block_p
     // walks the layer block by block (data-parallel training, BlockwiseReducer) gets a pass per block, accumulating into dx_ref, so
     // that every block's gradient slice is complete when its range returns.
     RedJobs* tail_jobs = nullptr;
-#ifndef CFFM_EMU
     if (last_block == 0 && g_tail.has) {     // the last block's record reductions ride in the CFFA's final reduction launch
         g_tail.has = false;
         tail_jobs = &g_tail.jobs;
     }
-#endif
     TRY(cffa_finish(g, depth, params, grads, first_block, last_block, blk0, L.total, xs, 4 * img, dxs, 4 * img, first_block != depth - 1, stream, tail_jobs));
     // (dy_full: the upstream gradient of the whole [B,4,C,H,W] output -- its pass-through frames 0..2 join dx in the same pass)
     // (so the last block's parameter-gradient tail stays on the caller's stream, in front of the output transpose: no fork behind the last
@@ -2737,14 +2529,8 @@ static int km_check(const char* who, long N, int K) {
 template <int KT>
 static int km_run(const float* x, int N, int K, int iters, float* centers, int* labels, int* counts, char* ws, const KmPlan& p, hipStream_t st) {
     const size_t lds = (size_t)km_step_lds(KT, p.tpw);
-#ifndef CFFM_EMU
-    static size_t granted = 0;
-    if (lds > granted) {
-        REQUIRE(hipFuncSetAttribute((const void*)k_km_step<KT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)km_step_lds(KT, KM_MAX_TPW)) == hipSuccess,
-                "kmeans: LDS grant failed");
-        granted = (size_t)km_step_lds(KT, KM_MAX_TPW);
-    }
-#endif
+    static int lds_have = 0;      // (granted for the most tiles per wave a plan can ask for: lds never exceeds it)
+    REQUIRE(lds_grant(lds_have, {{(const void*)k_km_step<KT>, km_step_lds(KT, KM_MAX_TPW)}}), "kmeans: LDS grant failed");
     f32x4* frags = (f32x4*)ws;
     float* partial = (float*)(ws + p.frag_b);
     int* pcount = (int*)(ws + p.frag_b + p.part_b);
@@ -2863,7 +2649,6 @@ static DwgGeom dwg_plan(int M, int H, int W, int C, int xr, long lanes, int per_
 }
 #define DWG_FWD_LANES (2048L * 256)     // forward and dh: up to 2048 workgroups of 256 lanes
 #define DWG_BWD1_LANES (1024L * 256)    // first backward pass: up to 1024 workgroups, each leaving a 10 KB slab of partial sums
-static bool dwg_aligned(const void* p) { return p && (uintptr_t)p % 16 == 0; }
 // (checked arguments -> the launch: shared with the MiT stage call)
 static void dwg_fwd_launch(const float* h, const float* w, const float* b, float* out, int M, int H, int W, int C, hipStream_t st) {
     const DwgGeom G = dwg_plan(M, H, W, C, DWG_XR, DWG_FWD_LANES, 1);
@@ -2872,7 +2657,7 @@ static void dwg_fwd_launch(const float* h, const float* w, const float* b, float
 extern "C" {
 int cffm_dwconv_gelu_fwd(const float* h, const float* w, const float* b, float* out, int M, int H, int W, int C, void* stream) {
     TRY(dwg_check("dwconv_gelu_fwd", M, H, W, C));
-    REQUIRE(dwg_aligned(h) && dwg_aligned(w) && dwg_aligned(b) && dwg_aligned(out), "dwconv_gelu_fwd: h / w / b / out must be non-null and 16-byte aligned");
+    REQUIRE(aligned16(h) && aligned16(w) && aligned16(b) && aligned16(out), "dwconv_gelu_fwd: h / w / b / out must be non-null and 16-byte aligned");
     dwg_fwd_launch(h, w, b, out, M, H, W, C, (hipStream_t)stream);
     CHECK_LAUNCH("dwconv_gelu_fwd");
     return 0;
@@ -2885,8 +2670,8 @@ long cffm_dwconv_gelu_bwd_workspace_bytes(int M, int H, int W, int C) {
 int cffm_dwconv_gelu_bwd(const float* h, const float* w, const float* b, const float* dout, float* dh, float* dw, float* db,
                          void* workspace, int M, int H, int W, int C, void* stream) {
     TRY(dwg_check("dwconv_gelu_bwd", M, H, W, C));
-    REQUIRE(dwg_aligned(h) && dwg_aligned(w) && dwg_aligned(b) && dwg_aligned(dout) && dwg_aligned(dh) && dwg_aligned(dw) && dwg_aligned(db) &&
-            dwg_aligned(workspace), "dwconv_gelu_bwd: h / w / b / dout / dh / dw / db / workspace must be non-null and 16-byte aligned");
+    REQUIRE(aligned16(h) && aligned16(w) && aligned16(b) && aligned16(dout) && aligned16(dh) && aligned16(dw) && aligned16(db) &&
+            aligned16(workspace), "dwconv_gelu_bwd: h / w / b / dout / dh / dw / db / workspace must be non-null and 16-byte aligned");
     const DwgGeom G1 = dwg_plan(M, H, W, C, DWG_XR_BWD, DWG_BWD1_LANES, 4);
     const DwgGeom G2 = dwg_plan(M, H, W, C, DWG_XR, DWG_FWD_LANES, 1);
     float* g = (float*)workspace;                              // [M][H][W][C]
@@ -2922,7 +2707,6 @@ static int sra_chunks(int B, int N, int Nk, int heads, int* tpc) {
 static long sra_delta_floats(int B, int N, int heads) { return ((long)B * heads * N + 3) / 4 * 4; }
 // two query tiles per wave halve the K / V traffic; one when that leaves fewer than two workgroups per compute unit
 static bool sra_wide(int B, int N, int heads) { return (long)B * heads * ((N + 127) / 128) >= 512; }
-static bool sra_aligned(const void* p) { return p && (uintptr_t)p % 16 == 0; }
 // (checked arguments -> the launch: shared with the MiT stage call)
 static void sra_fwd_launch(const float* q, const float* kv, float* out, float* lse, int B, int N, int Nk, int heads, int hd, float scale, hipStream_t st) {
     const unsigned gz = (unsigned)(B * heads);
@@ -2934,7 +2718,7 @@ static void sra_fwd_launch(const float* q, const float* kv, float* out, float* l
 extern "C" {
 int cffm_sra_attn_fwd(const float* q, const float* kv, float* out, float* lse, int B, int N, int Nk, int heads, int hd, float scale, void* stream) {
     TRY(sra_check("sra_attn_fwd", B, N, Nk, heads, hd, scale));
-    REQUIRE(sra_aligned(q) && sra_aligned(kv) && sra_aligned(out) && (uintptr_t)lse % 16 == 0,
+    REQUIRE(aligned16(q) && aligned16(kv) && aligned16(out) && (uintptr_t)lse % 16 == 0,
             "sra_attn_fwd: q / kv / out must be non-null and q / kv / out / lse 16-byte aligned");
     sra_fwd_launch(q, kv, out, lse, B, N, Nk, heads, hd, scale, (hipStream_t)stream);
     CHECK_LAUNCH("sra_attn_fwd");
@@ -2949,8 +2733,8 @@ long cffm_sra_attn_bwd_workspace_bytes(int B, int N, int Nk, int heads, int hd) 
 int cffm_sra_attn_bwd(const float* q, const float* kv, const float* out, const float* lse, const float* dout, float* dq, float* dkv,
                       void* workspace, int B, int N, int Nk, int heads, int hd, float scale, void* stream) {
     TRY(sra_check("sra_attn_bwd", B, N, Nk, heads, hd, scale));
-    REQUIRE(sra_aligned(q) && sra_aligned(kv) && sra_aligned(out) && sra_aligned(lse) && sra_aligned(dout) && sra_aligned(dq) && sra_aligned(dkv) &&
-            sra_aligned(workspace), "sra_attn_bwd: q / kv / out / lse / dout / dq / dkv / workspace must be non-null and 16-byte aligned");
+    REQUIRE(aligned16(q) && aligned16(kv) && aligned16(out) && aligned16(lse) && aligned16(dout) && aligned16(dq) && aligned16(dkv) &&
+            aligned16(workspace), "sra_attn_bwd: q / kv / out / lse / dout / dq / dkv / workspace must be non-null and 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const unsigned gz = (unsigned)(B * heads);
     const double c = (double)scale * 1.4426950408889634;
@@ -2986,7 +2770,6 @@ static int srln_check(const char* who, int B, int H, int W, int C, int s, float 
     G->B = B; G->H = H; G->W = W; G->C = C; G->Ho = H / s; G->Wo = W / s; G->M = B * G->Ho * G->Wo;
     return 0;
 }
-static bool srln_aligned(const void* p) { return p && (uintptr_t)p % 16 == 0; }
 static long srln_dz_floats(const SrGeom& G) { return (long)G.M * G.C; }                       // (a multiple of 16)
 static int srln_row_blocks(const SrGeom& G) { return (G.M + 15) / 16; }
 // column tiles per wave of k_srln_fwd: the largest of 5, 4, 2, 1 that divides C / 16
@@ -3023,7 +2806,7 @@ int cffm_sr_ln_fwd(const float* x, const float* w, const float* b, const float* 
                    int B, int H, int W, int C, int s, float eps, void* stream) {
     SrGeom G;
     TRY(srln_check("sr_ln_fwd", B, H, W, C, s, eps, &G));
-    REQUIRE(srln_aligned(x) && srln_aligned(w) && srln_aligned(b) && srln_aligned(gamma) && srln_aligned(beta) && srln_aligned(out) &&
+    REQUIRE(aligned16(x) && aligned16(w) && aligned16(b) && aligned16(gamma) && aligned16(beta) && aligned16(out) &&
             (uintptr_t)z % 16 == 0 && (uintptr_t)stats % 16 == 0,
             "sr_ln_fwd: x / w / b / gamma / beta / out must be non-null and all pointers 16-byte aligned");
     REQUIRE(!z == !stats, "sr_ln_fwd: z and stats must both be given or both be null");
@@ -3041,8 +2824,8 @@ int cffm_sr_ln_bwd(const float* x, const float* w, const float* gamma, const flo
                    void* stream) {
     SrGeom G;
     TRY(srln_check("sr_ln_bwd", B, H, W, C, s, eps, &G));
-    REQUIRE(srln_aligned(x) && srln_aligned(w) && srln_aligned(gamma) && srln_aligned(z) && srln_aligned(stats) && srln_aligned(dout) &&
-            srln_aligned(dx) && srln_aligned(dw) && srln_aligned(db) && srln_aligned(dgamma) && srln_aligned(dbeta) && srln_aligned(workspace),
+    REQUIRE(aligned16(x) && aligned16(w) && aligned16(gamma) && aligned16(z) && aligned16(stats) && aligned16(dout) &&
+            aligned16(dx) && aligned16(dw) && aligned16(db) && aligned16(dgamma) && aligned16(dbeta) && aligned16(workspace),
             "sr_ln_bwd: x / w / gamma / z / stats / dout / dx / dw / db / dgamma / dbeta / workspace must be non-null and 16-byte aligned");
     float* dz = (float*)workspace;                               // [M][C]
     float* part = dz + srln_dz_floats(G);                        // [row blocks][3][C]
@@ -3056,7 +2839,6 @@ int cffm_sr_ln_bwd(const float* x, const float* w, const float* gamma, const flo
 
 // ------------------------------------------------------------------------------------------- LayerNorm of token rows at any width + one MiT stage per call (mitln_kernels.h)
 }  // extern "C"
-static bool mln_aligned(const void* p) { return p && (uintptr_t)p % 16 == 0; }
 static int mln_check(const char* who, int C, float eps) {
     REQUIRE(C >= 16 && C <= 512 && C % 4 == 0, "%s: C=%d must be a multiple of 4 in 16..512", who, C);
     REQUIRE(eps >= 0.f && eps < INFINITY, "%s: eps %g must be finite and not negative", who, (double)eps);
@@ -3142,14 +2924,14 @@ extern "C" {
 int cffm_ln_rows(const float* x, const float* gamma, const float* beta, float* out, long M, int C, float eps, void* stream) {
     TRY(mln_check("ln_rows", C, eps));
     REQUIRE(M >= 1 && M * C < (1L << 31), "ln_rows: M=%ld rows of C=%d: M must be at least 1 and M*C below 2^31", M, C);
-    REQUIRE(mln_aligned(x) && mln_aligned(gamma) && mln_aligned(beta) && mln_aligned(out), "ln_rows: x / gamma / beta / out must be non-null and 16-byte aligned");
+    REQUIRE(aligned16(x) && aligned16(gamma) && aligned16(beta) && aligned16(out), "ln_rows: x / gamma / beta / out must be non-null and 16-byte aligned");
     mln_launch(0, (hipStream_t)stream, x, gamma, beta, out, M, 0, C, 1, eps);
     CHECK_LAUNCH("ln_rows");
     return 0;
 }
 int cffm_nchw_ln_rows(const float* x_nchw, const float* gamma, const float* beta, float* out_rows, int B, int C, int H, int W, float eps, void* stream) {
     TRY(mln_check_map("nchw_ln_rows", B, C, H, W, eps));
-    REQUIRE(mln_aligned(x_nchw) && mln_aligned(gamma) && mln_aligned(beta) && mln_aligned(out_rows),
+    REQUIRE(aligned16(x_nchw) && aligned16(gamma) && aligned16(beta) && aligned16(out_rows),
             "nchw_ln_rows: x_nchw / gamma / beta / out_rows must be non-null and 16-byte aligned");
     mln_launch(1, (hipStream_t)stream, x_nchw, gamma, beta, out_rows, (long)B * H * W, B, C, H * W, eps);
     CHECK_LAUNCH("nchw_ln_rows");
@@ -3157,7 +2939,7 @@ int cffm_nchw_ln_rows(const float* x_nchw, const float* gamma, const float* beta
 }
 int cffm_ln_rows_nchw(const float* x_rows, const float* gamma, const float* beta, float* out_nchw, int B, int C, int H, int W, float eps, void* stream) {
     TRY(mln_check_map("ln_rows_nchw", B, C, H, W, eps));
-    REQUIRE(mln_aligned(x_rows) && mln_aligned(gamma) && mln_aligned(beta) && mln_aligned(out_nchw),
+    REQUIRE(aligned16(x_rows) && aligned16(gamma) && aligned16(beta) && aligned16(out_nchw),
             "ln_rows_nchw: x_rows / gamma / beta / out_nchw must be non-null and 16-byte aligned");
     mln_launch(2, (hipStream_t)stream, x_rows, gamma, beta, out_nchw, (long)B * H * W, B, C, H * W, eps);
     CHECK_LAUNCH("ln_rows_nchw");
@@ -3173,19 +2955,19 @@ int cffm_mit_stage_infer(const cffm_mit_stage_cfg* c, const cffm_mit_block_param
     MitWs W;
     TRY(mit_cfg_check("mit_stage_infer", c, &W));
     REQUIRE(blocks, "mit_stage_infer: null block parameters");
-    REQUIRE(mln_aligned(embed_g) && mln_aligned(embed_b) && mln_aligned(out_g) && mln_aligned(out_b) && mln_aligned(conv_nchw) &&
-            mln_aligned(out_nchw) && mln_aligned(ws),
+    REQUIRE(aligned16(embed_g) && aligned16(embed_b) && aligned16(out_g) && aligned16(out_b) && aligned16(conv_nchw) &&
+            aligned16(out_nchw) && aligned16(ws),
             "mit_stage_infer: embed_g / embed_b / out_g / out_b / conv_nchw / out_nchw / ws must be non-null and 16-byte aligned");
     REQUIRE(conv_nchw != out_nchw, "mit_stage_infer: input and output must not alias");
     const int s = c->sr_ratio;
     for (int i = 0; i < c->depth; ++i) {
         const cffm_mit_block_params& p = blocks[i];
         const float* need[] = {p.n1_g, p.n1_b, p.q_w, p.kv_w, p.proj_w, p.proj_b, p.n2_g, p.n2_b, p.fc1_w, p.fc1_b, p.dw_w, p.dw_b, p.fc2_w, p.fc2_b};
-        for (const float* t : need) REQUIRE(mln_aligned(t), "mit_stage_infer: block %d: a parameter is null or not 16-byte aligned", i);
+        for (const float* t : need) REQUIRE(aligned16(t), "mit_stage_infer: block %d: a parameter is null or not 16-byte aligned", i);
         REQUIRE((uintptr_t)p.q_b % 16 == 0 && (uintptr_t)p.kv_b % 16 == 0, "mit_stage_infer: block %d: q_b / kv_b not 16-byte aligned", i);
         const float* sr[] = {p.sr_w, p.sr_b, p.srn_g, p.srn_b};
         for (const float* t : sr)
-            REQUIRE(s > 1 ? mln_aligned(t) : !t, "mit_stage_infer: block %d: sr_w / sr_b / srn_g / srn_b must be %s", i,
+            REQUIRE(s > 1 ? aligned16(t) : !t, "mit_stage_infer: block %d: sr_w / sr_b / srn_g / srn_b must be %s", i,
                     s > 1 ? "non-null and 16-byte aligned (sr_ratio > 1)" : "null (sr_ratio == 1)");
     }
     hipStream_t st = (hipStream_t)stream;

@@ -6,6 +6,22 @@
 #include "gemm_kernels.h"
 #include "dws_kernels.h"
 
+#include <initializer_list>
+
+// More than 64 KiB of dynamic LDS has to be granted per kernel.  Every site that launches such kernels keeps one `have` (a static, 0 at
+// first: the largest size it has been granted) and asks here before the launch: the kernels are granted, in order, when the site asks
+// for more than it has -- once for a fixed size, again when a larger one comes.  false: the runtime refused (`have` stays).
+struct LdsAsk { const void* kernel; int bytes; };
+static bool lds_grant(int& have, std::initializer_list<LdsAsk> asks) {
+    int most = 0;
+    for (const LdsAsk& a : asks) most = a.bytes > most ? a.bytes : most;
+    if (most <= have) return true;
+    for (const LdsAsk& a : asks)
+        if (hipFuncSetAttribute(a.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, a.bytes) != hipSuccess) return false;
+    have = most;
+    return true;
+}
+
 // ---- hand-written split-bf16 MFMA path (default) -------------------------------------------------------------
 float* lib_scratch(size_t nfloats);   // cffm_hip.hip: library-owned device scratch (grows on demand)
 __global__ void k_sum_splits(const float* __restrict__ part, int nsplit, long n, float* __restrict__ out);
@@ -23,22 +39,10 @@ static int gemm_split_launch(const float* A, const float* B, float* C, int M, in
         if (!out) return -1;
     }
     const long b128 = (long)((N + 127) / 128) * ((M + 127) / 128) * ksplit;
-#ifdef CFFM_EMU
-#define GEMM_BIG_LDS(BM_, BN_, BK_, PF_)
-#else   // more than 64 KiB of dynamic LDS has to be granted per kernel, once
-#define GEMM_BIG_LDS(BM_, BN_, BK_, PF_)                                                                                      \
-    if (GEMM_LDS(BM_, BN_, BK_) > 65536) {                                                                                    \
-        static bool granted = false;                                                                                          \
-        if (!granted) {                                                                                                       \
-            if (hipFuncSetAttribute((const void*)k_gemm_split<BM_, BN_, BK_, A_T, B_T, EPI, PF_, A_PRE, B_PRE>,                              \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS(BM_, BN_, BK_)) != hipSuccess)       \
-                return -1;                                                                                                    \
-            granted = true;                                                                                                   \
-        }                                                                                                                     \
-    }
-#endif
 #define GEMM_GO(BM_, BN_, BK_, PF_) do {                                                                                               \
-    GEMM_BIG_LDS(BM_, BN_, BK_, PF_)                                                                                                   \
+    static int lds_have = 0;                                                                                                           \
+    if (GEMM_LDS(BM_, BN_, BK_) > 65536 &&                                                                                             \
+        !lds_grant(lds_have, {{(const void*)k_gemm_split<BM_, BN_, BK_, A_T, B_T, EPI, PF_, A_PRE, B_PRE>, GEMM_LDS(BM_, BN_, BK_)}})) return -1; \
     CFFM_LAUNCH((k_gemm_split<BM_, BN_, BK_, A_T, B_T, EPI, PF_, A_PRE, B_PRE>), ((unsigned)(((N + BN_ - 1) / BN_) * ((M + BM_ - 1) / BM_) * ksplit)), (256), \
                 GEMM_LDS(BM_, BN_, BK_), st, A, \
                 B, out, M, N, K, lda, ldb, ldc, klen, split_stride, bias, aux, aux2); } while (0)
@@ -160,14 +164,8 @@ static int gemm_tn_group_split(const GemmTN* pr, int n, hipStream_t st, const Ge
     }
     for (int p = n; p < GEMM_GROUP_MAX; ++p) { G.A[p] = G.B[p] = nullptr; G.C[p] = nullptr; G.M[p] = G.N[p] = 128; G.K[p] = 0; G.wg_end[p] = wg; G.a_pre[p] = G.b_pre[p] = 0; G.b_bias[p] = nullptr; }
     G.klen = klen; G.n = n;
-#ifndef CFFM_EMU
-    static bool granted = false;
-    if (!granted) {
-        if (hipFuncSetAttribute((const void*)k_gemm_group_tt, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS(128, 128, 32) + 16384) != hipSuccess)
-            return -1;
-        granted = true;
-    }
-#endif
+    static int lds_have = 0;
+    if (!lds_grant(lds_have, {{(const void*)k_gemm_group_tt, GEMM_LDS(128, 128, 32) + 16384}})) return -1;
     // 8 KB more LDS than the tiles need: ONE workgroup of the group per CU instead of two.  Two fill a CU's LDS exactly, and the CFFA
     // backward that runs beside the group in a block backward (69 KB per workgroup) then finds no slot until the group's workgroups
     // finish; with one per CU the two kernels really share the CUs: the group 62 -> 70 us, k_ln_pool_bwd 85 -> 77, step 0.717-0.730 ->
@@ -241,13 +239,8 @@ static int dw_group_stream(const GemmTN* pr, int n, hipStream_t st, float* part,
     }
     for (int p = n; p < DWS_MAX; ++p) { G.DY[p] = G.X[p] = nullptr; G.C[p] = nullptr; G.N[p] = DWS_TO; G.K[p] = DWS_TI; G.KS[p] = 0; G.kw[p] = 1; G.wg_end[p] = wg; }
     G.n = n;
-#ifndef CFFM_EMU
-    static bool granted = false;
-    if (!granted) {
-        if (hipFuncSetAttribute((const void*)k_dw_stream, hipFuncAttributeMaxDynamicSharedMemorySize, DWS_LDS) != hipSuccess) return -1;
-        granted = true;
-    }
-#endif
+    static int lds_have = 0;
+    if (!lds_grant(lds_have, {{(const void*)k_dw_stream, DWS_LDS}})) return -1;
     CFFM_LAUNCH(k_dw_stream, ((unsigned)wg), (256), DWS_LDS, st, G);
     if (after_gemm) after_gemm(st);
     if (nsum) {

@@ -43,6 +43,23 @@ static inline const char* hipGetErrorString(hipError_t) { return "emu"; }
 static inline hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t) { memset(p, v, n); return 0; }
 static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, int, hipStream_t) { memcpy(d, s, n); return 0; }
 #define hipMemcpyDeviceToDevice 3
+// The rest of the runtime the host code calls, as a device WITHOUT extra streams: creating one fails, so the library settles in the
+// state it has for that anyway (cffm_side_streams(0), creation failures: everything on the caller's stream, in order).  Events and
+// waits are then never reached with a second stream; they succeed and do nothing.  Device memory is the heap.
+typedef void* hipEvent_t;
+enum hipStreamCaptureStatus { hipStreamCaptureStatusNone, hipStreamCaptureStatusActive };
+#define hipStreamNonBlocking 1
+#define hipEventDisableTiming 2
+#define hipFuncAttributeMaxDynamicSharedMemorySize 8
+static inline hipError_t hipStreamCreateWithFlags(hipStream_t*, unsigned) { return 1; }
+static inline hipError_t hipStreamIsCapturing(hipStream_t, hipStreamCaptureStatus* s) { *s = hipStreamCaptureStatusNone; return 0; }
+static inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = nullptr; return 0; }
+static inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return 0; }
+static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return 0; }
+static inline hipError_t hipDeviceSynchronize() { return 0; }
+static inline hipError_t hipFuncSetAttribute(const void*, int, int) { return 0; }
+static inline hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n); return *p ? 0 : 2; }
+static inline hipError_t hipFree(void* p) { free(p); return 0; }
 
 namespace emu {
 
