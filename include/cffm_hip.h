@@ -185,6 +185,11 @@ int cffm_mlp_bwd(const float* dout, const float* hraw, const float* b1, const fl
                  const float* rstd2, const float* g2, const float* w2_n, const float* w1_n, const float* wp_n, float* dhs,
                  float* dx1, float* dao, float* dg2, float* dbe2, float* db1, float* db2, float* dbp, long NP, void* stream);
 int cffm_colsum(const float* a, long rows, int cols /* multiple of 4 */, float* out /* overwritten */, void* stream);
+/* added under ABI 13, additive: the block's q|k|v Linear as a stage -- qkv16 [M,768] f16 = x w^T + b with the q third times 32^-0.5, from
+ * x in split-4 storage ([M,256]) and w in fragment order (cffm_panel_pack_weight of w [768,256], form 0).  Each workgroup computes one of
+ * the q / k / v column thirds of a row panel, two workgroups per CU.  x_t (or NULL): also writes the T-frag copy of x
+ * (cffm_tfrag_floats(M, 256) floats, rows past M zero). */
+int cffm_panel_qkv_fwd(const float* x_split4, const float* w_frag, const float* b /*[768]*/, void* qkv16, long M, float* x_t, void* stream);
 
 /* ---- CFFM++ global temporal context (WindowAttention_cluster, pvt/swin_transformer_2d.py:208-262) ---- */
 /* q_raw [B*T,256] = LN(x) Wq^T without bias, kv_raw [B*K,512] = LN(centers) Wkv^T without bias; softmax over the K

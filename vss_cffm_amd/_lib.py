@@ -98,6 +98,7 @@ SIGNATURES = {
     'cffm_linear_bwd_weight_tfrag_group': (ci, [vp, ci, vp]),
     'cffm_colsum': (ci, [vp, cl, ci, vp, vp]),
     'cffm_panel_pack_weight': (ci, [vp, ci, ci, ci, vp, vp]),
+    'cffm_panel_qkv_fwd': (ci, [vp, vp, vp, vp, cl, vp, vp]),
     'cffm_mlp_fwd': (ci, [vp, vp, cl, ci] + [vp] * 15 + [cl, vp]),
     'cffm_mlp_bwd': (ci, [vp] * 18 + [cl, vp]),
     'cffm_block_forward': (ci, [GP, BP, vp, cl, vp, cl, vp, vp, vp, vp, vp]),

@@ -1097,36 +1097,48 @@ static int mlp_lds_grant() {
     static int lds_have = 0;
     return lds_grant(lds_have, {{(const void*)k_mlp_fwd<MLP_MT, MLP_D>, PNL_FUSED_LDS(MLP_MT)}, {(const void*)k_mlp_bwd<MLP_MT, MLP_D>, PNL_FUSED_LDS(MLP_MT)}}) ? 0 : -1;
 }
-// q|k|v Linear and its input gradient as row-panel GEMMs (weights in fragment order): rows per workgroup (32 or 48) chosen so that
-// the grid wastes the least of its last round on 256 CUs
+// The q|k|v input gradient (and the prototype block's q projection) as row-panel GEMMs (weights in fragment order): rows per workgroup
+// (32 or 48) chosen so that the grid wastes the least of its last round on 256 CUs
 static int panel_mt(long M) {
     const long w2 = (M + 31) / 32, w3 = (M + 47) / 48;
     return ((w3 + 255) / 256) * 3 < ((w2 + 255) / 256) * 2 ? 3 : 2;
 }
 extern "C++" {
 template <int MT, int NTW, bool A_PRE, int EPI>
-static int panel_gemm_launch(const float* A, int lda, long M, int K, const float* wf, float* Cout, int ldc, const float* bias, void* aux,
+static int panel_gemm_launch(const float* A, int lda, long M, int K, const float* wf, float* Cout, int ldc, const float* bias,
                              hipStream_t st, float* colrec = nullptr, float* a_t = nullptr) {
     auto kern = k_panel_gemm<MT, NTW, 2, 4, A_PRE, EPI>;
     static int lds_have = 0;
     if (!lds_grant(lds_have, {{(const void*)kern, PNL_LDS(MT)}})) return -1;
-    CFFM_LAUNCH(kern, ((unsigned)((M + 16 * MT - 1) / (16 * MT))), (PNL_THREADS), PNL_LDS(MT), st, A, lda, (int)M, K, (const f32x4*)wf, Cout, ldc, bias, aux, colrec, (f32x4*)a_t);
+    CFFM_LAUNCH(kern, ((unsigned)((M + 16 * MT - 1) / (16 * MT))), (PNL_THREADS), PNL_LDS(MT), st, A, lda, (int)M, K, (const f32x4*)wf, Cout, ldc, bias, colrec, (f32x4*)a_t);
     return 0;
 }
 }  // extern "C++"
 // qkv16[M][768] (f16) = f16((x W^T + b) [q third * 32^-0.5]), x in split-4 storage, W fragment-ordered (forward form)
-// x_t (or NULL): T-frag copy of x for the streaming weight gradient
+// x_t (or NULL): T-frag copy of x for the streaming weight gradient.  One workgroup per (panel, column third), two resident per CU
+// (k_panel_qkv3): rows per panel by the reasoning of panel_mt, on 512 slots and three workgroups per panel
+static int panel_qkv_fwd_mt(long M) {
+    const long w2 = 3 * ((M + 31) / 32), w3 = 3 * ((M + 47) / 48);
+    return ((w3 + 511) / 512) * 3 < ((w2 + 511) / 512) * 2 ? 3 : 2;
+}
+extern "C++" {
+template <int MT>
+static int panel_qkv3_launch(const float* x_s, const float* wf, const float* b, h16* qkv16, long M, hipStream_t st, float* x_t) {
+    const long panels = (M + 16 * MT - 1) / (16 * MT);
+    CFFM_LAUNCH(k_panel_qkv3<MT>, ((unsigned)(24 * ((panels + 7) / 8))), (PNL_THREADS), QKV3_LDS(MT), st, x_s, (int)M, (const f32x4*)wf, b, qkv16, (f32x4*)x_t);
+    return 0;
+}
+}  // extern "C++"
 static int panel_qkv_fwd(const float* x_s, const float* wf, const float* b, h16* qkv16, long M, hipStream_t st, float* x_t = nullptr) {
-    return panel_mt(M) == 3 ? panel_gemm_launch<3, 6, true, 3>(x_s, 256, M, 256, wf, nullptr, 768, b, qkv16, st, nullptr, x_t)
-                            : panel_gemm_launch<2, 6, true, 3>(x_s, 256, M, 256, wf, nullptr, 768, b, qkv16, st, nullptr, x_t);
+    return panel_qkv_fwd_mt(M) == 3 ? panel_qkv3_launch<3>(x_s, wf, b, qkv16, M, st, x_t) : panel_qkv3_launch<2>(x_s, wf, b, qkv16, M, st, x_t);
 }
 // dx[M][256] = dqkv[M][768] W, W fragment-ordered (input-gradient form); colrec (or NULL): panel_qkv_records(M) records of 768
 // column sums of dqkv (the q|k|v bias gradient before its reduction)
 static long panel_qkv_records(long M) { return (M + 16 * panel_mt(M) - 1) / (16 * panel_mt(M)); }
 // dqkv_t (or NULL): T-frag copy of dqkv for the streaming weight gradient
 static int panel_qkv_dx(const float* dqkv, const float* wfn, float* dx, long M, hipStream_t st, float* colrec = nullptr, float* dqkv_t = nullptr) {
-    return panel_mt(M) == 3 ? panel_gemm_launch<3, 2, false, 0>(dqkv, 768, M, 768, wfn, dx, 256, nullptr, nullptr, st, colrec, dqkv_t)
-                            : panel_gemm_launch<2, 2, false, 0>(dqkv, 768, M, 768, wfn, dx, 256, nullptr, nullptr, st, colrec, dqkv_t);
+    return panel_mt(M) == 3 ? panel_gemm_launch<3, 2, false, 0>(dqkv, 768, M, 768, wfn, dx, 256, nullptr, st, colrec, dqkv_t)
+                            : panel_gemm_launch<2, 2, false, 0>(dqkv, 768, M, 768, wfn, dx, 256, nullptr, st, colrec, dqkv_t);
 }
 // (the q|k|v Linear as row panels against the tiled GEMMs: 0.8729 vs 0.8843 ms per step, means of three alternating runs)
 // The block's four weight gradients take one of two forms: the streaming kernel (dws_kernels.h) on operands in T-frag storage, written
@@ -1146,6 +1158,15 @@ int cffm_panel_pack_weight(const float* w, int N, int K, int form, float* w_frag
     REQUIRE(w && w_frag && N >= 16 && K >= 16 && N % 32 == 0 && K % 32 == 0 && (form == 0 || form == 1), "panel_pack_weight: bad arguments");
     CFFM_LAUNCH(k_pnl_pack_weight, ((unsigned)(((long)N * K / 8 + 255) / 256)), (256), 0, (hipStream_t)stream, w, N, K, form, (f32x4*)w_frag);
     CHECK_LAUNCH("panel_pack_weight");
+    return 0;
+}
+
+// the q|k|v Linear of the block as a stage (k_panel_qkv3): x in split-4 storage, w_frag = cffm_panel_pack_weight(w [768][256], form 0)
+int cffm_panel_qkv_fwd(const float* x_split4, const float* w_frag, const float* b, void* qkv16, long M, float* x_t, void* stream) {
+    REQUIRE(x_split4 && w_frag && b && qkv16 && M >= 1 && M < (1L << 21), "panel_qkv_fwd: bad arguments");
+    PROF(ST_GEMM);
+    REQUIRE(!panel_qkv_fwd(x_split4, w_frag, b, (h16*)qkv16, M, (hipStream_t)stream, x_t), "panel_qkv_fwd: launch failed");
+    CHECK_LAUNCH("panel_qkv_fwd");
     return 0;
 }
 
@@ -1295,8 +1316,8 @@ int cffm_gtc_block_forward(const cffm_gtc_params* p, const float* x, const float
     {
         PROF(ST_GEMM);
         float* z_t = ws + W.z_t;
-        const int rc = panel_mt(nt) == 3 ? panel_gemm_launch<3, 2, true, 0>(ws + W.z, 256, nt, 256, wf, ws + W.qraw, 256, nullptr, nullptr, st, nullptr, z_t)
-                                         : panel_gemm_launch<2, 2, true, 0>(ws + W.z, 256, nt, 256, wf, ws + W.qraw, 256, nullptr, nullptr, st, nullptr, z_t);
+        const int rc = panel_mt(nt) == 3 ? panel_gemm_launch<3, 2, true, 0>(ws + W.z, 256, nt, 256, wf, ws + W.qraw, 256, nullptr, st, nullptr, z_t)
+                                         : panel_gemm_launch<2, 2, true, 0>(ws + W.z, 256, nt, 256, wf, ws + W.qraw, 256, nullptr, st, nullptr, z_t);
         REQUIRE(!rc, "gtc_block_forward: q gemm failed");
         REQUIRE(!gemm_nt(ws + W.cn, p->kv_w, ws + W.kvraw, nk, 512, 256, st), "gtc_block_forward: kv gemm failed");
     }
@@ -1334,8 +1355,8 @@ int cffm_gtc_block_backward(const cffm_gtc_params* p, const cffm_gtc_grads* g, c
         float* qrec = red_scratch((size_t)nrec * 256, st);
         REQUIRE(qrec, "gtc_block_backward: scratch allocation failed");
         float* dq_t = ws + W.dq_t;
-        const int rc = mt == 3 ? panel_gemm_launch<3, 2, false, 0>(ws + W.dq, 256, nt, 256, wn, ws + W.dz, 256, nullptr, nullptr, st, qrec, dq_t)
-                               : panel_gemm_launch<2, 2, false, 0>(ws + W.dq, 256, nt, 256, wn, ws + W.dz, 256, nullptr, nullptr, st, qrec, dq_t);
+        const int rc = mt == 3 ? panel_gemm_launch<3, 2, false, 0>(ws + W.dq, 256, nt, 256, wn, ws + W.dz, 256, nullptr, st, qrec, dq_t)
+                               : panel_gemm_launch<2, 2, false, 0>(ws + W.dq, 256, nt, 256, wn, ws + W.dz, 256, nullptr, st, qrec, dq_t);
         REQUIRE(!rc, "gtc_block_backward: q input-gradient gemm failed");
         RedSegs segs;
         segs.nseg = 0;
@@ -2308,8 +2329,7 @@ long cffm_layer_infer_ws_floats(const cffm_geom* g) { return (!g || g->B < 1 || 
 
 static int infer_lds_grant() {
     static int lds_have = 0;
-    return lds_grant(lds_have, {{(const void*)k_mlp_fwd<MLP_MT, MLP_D, true>, PNL_FUSED_LDS(MLP_MT)}, {(const void*)k_panel_gemm<2, 6, 2, 4, true, 3>, PNL_LDS(2)},
-                                {(const void*)k_panel_gemm<3, 6, 2, 4, true, 3>, PNL_LDS(3)}}) ? 0 : -1;
+    return lds_grant(lds_have, {{(const void*)k_mlp_fwd<MLP_MT, MLP_D, true>, PNL_FUSED_LDS(MLP_MT)}}) ? 0 : -1;
 }
 // Panel height of the inference Mlp kernel.  The training choice (MLP_MT = 2: 32 rows) leaves more than half of the 256 CUs idle when a
 // call has under 4096 rows (B = 1 on the 60 x 60 grid: 113 workgroups); 16-row panels then still fit one round (225 workgroups).  Measured

@@ -141,7 +141,8 @@ __device__ __forceinline__ void pnl_pin_vmem() {
 // fused forward) that drains at the HBM write rate (~6.5 B/clk per CU with every CU storing) holds up the B-fragment loads queued behind
 // it, and the matrix pipe idles: measured 44.6 us for the fused forward with the stores in bursts vs 24.4 us without any store.
 struct PnlNoExtra { __device__ __forceinline__ void operator()(int) const {} };
-template <int MT, int NTW, int NT, int D, class Extra = PnlNoExtra>
+// LAST: nothing follows this chunk -- the ring is not refilled past it (`nst` is not read)
+template <int MT, int NTW, int NT, int D, class Extra = PnlNoExtra, bool LAST = false>
 __device__ __forceinline__ void pnl_chunk_mma(f32x4 (&acc)[NTW][MT], PnlRing<NT, D>& ring, const bf16* __restrict__ Ahi,
                                               const bf16* __restrict__ Alo, const PnlStream& st, int jt0, int ks0, int l15, int g,
                                               // where the stream goes after this chunk (its first D-1 steps are prefetched from here)
@@ -160,7 +161,7 @@ __device__ __forceinline__ void pnl_chunk_mma(f32x4 (&acc)[NTW][MT], PnlRing<NT,
         // the slot consumed by the previous step takes step sc + D - 1 (of this chunk, or of what follows it)
         const int sn = sc + D - 1, slot_n = sn % D;
         if (sn < SC) pnl_ring_load<NT, D>(ring, slot_n, st, jt0 + (sn / 8) * NT, ks0 + sn % 8);
-        else pnl_ring_load<NT, D>(ring, slot_n, nst, njt0 + ((sn - SC) / 8) * NT, nks0 + (sn - SC) % 8);
+        else if (!LAST) pnl_ring_load<NT, D>(ring, slot_n, nst, njt0 + ((sn - SC) / 8) * NT, nks0 + (sn - SC) % 8);
         extra(sc);
         pnl_pin_vmem();
         if (sc + 1 < SC) {
@@ -245,12 +246,11 @@ __device__ __forceinline__ uint32_t pnl_l2_touch(const void* w, long bytes, int 
 //  no difference measured, 0.719-0.727 ms per step with, 0.715-0.731 without)
 // ---- plain panel GEMM: C[M][N] = A[M][K] W^T (+ bias), W in fragment order (NT or NN form decides what "W^T" means) ---------
 // grid = ceil(M / (16 MT)) workgroups of 512 threads; N = 8 waves x NTW tiles x 16; K a multiple of 256.
-// EPI: 0 plain fp32 (+bias) | 3 q|k|v: nothing in C; aux (h16 [M][ldc]) = f16(raw + bias), features < 256 (the q third) also times
-//      32^-0.5 -- what the attention kernels read (cffm_transformer.py:374, :528)
+// EPI: 0 plain fp32 (+bias) -- the only epilogue left: the q|k|v forward, once EPI 3 here, is k_panel_qkv3 below
 template <int MT, int NTW, int NT, int D, bool A_PRE, int EPI>
 __global__ void __launch_bounds__(PNL_THREADS) k_panel_gemm(const float* __restrict__ A, int lda, int M, int K, const f32x4* __restrict__ Wf,
                                                             float* __restrict__ C, int ldc, const float* __restrict__ bias,
-                                                            void* __restrict__ aux = nullptr, float* __restrict__ colrec = nullptr,
+                                                            float* __restrict__ colrec = nullptr,
                                                             f32x4* __restrict__ a_t = nullptr /* T-frag copy of A [M][K] (pnl_tfrag_store), or NULL */) {
     CFFM_DYN_SMEM(smem);
     bf16* img = (bf16*)smem;     // [buf][hi | lo][16 MT][256]
@@ -316,11 +316,11 @@ __global__ void __launch_bounds__(PNL_THREADS) k_panel_gemm(const float* __restr
     // epilogue: acc[t][i][r] = C[m0 + 16 i + l15][16 (jt0 + t) + 4 g + r]
     {
         // Through LDS: a lane of the MFMA C layout owns 4 consecutive features of one row, so a store instruction writes 16 rows x 32 B
-        // (f16 q|k|v) or x 64 B (fp32) -- short runs that drain at about half the rate of whole rows (the q|k|v forward spent 8 of its
-        // 20 us on its 15.9 MB of stores).  The panel's output [16 MT rows][N] is assembled in the (now free) image buffers, rows padded by
+        // (fp32) -- short runs that drain at about half the rate of whole rows (the q|k|v forward, then a form of this kernel, spent 8 of
+        // its 20 us on its 15.9 MB of 32 B f16 runs).  The panel's output [16 MT rows][N] is assembled in the (now free) image buffers, rows padded by
         // 32 B against bank conflicts, and leaves as 16-byte units in row order: every wave instruction writes 1 KiB of one or two rows.
-        static_assert(EPI == 0 || EPI == 3, "k_panel_gemm epilogue");
-        constexpr int ESZ = (EPI == 3) ? 2 : 4, NCOL = PNL_WAVES * NTW * 16, ROWB = NCOL * ESZ + 32, UPR = NCOL * ESZ / 16;
+        static_assert(EPI == 0, "k_panel_gemm epilogue");
+        constexpr int ESZ = 4, NCOL = PNL_WAVES * NTW * 16, ROWB = NCOL * ESZ + 32, UPR = NCOL * ESZ / 16;
         static_assert(16 * MT * ROWB <= PNL_LDS(MT), "panel output does not fit the image buffers");
         char* out = (char*)smem;
         __syncthreads();               // every wave has read its last fragments
@@ -331,24 +331,87 @@ __global__ void __launch_bounds__(PNL_THREADS) k_panel_gemm(const float* __restr
             if (bias) bv = *(const f32x4*)(bias + n);
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
-                char* q = out + (16 * i + l15) * ROWB + n * ESZ;
-                if (EPI == 3) {
-                    const float sc = n < CFFM_C ? 0.17677669529663687f : 1.f;
-                    typedef h16 h16x4 __attribute__((ext_vector_type(4)));
-                    h16x4 o;
-                    for (int e = 0; e < 4; ++e) o[e] = (h16)((acc[t][i][e] + bv[e]) * sc);
-                    *(h16x4*)q = o;
-                } else {
-                    *(f32x4*)q = acc[t][i] + bv;
-                }
+                *(f32x4*)(out + (16 * i + l15) * ROWB + n * ESZ) = acc[t][i] + bv;
             }
         }
         __syncthreads();
-        char* dst = (EPI == 3) ? (char*)aux : (char*)C;
+        char* dst = (char*)C;
         for (int u = tid; u < 16 * MT * UPR; u += PNL_THREADS) {
             const int r = u / UPR, c = u % UPR;
             if (m0 + r < M) *(f32x4*)(dst + ((long)(m0 + r) * ldc) * ESZ + 16 * c) = *(const f32x4*)(out + r * ROWB + 16 * c);
         }
+    }
+}
+
+// ---- the q|k|v forward as column thirds: qkv16[M][768] (f16) = f16((x W^T + b) [q third * 32^-0.5]), K = 256 -----------------------------
+// As k_panel_gemm<MT, 6, .., EPI 3> this Linear was one workgroup per CU (256 VGPRs with spills, 112 KB of LDS): every CU staged its
+// panel, multiplied and drained its stores at the same time, and the three phases added up (20 us, 8 of them the store drain).  Here a
+// workgroup computes ONE third (q, k or v: 256 columns, two tiles per wave) of a panel from one {hi, lo} image pair (K = 256 is a single
+// chunk) in <= 128 VGPRs and 32 / 48 KB of LDS, so that two workgroups share a CU (and leave room beside the side stream's kernels): one's
+// stores drain under the other's product.  Per output element the arithmetic is that of the former kernel: same fragments, same pass
+// order, k-steps 0..7 into one accumulator, same epilogue expression -- the same bits.
+// grid = 24 * ceil(panels / 8): workgroups are dealt round-robin over the 8 XCDs by linear id, so id = 8 (3 j + t) + x is panel 8 j + x,
+// third t -- the three readers of a panel share an L2.  x in split-4 storage; x_t (or NULL): T-frag copy of x, written by third 0.
+// Ring depth 2 (one k-step ahead): the co-resident workgroups cover the latency, and depth 4 pushes MT = 3 past 128 VGPRs
+// (profiles/qkv_fwd_thirds_ab.txt has the shapes that were measured)
+#define QKV3_LDS(MT) (2 * PNL_IMG(MT) * 2)
+template <int MT>
+__global__ void __launch_bounds__(PNL_THREADS, 4) k_panel_qkv3(const float* __restrict__ xs, int M, const f32x4* __restrict__ Wf,
+                                                               const float* __restrict__ bias, h16* __restrict__ qkv16, f32x4* __restrict__ x_t) {
+    constexpr int NTW = 2, D = 2, KS = CFFM_C / 32;
+    static_assert(CFFM_C == PNL_KC && PNL_WAVES * NTW * 16 == CFFM_C, "one chunk, 256 columns per third");
+    CFFM_DYN_SMEM(smem);
+    bf16* img = (bf16*)smem;     // [hi | lo][16 MT][256]
+    const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6), l15 = lane & 15, g = lane >> 4;
+    const int q = blockIdx.x >> 3, t = q % 3, pan = 8 * (q / 3) + (blockIdx.x & 7);
+    if (pan >= (M + 16 * MT - 1) / (16 * MT)) return;      // the last group of 8 panels may be short
+    const int m0 = pan * 16 * MT;
+    const buf_t rsa = buf_make(xs, (uint32_t)((long)M * CFFM_C * 4));
+    PnlStream st;
+    st.rs = buf_make(Wf, (uint32_t)(3 * CFFM_C * CFFM_C * 4));
+    st.voff = lane * 16;
+    st.KS = KS;
+    const int jt0 = 16 * t + wave * NTW;
+    f32x4 acc[NTW][MT];
+#pragma unroll
+    for (int j = 0; j < NTW; ++j)
+#pragma unroll
+        for (int i = 0; i < MT; ++i) acc[j][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    PnlRing<2, D> ring;
+    pnl_ring_load<2, D>(ring, 0, st, jt0, 0);
+    pnl_pin_vmem();
+    {
+        PnlStage<MT> sr;
+        pnl_stage_load<MT>(sr, rsa, CFFM_C, m0, 0, tid);
+        pnl_stage_store<MT, true>(sr, img, img + PNL_IMG(MT), tid);
+    }
+    pnl_lds_barrier();
+    pnl_chunk_mma<MT, NTW, 2, D, PnlNoExtra, true>(acc, ring, img, img + PNL_IMG(MT), st, jt0, 0, l15, g, st, jt0, 0);
+    // (behind the product, as in k_panel_gemm: in front of it the stores hold up the B-fragment loads)
+    if (x_t && t == 0) pnl_tfrag_store<MT>(img, img + PNL_IMG(MT), x_t, m0, 0, CFFM_C / 16, M, ((long)M + 31) / 32 * 32, wave, lane);
+    // epilogue through LDS (see k_panel_gemm): the third's [16 MT rows][256] f16 leave as whole 512-byte row segments
+    constexpr int ROWB = CFFM_C * 2 + 32, UPR = CFFM_C * 2 / 16;
+    static_assert(16 * MT * ROWB <= QKV3_LDS(MT), "panel output does not fit the image");
+    char* out = (char*)smem;
+    pnl_lds_barrier();                 // every wave has read its last fragments
+    const float sc = t == 0 ? 0.17677669529663687f : 1.f;
+#pragma unroll
+    for (int j = 0; j < NTW; ++j) {
+        const int nl = 16 * (wave * NTW + j) + 4 * g;
+        const f32x4 bv = *(const f32x4*)(bias + CFFM_C * t + nl);
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+            typedef h16 h16x4 __attribute__((ext_vector_type(4)));
+            h16x4 o;
+            for (int e = 0; e < 4; ++e) o[e] = (h16)((acc[j][i][e] + bv[e]) * sc);
+            *(h16x4*)(out + (16 * i + l15) * ROWB + nl * 2) = o;
+        }
+    }
+    pnl_lds_barrier();
+    char* dst = (char*)qkv16 + CFFM_C * 2 * t;
+    for (int u = tid; u < 16 * MT * UPR; u += PNL_THREADS) {
+        const int r = u / UPR, c = u % UPR;
+        if (m0 + r < M) *(f32x4*)(dst + (long)(m0 + r) * (3 * CFFM_C * 2) + 16 * c) = *(const f32x4*)(out + r * ROWB + 16 * c);
     }
 }
 
