@@ -476,9 +476,34 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_fwd(MlpFwdArgs a) {
     for (int s = 0; s < D - 1; ++s) pnl_ring_load<2, D>(ring, s, sp, 2 * wave, s);
     uint32_t touch = 0;
     pnl_pin_vmem();
+    const f32x4 z4 = (f32x4){0.f, 0.f, 0.f, 0.f};
+    bool valid[MT];
+    long mrow[MT];
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+        const long m = m0 + 16 * i + l15;
+        valid[i] = m < NP;
+        mrow[i] = m;
+    }
+    f32x4 xtv[2][MT], bpv[2];
     {
         PnlStage<MT> sr;
         pnl_stage_load<MT>(sr, buf_make(a.ao, (uint32_t)((long)NP * 256 * 4)), 256, m0, 0, tid);
+        // the residual rows and the proj bias ride behind the panel's loads (staging does not wait for them) and are consumed behind the
+        // proj product: requested there, they would be one exposed HBM round trip with the ring empty (operand prefetch rule, k_mlp_bwd)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int n = 32 * wave + 16 * t + 4 * g;
+            bpv[t] = *(const f32x4*)(a.bp + n);
+#pragma unroll
+            for (int i = 0; i < MT; ++i) {
+                xtv[t][i] = z4;
+                if (valid[i]) {
+                    const long b = mrow[i] / a.rows_per_batch, rr = mrow[i] % a.rows_per_batch;
+                    xtv[t][i] = *(const f32x4*)(a.xt + b * a.xt_bs + rr * 256 + n);
+                }
+            }
+        }
         // L2 warm-up (pnl_l2_touch), behind the panel's loads in the memory queue: staging does not wait for it
         pnl_pin_vmem();
         const uint32_t t0 = pnl_l2_touch(a.w1, 1024L * 256 * 4, tid), t1 = pnl_l2_touch(a.w2, 1024L * 256 * 4, tid);
@@ -489,7 +514,6 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_fwd(MlpFwdArgs a) {
     pnl_lds_barrier();
     const long NP32 = ((long)NP + 31) / 32 * 32;
     if (!INFER && a.ao_t) pnl_tfrag_store<MT>(P, P + PNL_IMG(MT), a.ao_t, m0, 0, 16, NP, NP32, wave, lane);
-    const f32x4 z4 = (f32x4){0.f, 0.f, 0.f, 0.f};
     f32x4 acc[2][MT];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -498,28 +522,24 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_fwd(MlpFwdArgs a) {
     pnl_chunk_mma<MT, 2, 2, D>(acc, ring, P, P + PNL_IMG(MT), sp, 2 * wave, 0, l15, g, s1, 2 * wave, 0);
     // ---- x1 = xt + proj + bp, LayerNorm statistics over the 256 features of a row (8 waves x 32 features)
     f32x4 x1v[2][MT];
-    bool valid[MT];
-    long mrow[MT];
     float s[MT];
 #pragma unroll
-    for (int i = 0; i < MT; ++i) {
-        const long m = m0 + 16 * i + l15;
-        valid[i] = m < NP;
-        mrow[i] = m;
-        s[i] = 0.f;
-    }
+    for (int i = 0; i < MT; ++i) s[i] = 0.f;
+    // LayerNorm weights: requested here, used behind the two reductions below
+    f32x4 gmv[2], bev[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const int n = 32 * wave + 16 * t + 4 * g;
-        const f32x4 bv = *(const f32x4*)(a.bp + n);
+        gmv[t] = *(const f32x4*)(a.g2 + n);
+        bev[t] = *(const f32x4*)(a.be2 + n);
+    }
+    pnl_pin_vmem();
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int n = 32 * wave + 16 * t + 4 * g;
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
-            f32x4 r = z4;
-            if (valid[i]) {
-                const long b = mrow[i] / a.rows_per_batch, rr = mrow[i] % a.rows_per_batch;
-                r = *(const f32x4*)(a.xt + b * a.xt_bs + rr * 256 + n);
-            }
-            const f32x4 v = acc[t][i] + bv + r;
+            const f32x4 v = acc[t][i] + bpv[t] + xtv[t][i];
             x1v[t][i] = v;
             if (!INFER && valid[i]) *(f32x4*)(a.x1 + mrow[i] * 256 + n) = v;
             s[i] += (v[0] + v[1]) + (v[2] + v[3]);
@@ -560,7 +580,7 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_fwd(MlpFwdArgs a) {
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const int n = 32 * wave + 16 * t + 4 * g;
-        const f32x4 gm = *(const f32x4*)(a.g2 + n), be = *(const f32x4*)(a.be2 + n);
+        const f32x4 gm = gmv[t], be = bev[t];
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
             const f32x4 zv = (x1v[t][i] - mu[i]) * rs[i] * gm + be;
@@ -578,18 +598,27 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_fwd(MlpFwdArgs a) {
     for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int i = 0; i < MT; ++i) acc2[t][i] = z4;
+    // the fc2 bias of the last lines: requested ahead of the hidden chunks
+    f32x4 b2v[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) b2v[t] = *(const f32x4*)(a.b2 + 32 * wave + 16 * t + 4 * g);
     for (int c = 0; c < 4; ++c) {
         f32x4 h1[2][MT];
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int i = 0; i < MT; ++i) h1[t][i] = z4;
+        // the chunk's fc1 bias: requested in front of the product whose epilogue adds it
+        f32x4 b1v[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) b1v[t] = *(const f32x4*)(a.b1 + 256 * c + 32 * wave + 16 * t + 4 * g);
+        pnl_pin_vmem();
         pnl_chunk_mma<MT, 2, 2, D>(h1, ring, P, P + PNL_IMG(MT), s1, 16 * c + 2 * wave, 0, l15, g, s2, 2 * wave, 8 * c);
         bf16* Ah = ACT + (c & 1) * 2 * PNL_IMG(MT);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const int nl = 32 * wave + 16 * t + 4 * g, n = 256 * c + nl;
-            const f32x4 bv = *(const f32x4*)(a.b1 + n);
+            const f32x4 bv = b1v[t];
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 const f32x4 raw = h1[t][i];
@@ -612,7 +641,7 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_fwd(MlpFwdArgs a) {
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const int n = 32 * wave + 16 * t + 4 * g;
-        const f32x4 bv = *(const f32x4*)(a.b2 + n);
+        const f32x4 bv = b2v[t];
 #pragma unroll
         for (int i = 0; i < MT; ++i)
             if (valid[i]) *(f32x4*)(a.x2 + mrow[i] * 256 + n) = x1v[t][i] + acc2[t][i] + bv;
@@ -652,9 +681,36 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_bwd(MlpBwdArgs a) {
     uint32_t touch = 0;
     pnl_pin_vmem();
     const buf_t rs_dout = buf_make(a.dout, (uint32_t)((long)NP * 256 * 4));
+    const f32x4 z4 = (f32x4){0.f, 0.f, 0.f, 0.f};
+    bool valid[MT];
+    long mrow[MT];
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+        const long m = m0 + 16 * i + l15;
+        valid[i] = m < NP;
+        mrow[i] = m;
+    }
+    // Operand prefetch.  The CU's vector-memory path is one in-order queue and vmcnt counts a wave's loads in issue order (see
+    // pnl_chunk_mma), so a B-ring slot is consumed only after every load issued before it has returned: an HBM read (2-3 us under
+    // this load) requested in front of a product, or between two, stalls the weight stream (D - 1 k-steps, about 1 us of lead) until
+    // it is back.  Rule: an HBM operand is requested at the START of a phase that does not consume the ring -- panel staging, the
+    // VALU / LDS epilogue between two products -- so that the phase plus the D - 1 prefetched k-steps cover it:
+    //   hr[c & 1]  the saved fc1 product of chunk c: chunk 0 with the dout panel, chunk c + 1 at the start of chunk c's epilogue;
+    //   the LayerNorm operands (x1 in the hr buffer that has no next chunk, dout, mean2, rstd2, g2): at the start of the LAST
+    //   chunk's epilogue, consumed behind the last dz product.
+    // The chunk loop is unrolled so that buffer indices and "last chunk" are compile-time.
+    f32x4 hr[2][2][MT];
+    const auto hr_request = [&](int c) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+                hr[c & 1][t][i] = valid[i] ? *(const f32x4*)(a.hraw + mrow[i] * 1024 + 256 * c + 32 * wave + 16 * t + 4 * g) : z4;
+    };
     {
         PnlStage<MT> sr;
         pnl_stage_load<MT>(sr, rs_dout, 256, m0, 0, tid);
+        hr_request(0);
         // L2 warm-up (pnl_l2_touch), behind the panel's loads in the memory queue
         pnl_pin_vmem();
         const uint32_t t0 = pnl_l2_touch(a.w2n, 1024L * 256 * 4, tid), t1 = pnl_l2_touch(a.w1n, 1024L * 256 * 4, tid), t2 = pnl_l2_touch(a.wpn, 256L * 256 * 4, tid);
@@ -665,45 +721,61 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_bwd(MlpBwdArgs a) {
     pnl_lds_barrier();
     const long NP32 = ((long)NP + 31) / 32 * 32;
     if (a.dout_t) pnl_tfrag_store<MT>(P, P + PNL_IMG(MT), a.dout_t, m0, 0, 16, NP, NP32, wave, lane);
-    const f32x4 z4 = (f32x4){0.f, 0.f, 0.f, 0.f};
-    bool valid[MT];
-    long mrow[MT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-        const long m = m0 + 16 * i + l15;
-        valid[i] = m < NP;
-        mrow[i] = m;
-    }
     f32x4 dz[2][MT];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int i = 0; i < MT; ++i) dz[t][i] = z4;
+    f32x4 dr[2][MT], gmv[2];
+    float mu[MT], rs[MT];
+#pragma unroll
     for (int c = 0; c < 4; ++c) {
         f32x4 da[2][MT];
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int i = 0; i < MT; ++i) da[t][i] = z4;
-        // the saved fc1 product of this chunk is requested before the chunk's first product and consumed behind it
-        f32x4 hr[2][MT];
+        // the chunk's fc1 bias (an L2 hit) goes in front of the product whose epilogue adds it
+        f32x4 b1v[2];
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int i = 0; i < MT; ++i) hr[t][i] = valid[i] ? *(const f32x4*)(a.hraw + mrow[i] * 1024 + 256 * c + 32 * wave + 16 * t + 4 * g) : z4;
+        for (int t = 0; t < 2; ++t) b1v[t] = *(const f32x4*)(a.b1 + 256 * c + 32 * wave + 16 * t + 4 * g);
         pnl_pin_vmem();
         pnl_chunk_mma<MT, 2, 2, D>(da, ring, P, P + PNL_IMG(MT), s2, 16 * c + 2 * wave, 0, l15, g, s1, 2 * wave, 8 * c);
+        const bool more = c < 3;
+        if (more) {
+            hr_request(c + 1);
+        } else {
+#pragma unroll
+            for (int i = 0; i < MT; ++i) {
+                mu[i] = valid[i] ? a.mean2[mrow[i]] : 0.f;
+                rs[i] = valid[i] ? a.rstd2[mrow[i]] : 0.f;
+            }
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const int n = 32 * wave + 16 * t + 4 * g;
+                gmv[t] = *(const f32x4*)(a.g2 + n);
+#pragma unroll
+                for (int i = 0; i < MT; ++i) {
+                    hr[(c + 1) & 1][t][i] = dr[t][i] = z4;
+                    if (valid[i]) {
+                        hr[(c + 1) & 1][t][i] = *(const f32x4*)(a.x1 + mrow[i] * 256 + n);
+                        dr[t][i] = *(const f32x4*)(a.dout + mrow[i] * 256 + n);
+                    }
+                }
+            }
+        }
+        pnl_pin_vmem();
         bf16* Ah = DH + (c & 1) * 2 * PNL_IMG(MT);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const int nl = 32 * wave + 16 * t + 4 * g, n = 256 * c + nl;
-            const f32x4 bv = *(const f32x4*)(a.b1 + n);
+            const f32x4 bv = b1v[t];
             f32x4 cs = z4;
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 f32x4 dh = z4;
                 if (valid[i]) {
-                    const f32x4 hv = hr[t][i] + bv;
+                    const f32x4 hv = hr[c & 1][t][i] + bv;
                     for (int e = 0; e < 4; ++e) dh[e] = da[t][i][e] * gelu_erf_grad(hv[e]);
                 }
                 bf16x4 h, l;
@@ -717,33 +789,23 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_bwd(MlpBwdArgs a) {
         }
         pnl_lds_barrier();
         if (a.dh_t) pnl_tfrag_store<MT>(Ah, Ah + PNL_IMG(MT), a.dh_t, m0, 16 * c, 64, NP, NP32, wave, lane);
-        const bool more = c < 3;
         pnl_chunk_mma<MT, 2, 2, D>(dz, ring, Ah, Ah + PNL_IMG(MT), s1, 2 * wave, 8 * c, l15, g, more ? s2 : sp, more ? 16 * (c + 1) + 2 * wave : 2 * wave, 0);
     }
     // ---- LayerNorm backward + residual: dx1 = dout + rstd (gz - mean(gz) - xh mean(gz xh)), gz = dz2 * gamma
-    f32x4 xh[2][MT], gz[2][MT], dr[2][MT];
-    float mu[MT], rs[MT], m1[MT], m2[MT];
+    f32x4 xh[2][MT], gz[2][MT];
+    float m1[MT], m2[MT];
 #pragma unroll
-    for (int i = 0; i < MT; ++i) {
-        mu[i] = valid[i] ? a.mean2[mrow[i]] : 0.f;
-        rs[i] = valid[i] ? a.rstd2[mrow[i]] : 0.f;
-        m1[i] = m2[i] = 0.f;
-    }
+    for (int i = 0; i < MT; ++i) m1[i] = m2[i] = 0.f;
     f32x4 ag[2], ab[2], ar[2], ax[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const int n = 32 * wave + 16 * t + 4 * g;
-        const f32x4 gm = *(const f32x4*)(a.g2 + n);
+        const f32x4 gm = gmv[t];
         ag[t] = ab[t] = ar[t] = ax[t] = z4;
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
-            f32x4 xv = z4, dv = z4;
-            if (valid[i]) {
-                xv = *(const f32x4*)(a.x1 + mrow[i] * 256 + n);
-                dv = *(const f32x4*)(a.dout + mrow[i] * 256 + n);
-            }
+            const f32x4 xv = hr[0][t][i], dv = dr[t][i];      // (hr[0]: the x1 rows since the last chunk's epilogue)
             xh[t][i] = (xv - mu[i]) * rs[i];
-            dr[t][i] = dv;
             gz[t][i] = dz[t][i] * gm;
             ag[t] += dz[t][i] * xh[t][i];
             ab[t] += dz[t][i];
