@@ -8,9 +8,11 @@
  *   cffm_block_forward / _backward   <->  CffmTransformerBlock3d3.forward  cffm_transformer.py:709-832
  *   cffm_ln_pool_fwd                 <->  CFFA: norm1 + pad + pool_layers / pool_layers_clips
  *                                                                           cffm_transformer.py:716-805
- *   cffm_bias_assemble               <->  relative-position bias gathers    cffm_transformer.py:536-587
+ *   cffm_ln_pool_bwd                 <->  autograd through the same lines (the stage-level backward of the CFFA)
+ *   cffm_bias_assemble / _scatter    <->  relative-position bias gathers (and their adjoint)  cffm_transformer.py:536-587
  *   cffm_attn_fwd / _bwd             <->  WindowAttention3d3.forward (CFM)  cffm_transformer.py:364-606
  *   cffm_linear_*                    <->  nn.Linear (qkv :374, proj :602, Mlp :10-26)
+ *   cffm_panel_qkv_fwd / _bwd_input  <->  the q|k|v Linear (:374) on token rows, forward and input gradient
  *   cffm_mlp_fwd / _bwd              <->  proj + residual + norm2 + Mlp + residual  :602, :823-824
  *   cffm_gtc_*                       <->  BasicLayer_cluster / WindowAttention_cluster (CFFM++)
  *                                                         pvt/swin_transformer_2d.py:1103-1148, :208-262
@@ -190,6 +192,32 @@ int cffm_colsum(const float* a, long rows, int cols /* multiple of 4 */, float* 
  * the q / k / v column thirds of a row panel, two workgroups per CU.  x_t (or NULL): also writes the T-frag copy of x
  * (cffm_tfrag_floats(M, 256) floats, rows past M zero). */
 int cffm_panel_qkv_fwd(const float* x_split4, const float* w_frag, const float* b /*[768]*/, void* qkv16, long M, float* x_t, void* stream);
+/* added under ABI 13, additive: three pieces of the block backward as stages (what cffm_block_backward / cffm_layer_backward* run, through
+ * the same launch helpers), for the parity tests.
+ *
+ * cffm_ln_pool_bwd: the CFFA backward -- the whole adjoint of cffm_pool_matrix + cffm_ln_pool_fwd -- for n = 1..8 blocks that share the
+ * reference frames x_ref [B,3,HW,256] (batch stride ref_bs).  Per block (a HOST array of n structs): x_tgt [B,HW,256] (batch stride tgt_bs),
+ * norm1's gamma / beta, the block's composed pooling matrix M [15*49], mean / rstd [B*4*HW] as cffm_ln_pool_fwd wrote them (the reference
+ * pass reads the copy of the first block of each launch), the token-row gradient dzall [B*RC,256] (rows of padded target pixels are not
+ * read) and dres [B*HW,256] or NULL, the residual-path gradient added to dx_tgt.  Written per block: dx_tgt [B,HW,256] (batch stride
+ * dtgt_bs), dgamma / dbeta [256], dpool_w (49 / 49 / 9 / 4 floats) and dpool_b (1 float each; with cffm_grad_slices_padded(1) also 3 zeros
+ * behind the first three weights and behind every bias).  dx_ref [B,3,HW,256] (batch stride dref_bs) = the sum over the blocks, added to
+ * what it holds when accum_ref != 0.  Blocks go four per reference launch (blocks 0..3, then 4..7), the second launch accumulating. */
+typedef struct cffm_cffa_bwd_block {
+    const float* x_tgt; long tgt_bs;
+    const float *gamma, *beta, *M, *mean, *rstd, *dzall, *dres;
+    float* dx_tgt; long dtgt_bs;
+    float *dgamma, *dbeta, *dpool_w[4], *dpool_b[4];
+} cffm_cffa_bwd_block;
+int cffm_ln_pool_bwd(const cffm_geom* g, int n, const cffm_cffa_bwd_block* blocks /* host [n] */, const float* x_ref, long ref_bs,
+                     float* dx_ref, long dref_bs, int accum_ref, void* stream);
+/* the q|k|v input gradient: dx [M,256] = dqkv [M,768] w, dqkv fp32, w in fragment order (cffm_panel_pack_weight of w [768,256], form 1);
+ * db (or NULL) [768] = the column sums of dqkv (qkv.bias.grad: records out of the same launch, then one reduction); dqkv_t (or NULL): also
+ * writes the T-frag copy of dqkv (cffm_tfrag_floats(M, 768) floats, rows past M zero).  Nothing past row M of dqkv is read. */
+int cffm_panel_qkv_bwd_input(const float* dqkv, const float* w_frag, float* dx, float* db, float* dqkv_t, long M, void* stream);
+/* the adjoint of cffm_bias_assemble: dbiasT [8 heads][304 keys][64 queries] (key-major, as cffm_attn_bwd leaves it) -> the gradients of
+ * the six tables (shapes as in cffm_block_params), every entry written; query columns 49..63 and key rows 289..303 are not read. */
+int cffm_bias_scatter(const float* dbiasT, float* down, float* dring, float* const dpool[4], void* stream);
 
 /* ---- CFFM++ global temporal context (WindowAttention_cluster, pvt/swin_transformer_2d.py:208-262) ---- */
 /* q_raw [B*T,256] = LN(x) Wq^T without bias, kv_raw [B*K,512] = LN(centers) Wkv^T without bias; softmax over the K

@@ -151,6 +151,39 @@ def gelu_erf(x):
     return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
 
 
+def cffa_forward(x, p):
+    """The CFFA in front of the attention (cffm_transformer.py:716-805): x [B,4,H0,W0,C] -> the normalised, zero-padded target frame
+    zt [B,Hp,Wp,C] and the four pooled grids [P0 (target windows), f0, f1, f2 (reference frames 0, 1, 2: 1, 2x2, 3x3 cells a window)]."""
+    _, t, h0, w0, c = x.shape
+    hp, wp = padded_size(h0, w0)
+    gy, gx = hp // WS, wp // WS
+    # A.1  LayerNorm on all frames, then zero padding (:716, :721-724)
+    z = F.layer_norm(x, (c,), p['norm1.weight'], p['norm1.bias'], 1e-5)
+    zp = F.pad(z, (0, 0, 0, wp - w0, 0, hp - h0))
+    zt = zp[:, t - 1]
+    # A.5  pooled target windows (:741-776)
+    pooled = [pool_windows(zt, WS, p['pool_layers.0.weight'], p['pool_layers.0.bias'])]
+    # A.6  reference frames (:780-805)
+    for f, s in enumerate(FOCAL_L_CLIPS):
+        wsg = WS // s
+        hpool, wpool = gy * s * wsg, gx * s * wsg
+        zf = zp[:, f]
+        if hpool != hp or wpool != wp:                                              # :794-795
+            zf = F.interpolate(zf.permute(0, 3, 1, 2), size=(hpool, wpool), mode='bilinear').permute(0, 2, 3, 1)
+        pooled.append(pool_windows(zf.contiguous(), wsg, p['pool_layers_clips.%d.weight' % f],
+                                   p['pool_layers_clips.%d.bias' % f]))
+    return zt, pooled
+
+
+def cffa_token_rows(x, p):
+    """cffa_forward's results as the rows the q|k|v Linear reads, per clip [B,64 nW,C]: the target tokens window by window
+    (window_pixels), then the pooled cells P0 | f0 | f1 | f2, each grid row-major."""
+    b, c = x.shape[0], x.shape[-1]
+    zt, pooled = cffa_forward(x, p)
+    win = torch.from_numpy(window_pixels(zt.shape[1], zt.shape[2])).to(x.device)
+    return torch.cat([zt.reshape(b, -1, c)[:, win.view(-1)]] + [pg.reshape(b, -1, c) for pg in pooled], dim=1)
+
+
 # --------------------------------------------------------------------------- the block
 def block_forward(x, p, want=False):
     """One CffmTransformerBlock3d3 (cffm_transformer.py:709-832).
@@ -168,10 +201,7 @@ def block_forward(x, p, want=False):
     dev = x.device
     ix = lambda a: torch.from_numpy(a).to(dev)
 
-    # A.1  LayerNorm on all frames, then zero padding (:716, :721-724)
-    z = F.layer_norm(x, (c,), p['norm1.weight'], p['norm1.bias'], 1e-5)
-    zp = F.pad(z, (0, 0, 0, wp - w0, 0, hp - h0))
-    zt = zp[:, t - 1]
+    zt, pooled = cffa_forward(x, p)          # A.1, A.5, A.6
 
     wq, bq = p['attn.qkv.weight'], p['attn.qkv.bias']
 
@@ -186,19 +216,8 @@ def block_forward(x, p, want=False):
     v_parts = [v[:, win], v[:, ring]]
     mask_parts = [torch.zeros(nw, 49 + 132, dtype=x.dtype, device=dev)]
 
-    # A.5  pooled target windows (:741-776) and their 5x5 neighbourhood (:426-468)
-    pooled = [pool_windows(zt, WS, p['pool_layers.0.weight'], p['pool_layers.0.bias'])]
-    geo = [(1, FOCAL_WINDOW, FOCAL_WINDOW // 2)]
-    # A.6  reference frames (:780-805, :470-518)
-    for f, (s, kk) in enumerate(zip(FOCAL_L_CLIPS, FOCAL_KERNEL_CLIPS)):
-        wsg = WS // s
-        hpool, wpool = gy * s * wsg, gx * s * wsg
-        zf = zp[:, f]
-        if hpool != hp or wpool != wp:                                              # :794-795
-            zf = F.interpolate(zf.permute(0, 3, 1, 2), size=(hpool, wpool), mode='bilinear').permute(0, 2, 3, 1)
-        pooled.append(pool_windows(zf.contiguous(), wsg, p['pool_layers_clips.%d.weight' % f],
-                                   p['pool_layers_clips.%d.bias' % f]))
-        geo.append((s, kk, kk // 2))
+    # the 5x5 neighbourhood of the pooled target windows (:426-468) and the unfolds of the reference frames' cells (:470-518)
+    geo = [(1, FOCAL_WINDOW, FOCAL_WINDOW // 2)] + [(s, kk, kk // 2) for s, kk in zip(FOCAL_L_CLIPS, FOCAL_KERNEL_CLIPS)]
     for pg, (s, kk, pad) in zip(pooled, geo):
         kv = F.linear(pg, wq, bq).view(bsz, -1, 3, c)                              # :449, :495 (q third unused)
         cells = ix(unfold_cells(gy, gx, s, kk, pad))                                # [nW,kk*kk]

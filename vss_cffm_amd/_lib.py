@@ -31,6 +31,12 @@ class BlockWs(C.Structure):
                                   'rstd2', 'z2', 'hraw', 'act', 'x2', 'w_split', 'w_frag', 'ao_t', 'zall_t', 'total')]
 
 
+class CffaBwdBlock(C.Structure):
+    """cffm_cffa_bwd_block"""
+    _fields_ = ([('x_tgt', vp), ('tgt_bs', cl)] + [(n, vp) for n in ('gamma', 'beta', 'M', 'mean', 'rstd', 'dzall', 'dres')]
+                + [('dx_tgt', vp), ('dtgt_bs', cl), ('dgamma', vp), ('dbeta', vp), ('dpool_w', vp * 4), ('dpool_b', vp * 4)])
+
+
 class GtcPtrs(C.Structure):
     """cffm_gtc_params / cffm_gtc_grads (same field order)."""
     _fields_ = [(n, vp) for n in ('norm1_w', 'norm1_b', 'qkv_w', 'qkv_b', 'kv_w', 'kv_b', 'proj_w', 'proj_b', 'norm2_w', 'norm2_b',
@@ -52,6 +58,7 @@ class MitStageCfg(C.Structure):
 GP, BP = C.POINTER(Geom), C.POINTER(BlockPtrs)
 MBP, MCP = C.POINTER(MitBlockPtrs), C.POINTER(MitStageCfg)
 GTP = C.POINTER(GtcPtrs)
+CBP = C.POINTER(CffaBwdBlock)
 P4 = vp * 4
 
 SIGNATURES = {
@@ -99,6 +106,9 @@ SIGNATURES = {
     'cffm_colsum': (ci, [vp, cl, ci, vp, vp]),
     'cffm_panel_pack_weight': (ci, [vp, ci, ci, ci, vp, vp]),
     'cffm_panel_qkv_fwd': (ci, [vp, vp, vp, vp, cl, vp, vp]),
+    'cffm_ln_pool_bwd': (ci, [GP, ci, CBP, vp, cl, vp, cl, ci, vp]),
+    'cffm_panel_qkv_bwd_input': (ci, [vp, vp, vp, vp, vp, cl, vp]),
+    'cffm_bias_scatter': (ci, [vp, vp, vp, C.POINTER(vp), vp]),
     'cffm_mlp_fwd': (ci, [vp, vp, cl, ci] + [vp] * 15 + [cl, vp]),
     'cffm_mlp_bwd': (ci, [vp] * 18 + [cl, vp]),
     'cffm_block_forward': (ci, [GP, BP, vp, cl, vp, cl, vp, vp, vp, vp, vp]),

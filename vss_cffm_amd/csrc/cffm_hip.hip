@@ -729,44 +729,46 @@ static int cffa_slot(const cffm_geom* g, int slot, int nslots, CffaSlot* o) {
     o->dzall = p; o->rec = p + a; o->dM = p + a + b;
     return 0;
 }
-// End of a range of block backwards (blocks first, first - 1, ..., last of a layer with `nslots` blocks; block i's parameters / gradients
-// at params[i] / grads[i], its workspace at ws0 + i * ws_stride): the reference frames of all of them in one pass (RB_MAXD blocks per
-// launch) -> dx_ref, then every CFFA parameter gradient of the range: norm1, the pooling matrix -> the pooling Linears, the pool biases.
+// One block's share of the end of the CFFA backward: what the reference pass reads of it (norm1, its composed pooling matrix, the saved
+// LayerNorm statistics, its token-row gradient), its records (target workgroups in rec[0, rows), reference workgroups behind them), its
+// pooling-matrix gradient and where its parameter gradients go.
+struct CffaBlk {
+    const float *gamma, *beta, *M, *mean, *rstd, *dzall;
+    float *rec, *dM;
+    float *dgamma, *dbeta;
+    float* const* dpool_w;
+    float* const* dpool_b;
+};
+// The reference frames of `count` blocks in one pass (RB_MAXD blocks per launch, the launches after the first add to dx_ref) -> dx_ref,
+// then every CFFA parameter gradient of those blocks: norm1, the pooling matrix -> the pooling Linears, the pool biases.  The target
+// records of every block are written by now (ln_pool_bwd_tgt).
 // `extra` (or NULL): record reductions of the caller that are due at this point of the stream anyway (the last block's parameter-gradient
 // tail): they join the final reduction launch instead of taking one of their own.
-static int cffa_finish(const cffm_geom* g, int nslots, const cffm_block_params* params, const cffm_block_grads* grads, int first, int last,
-                       const float* ws0, long ws_stride, const float* x_ref, long ref_bs, float* dx_ref, long dref_bs, int accum, void* stream,
-                       RedJobs* extra = nullptr) {
-    cffm_block_ws L;
-    cffm_block_ws_layout(g, &L);
+static int cffa_finish_blocks(const cffm_geom* g, const CffaBlk* blk, int count, const float* x_ref, long ref_bs, float* dx_ref, long dref_bs,
+                              int accum, void* stream, RedJobs* extra = nullptr) {
     hipStream_t st = (hipStream_t)stream;
     const long rows = cffa_rows(g);
     static_assert(PMB_MAXD == RB_MAXD, "one pooling-matrix launch per reference launch");
-    for (int hi = first; hi >= last; hi -= RB_MAXD) {
-        const int n = hi - last + 1 < RB_MAXD ? hi - last + 1 : RB_MAXD;
+    for (int k0 = 0; k0 < count; k0 += RB_MAXD) {
+        const int n = count - k0 < RB_MAXD ? count - k0 : RB_MAXD;
         CffaRefBlocks Bk;
         PoolWGN pw;
         RedJobs J;
         Bk.n = n; J.njob = 0;
         for (int d = 0; d < RB_MAXD; ++d) {
-            const int i = hi - (d < n ? d : 0);
-            CffaSlot S;
-            TRY(cffa_slot(g, i, nslots, &S));
-            Bk.gamma[d] = params[i].norm1_w; Bk.beta[d] = params[i].norm1_b; Bk.M[d] = ws0 + i * ws_stride + L.M;
-            Bk.dzall[d] = S.dzall; Bk.rec[d] = S.rec + rows * LNP_RSTRIDE;
-            pw.dM[d] = S.dM;
-            for (int q = 0; q < 4; ++q) { pw.gw[d].w[q] = grads[i].pool_w[q]; pw.gw[d].b[q] = g_grad_pads ? grads[i].pool_b[q] : nullptr; }
+            const CffaBlk& b = blk[k0 + (d < n ? d : 0)];
+            Bk.gamma[d] = b.gamma; Bk.beta[d] = b.beta; Bk.M[d] = b.M;
+            Bk.dzall[d] = b.dzall; Bk.rec[d] = b.rec + rows * LNP_RSTRIDE;
+            pw.dM[d] = b.dM;
+            for (int q = 0; q < 4; ++q) { pw.gw[d].w[q] = b.dpool_w[q]; pw.gw[d].b[q] = g_grad_pads ? b.dpool_b[q] : nullptr; }
         }
         // (the LayerNorm statistics of the reference frames are the same in every block: any block's saved copy serves)
-        const float* ws = ws0 + (long)hi * ws_stride;
-        TRY(ln_pool_bwd_ref(g, x_ref, ref_bs, Bk, ws + L.mean1, ws + L.rstd1, dx_ref, dref_bs, accum || hi != first, stream));
+        TRY(ln_pool_bwd_ref(g, x_ref, ref_bs, Bk, blk[k0].mean, blk[k0].rstd, dx_ref, dref_bs, accum || k0 != 0, stream));
         for (int d = 0; d < n; ++d) {
-            const int i = hi - d;
-            CffaSlot S;
-            TRY(cffa_slot(g, i, nslots, &S));
-            cffa_jobs(J, S.rec, rows, grads[i].norm1_w, grads[i].norm1_b, S.dM, grads[i].pool_b, st);
+            const CffaBlk& b = blk[k0 + d];
+            cffa_jobs(J, b.rec, rows, b.dgamma, b.dbeta, b.dM, b.dpool_b, st);
         }
-        if (extra && hi - RB_MAXD < last) {        // (the range's last launch)
+        if (extra && k0 + RB_MAXD >= count) {        // (the last launch)
             for (int j = 0; j < extra->njob; ++j) job_add(J, extra->part[j], extra->nblk[j], extra->stride[j], extra->total[j], extra->segs[j], st);
             extra->njob = 0;
         }
@@ -780,6 +782,49 @@ static int cffa_finish(const cffm_geom* g, int nslots, const cffm_block_params* 
     }
     return 0;
 }
+// End of a range of block backwards (blocks first, first - 1, ..., last of a layer with `nslots` blocks; block i's parameters / gradients
+// at params[i] / grads[i], its workspace at ws0 + i * ws_stride, its token-row gradient, records and pooling-matrix gradient in slot i).
+static int cffa_finish(const cffm_geom* g, int nslots, const cffm_block_params* params, const cffm_block_grads* grads, int first, int last,
+                       const float* ws0, long ws_stride, const float* x_ref, long ref_bs, float* dx_ref, long dref_bs, int accum, void* stream,
+                       RedJobs* extra = nullptr) {
+    cffm_block_ws L;
+    cffm_block_ws_layout(g, &L);
+    const int count = first - last + 1;
+    CffaBlk few[8];
+    std::vector<CffaBlk> many;
+    CffaBlk* blk = few;
+    if (count > 8) { many.resize(count); blk = many.data(); }
+    for (int k = 0; k < count; ++k) {
+        const int i = first - k;
+        const float* ws = ws0 + (long)i * ws_stride;
+        CffaSlot S;
+        TRY(cffa_slot(g, i, nslots, &S));
+        blk[k] = {params[i].norm1_w, params[i].norm1_b, ws + L.M, ws + L.mean1, ws + L.rstd1, S.dzall, S.rec, S.dM,
+                  grads[i].norm1_w, grads[i].norm1_b, grads[i].pool_w, grads[i].pool_b};
+    }
+    return cffa_finish_blocks(g, blk, count, x_ref, ref_bs, dx_ref, dref_bs, accum, stream, extra);
+}
+// The CFFA backward as a stage: the target frame of each block (as the block backward runs it), then the end of the range above
+int cffm_ln_pool_bwd(const cffm_geom* g, int n, const cffm_cffa_bwd_block* blocks, const float* x_ref, long ref_bs, float* dx_ref, long dref_bs,
+                     int accum_ref, void* stream) {
+    REQUIRE(g && blocks && x_ref && dx_ref, "ln_pool_bwd: null");
+    REQUIRE(n >= 1 && n <= 8, "ln_pool_bwd: %d blocks (1..8 per call)", n);
+    for (int d = 0; d < n; ++d) {
+        const cffm_cffa_bwd_block& b = blocks[d];
+        bool ok = b.x_tgt && b.gamma && b.beta && b.M && b.mean && b.rstd && b.dzall && b.dx_tgt && b.dgamma && b.dbeta;
+        for (int q = 0; q < 4; ++q) ok = ok && b.dpool_w[q] && b.dpool_b[q];
+        REQUIRE(ok, "ln_pool_bwd: null pointer in block %d", d);
+    }
+    CffaBlk blk[8];
+    for (int d = 0; d < n; ++d) {
+        const cffm_cffa_bwd_block& b = blocks[d];
+        CffaSlot S;              // (the slot's own dzall stays unused: the caller brings the token-row gradient)
+        TRY(cffa_slot(g, d, n, &S));
+        TRY(ln_pool_bwd_tgt(g, b.x_tgt, b.tgt_bs, b.gamma, b.beta, b.M, b.mean, b.rstd, b.dzall, b.dres, b.dx_tgt, b.dtgt_bs, S.rec, stream));
+        blk[d] = {b.gamma, b.beta, b.M, b.mean, b.rstd, b.dzall, S.rec, S.dM, b.dgamma, b.dbeta, b.dpool_w, b.dpool_b};
+    }
+    return cffa_finish_blocks(g, blk, n, x_ref, ref_bs, dx_ref, dref_bs, accum_ref, stream);
+}
 
 int cffm_bias_assemble(const float* own, const float* ring, const float* const pool[4], float* bias, void* biasH, void* stream) {
     PROF(ST_BIAS_ASM);
@@ -792,7 +837,8 @@ int cffm_bias_assemble(const float* own, const float* ring, const float* const p
     return 0;
 }
 
-static int cffm_bias_scatter(const float* dbiasT, float* down, float* dring, float* const dpool[4], void* stream) {
+int cffm_bias_scatter(const float* dbiasT, float* down, float* dring, float* const dpool[4], void* stream) {
+    REQUIRE(dbiasT && down && dring && dpool && dpool[0] && dpool[1] && dpool[2] && dpool[3], "bias_scatter: null");
     PROF(ST_BIAS_SCT);
     BiasTablesG t;
     t.own = down; t.ring = dring;
@@ -1167,6 +1213,31 @@ int cffm_panel_qkv_fwd(const float* x_split4, const float* w_frag, const float* 
     PROF(ST_GEMM);
     REQUIRE(!panel_qkv_fwd(x_split4, w_frag, b, (h16*)qkv16, M, (hipStream_t)stream, x_t), "panel_qkv_fwd: launch failed");
     CHECK_LAUNCH("panel_qkv_fwd");
+    return 0;
+}
+
+// the q|k|v input gradient of the block as a stage (k_panel_gemm, K = 768): w_frag = cffm_panel_pack_weight(w [768][256], form 1)
+int cffm_panel_qkv_bwd_input(const float* dqkv, const float* w_frag, float* dx, float* db, float* dqkv_t, long M, void* stream) {
+    REQUIRE(dqkv && w_frag && dx && M >= 1 && M < (1L << 21), "panel_qkv_bwd_input: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    float* rec = nullptr;
+    const long nrec = panel_qkv_records(M);
+    if (db) {
+        rec = red_scratch((size_t)nrec * 768, st);
+        REQUIRE(rec, "panel_qkv_bwd_input: scratch allocation failed");
+    }
+    {
+        PROF(ST_GEMM); PROF2(ST_G_QKV_DX);
+        REQUIRE(!panel_qkv_dx(dqkv, w_frag, dx, M, st, rec, dqkv_t), "panel_qkv_bwd_input: launch failed");
+        CHECK_LAUNCH("panel_qkv_bwd_input");
+    }
+    if (db) {    // the q|k|v bias gradient: the column sums of dqkv, out of the records of the launch above
+        RedSegs segs;
+        segs.nseg = 0;
+        seg_add(segs, 0, 768, db, 0);
+        reduce_records(rec, (int)nrec, 768, 768, segs, st);
+        CHECK_LAUNCH("panel_qkv_bwd_input reduction");
+    }
     return 0;
 }
 
