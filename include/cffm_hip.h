@@ -156,6 +156,13 @@ int cffm_linear_bwd_weight(const float* dy, const float* x, float* dw, long M, i
  * block (qkv / proj / fc1 / fc2 .weight.grad, cffm_transformer.py:374, :381, :18-19), none of which feeds the backward chain */
 typedef struct { const float* dy; const float* x; float* dw; long M; int N; int K; } cffm_wgrad;
 int cffm_linear_bwd_weight_group(const cffm_wgrad* problems /* host */, int n, void* stream);
+/* added under ABI 13, additive: the same call with what the block backward passes to the grouped kernel, for the parity tests.  forms (host,
+ * [n]): dy_pre / x_pre = 0: the operand is fp32; 1: it is in "split-4" storage ({bf16 hi x4, bf16 lo x4} per 4 floats of a row, same bytes);
+ * x_pre = 2: x is gelu(stored + x_bias[K]), applied while the tile is staged (only where the grouped kernel runs: every N and K a multiple of
+ * 128, every M >= 32; an error otherwise).  target_wgs: workgroups the launch aims for (sets the common k-slice length; 0 = the default). */
+typedef struct { int dy_pre, x_pre; const float* x_bias; } cffm_wgrad_form;
+int cffm_linear_bwd_weight_group_forms(const cffm_wgrad* problems /* host */, const cffm_wgrad_form* forms /* host */, int n, int target_wgs,
+                                       void* stream);
 /* ABI 9: weight gradient with both operands in "T-frag" storage (csrc/dws_kernels.h): MFMA fragments along the contraction -- unit (ks, jt, h)
  * = 64 lanes x 16 B at 16-byte word ((ks * C/16 + jt) * 2 + h) * 64, lane (l15, g) holding x[32 ks + 8 g + e][16 jt + l15], e = 0..7, as bf16
  * hi (h = 0) / lo (h = 1), rows past M zero -- streamed straight into registers: no LDS staging, no barrier in the contraction loop.  The

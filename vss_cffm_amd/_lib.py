@@ -98,6 +98,7 @@ SIGNATURES = {
     'cffm_linear_bwd_input': (ci, [vp, vp, vp, cl, ci, ci, vp]),
     'cffm_linear_bwd_weight': (ci, [vp, vp, vp, cl, ci, ci, vp]),
     'cffm_linear_bwd_weight_group': (ci, [vp, ci, vp]),
+    'cffm_linear_bwd_weight_group_forms': (ci, [vp, vp, ci, ci, vp]),
     'cffm_tfrag_floats': (cl, [cl, ci]),
     'cffm_dw_stream': (ci, [ci]),
     'cffm_tfrag_pack': (ci, [vp, vp, cl, ci, vp]),

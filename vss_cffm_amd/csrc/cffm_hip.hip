@@ -945,6 +945,23 @@ int cffm_linear_bwd_weight_group(const cffm_wgrad* problems, int n, void* stream
     return 0;
 }
 
+// the same call with the operand storage forms and the workgroup target the block backward passes (parity tests of the grouped kernel's forms)
+int cffm_linear_bwd_weight_group_forms(const cffm_wgrad* problems, const cffm_wgrad_form* forms, int n, int target_wgs, void* stream) {
+    REQUIRE(problems && forms && n >= 1 && n <= 4 && target_wgs >= 0, "linear_bwd_weight_group_forms: 1..4 problems");
+    static_assert(sizeof(cffm_wgrad) == sizeof(GemmTN) && sizeof(cffm_wgrad_form) == sizeof(GemmTNPre), "wgrad layout");
+    for (int i = 0; i < n; ++i) {
+        REQUIRE(problems[i].dy && problems[i].x && problems[i].dw, "linear_bwd_weight_group_forms: null operand");
+        REQUIRE((forms[i].dy_pre == 0 || forms[i].dy_pre == 1) && forms[i].x_pre >= 0 && forms[i].x_pre <= 2 && (forms[i].x_pre != 2 || forms[i].x_bias),
+                "linear_bwd_weight_group_forms: unknown storage form");
+    }
+    ScratchFor pool(stream);
+    PROF(ST_GEMM);
+    if (gemm_tn_group((const GemmTN*)problems, n, (hipStream_t)stream, (const GemmTNPre*)forms, lib_scratch, target_wgs))
+        return fail(-3, "linear_bwd_weight_group_forms: gemm failed");
+    CHECK_LAUNCH("linear_bwd_weight_group_forms");
+    return 0;
+}
+
 // row-major fp32 x[R][C] -> T-frag storage (dws_kernels.h: MFMA fragments along the contraction, bf16 hi | lo, rows padded to a multiple of
 // 32 with zeros): what the operands of cffm_linear_bwd_weight_tfrag are stored as.  dst: cffm_tfrag_floats(R, C) floats.  A utility: inside
 // the block the row-panel kernels leave their operands in this order themselves.

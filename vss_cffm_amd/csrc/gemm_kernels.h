@@ -230,12 +230,17 @@ __device__ __forceinline__ int xcd_linear_id() {
 }
 
 // One output tile (bx, by) of k-slice bz: the whole body of the GEMM kernels below.
-template <int BM, int BN, int BK, bool A_T, bool B_T, int EPI, int PF>
+// A_PRE / B_PRE: the storage form of each operand (tile_store's `pre`) as a compile-time constant, or -1: taken from the arguments
+// a_pre_rt / b_pre_rt at run time.  A run-time form puts a branch into every tile_store, which cuts the fast K-loop into basic blocks
+// (34 per K-step in the 128 x 128 <T,T> body, 2-3 times the instructions of a body with constant forms) and keeps the scheduling hints
+// from reaching across them.  With PF = 1 the split is a phase behind the MFMAs either way: it has to wait for the one tile in flight.
+template <int BM, int BN, int BK, bool A_T, bool B_T, int EPI, int PF, int A_PRE = -1, int B_PRE = -1>
 __device__ __forceinline__ void gemm_tile(char* smem, const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ C,
                                           int M, int N, int K, int lda, int ldb, int ldc, int klen, long split_stride,
                                           const float* __restrict__ bias, float* __restrict__ aux, int bx, int by, int bz,
-                                          bool a_pre = false, int b_pre = 0, float* __restrict__ aux2 = nullptr,
+                                          bool a_pre_rt = false, int b_pre_rt = 0, float* __restrict__ aux2 = nullptr,
                                           const float* __restrict__ b_bias = nullptr /* b_pre == 2: bias of the on-load GELU */) {
+    const int a_pre = A_PRE >= 0 ? A_PRE : (int)a_pre_rt, b_pre = B_PRE >= 0 ? B_PRE : b_pre_rt;
     bf16* Ah = (bf16*)smem;
     bf16* Al = Ah + GEMM_IMG(BM, BK);
     bf16* Bh = Al + GEMM_IMG(BM, BK);
@@ -433,8 +438,8 @@ __global__ void __launch_bounds__(256) k_gemm_split(const float* __restrict__ A,
     CFFM_DYN_SMEM(smem);
     const int lin = xcd_linear_id();
     const int ntn = (N + BN - 1) / BN, ntm = (M + BM - 1) / BM;
-    gemm_tile<BM, BN, BK, A_T, B_T, EPI, PF>(smem, A, B, C, M, N, K, lda, ldb, ldc, klen, split_stride, bias, aux, lin % ntn,
-                                             (lin / ntn) % ntm, lin / (ntn * ntm), A_PRE, B_PRE, aux2);
+    gemm_tile<BM, BN, BK, A_T, B_T, EPI, PF, A_PRE, B_PRE>(smem, A, B, C, M, N, K, lda, ldb, ldc, klen, split_stride, bias, aux, lin % ntn,
+                                                           (lin / ntn) % ntm, lin / (ntn * ntm), A_PRE, B_PRE, aux2);
 }
 
 // Up to GEMM_GROUP_MAX independent weight-gradient GEMMs (dw = dy^T x, <T,T>, 128x128 tiles) in ONE launch.  The four of a
@@ -442,6 +447,15 @@ __global__ void __launch_bounds__(256) k_gemm_split(const float* __restrict__ A,
 // ~20 k-slices to occupy 256 CUs, i.e. 12 K-steps per workgroup between a prologue and a 64 KB partial-tile epilogue, and
 // its own partial-sum pass.  None of them feeds the backward chain, so they are deferred and share one grid: ~480
 // workgroups with one common slice length (2-3x longer), a third of the partial traffic and one summation launch.
+// The storage forms of a block's four problems -- (dy, x) = (plain, split-4) for q|k|v and fc2, (split-4, split-4) for fc1, (plain, plain)
+// for proj -- each get a body of their own with the forms as constants: its fast K-loop is one basic block per K-step without exec-mask
+// branches (330-440 instructions where the run-time body has about 900; 50.1-51.3 us where that takes 54.1: DESIGN 3s).  The order inside a
+// K-step is the run-time body's: the 48 MFMAs among the fragment reads, then vmcnt(0), then the split, the ds_writes, the loads of the next
+// tile and the barrier -- with one tile in flight the hints have nothing to move in front of that wait.  Any other pair of forms, the
+// on-load GELU (b_pre == 2) among them, runs the run-time body.  GROUP_PF = 2 (with the changes DESIGN 3s lists) does put the split between
+// the MFMAs and adds nothing the step resolves.
+// Launch bound (256, 2): the compiler keeps the 64 accumulator registers among the VGPRs (164 in all); with (256) alone it moves them to
+// AGPRs (144 + 68) and pays ~1100 v_accvgpr copies over the kernel's bodies: 52.1 us against 50.1, the step 0.7 % slower.
 #ifndef GROUP_PF
 #define GROUP_PF 1
 #endif
@@ -456,7 +470,7 @@ struct GemmGroup {
     int a_pre[GEMM_GROUP_MAX], b_pre[GEMM_GROUP_MAX];   // operand already in split-4 storage (1); B only: 2 = gelu(stored + b_bias) on load
     const float* b_bias[GEMM_GROUP_MAX];
 };
-__global__ void __launch_bounds__(256) k_gemm_group_tt(GemmGroup G) {
+__global__ void __launch_bounds__(256, 2) k_gemm_group_tt(GemmGroup G) {
     CFFM_DYN_SMEM(smem);
     int lin = xcd_linear_id(), p = 0;
 #pragma unroll
@@ -464,6 +478,13 @@ __global__ void __launch_bounds__(256) k_gemm_group_tt(GemmGroup G) {
         if (q + 1 < G.n && lin >= G.wg_end[q]) p = q + 1;
     if (p > 0) lin -= G.wg_end[p - 1];
     const int M = G.M[p], N = G.N[p], ntn = N / 128, ntm = M / 128;
-    gemm_tile<128, 128, 32, true, true, 0, GROUP_PF>(smem, G.A[p], G.B[p], G.C[p], M, N, G.K[p], M, N, N, G.klen, (long)M * N, nullptr,
-                                              nullptr, lin % ntn, (lin / ntn) % ntm, lin / (ntn * ntm), G.a_pre[p] != 0, G.b_pre[p], nullptr, G.b_bias[p]);
+    const int ap = G.a_pre[p] != 0, bp = G.b_pre[p];
+#define GROUP_TILE(PF_, AP_, BP_)                                                                                                          \
+    gemm_tile<128, 128, 32, true, true, 0, PF_, AP_, BP_>(smem, G.A[p], G.B[p], G.C[p], M, N, G.K[p], M, N, N, G.klen, (long)M * N, nullptr, \
+                                                          nullptr, lin % ntn, (lin / ntn) % ntm, lin / (ntn * ntm), ap, bp, nullptr, G.b_bias[p])
+    if (!ap && bp == 1) GROUP_TILE(GROUP_PF, 0, 1);
+    else if (ap && bp == 1) GROUP_TILE(GROUP_PF, 1, 1);
+    else if (!ap && bp == 0) GROUP_TILE(GROUP_PF, 0, 0);
+    else GROUP_TILE(1, -1, -1);
+#undef GROUP_TILE
 }
