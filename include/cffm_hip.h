@@ -630,6 +630,39 @@ int cffm_mit_stage_infer(const cffm_mit_stage_cfg* c, const cffm_mit_block_param
                          const float* conv_nchw /* [B,C,H,W]: patch_embed.proj's output */, float* out_nchw /* [B,C,H,W] */,
                          float* ws, void* stream);
 
+/* ---- added under ABI 13, additive: MiT's overlapping patch embedding as a kernel, and n consecutive stages per call ----
+ * OverlapPatchEmbed.forward in eval mode (csrc/pembed_kernels.h): Conv2d(Cin, Cout, k, stride, padding = k / 2) on x_nchw [B][Cin][H][W],
+ * flatten(2).transpose(1, 2), LayerNorm(Cout) -> out_rows [B][Ho*Wo][Cout], Ho = (H + 2 (k / 2) - k) / stride + 1 and Wo likewise.  A GEMM
+ * on gathered patches: the input and the weight [Cout][Cin][k][k] are read where they lie (no im2col buffer, no repacked weight, no NCHW
+ * copy of the result), taps outside the image contribute exactly zero.  Products: the three-pass bf16 split of the Linear GEMMs (fp32
+ * operands split into bf16 hi + lo, hi.lo + lo.hi + hi.hi, fp32 accumulation); LayerNorm as cffm_ln_rows.  Fixed summation order, no
+ * atomics: the same bits on every call.  No workspace, no allocation, no host round trip.
+ * Limits: (k, stride) = (7, 4) or (3, 2); Cin in 1..4 for k = 7, a multiple of 4 in 4..512 for k = 3; Cout a multiple of 16 in 16..512;
+ * B, H, W >= 1; B*Cin*H*W and B*Ho*Wo*Cout below 2^31; eps finite and >= 0; pointers non-null and 16-byte aligned.  Errors enqueue
+ * nothing and leave the output as it is. */
+int cffm_patch_embed_fwd(const float* x_nchw, const float* w, const float* b, const float* gamma, const float* beta, float* out_rows, int B,
+                         int Cin, int H, int W, int Cout, int k, int stride, float eps, void* stream);
+
+/* n = 1..4 consecutive MiT stages, each WITH its patch embedding, as one call: per stage cffm_patch_embed_fwd's kernel writes the
+ * normalised rows straight into the stage's residual buffer (cffm_nchw_ln_rows does not run), then the blocks and cffm_ln_rows_nchw exactly as
+ * cffm_mit_stage_infer enqueues them.  x_nchw [B, stages[0].Cin, Hin, Win] is stage 0's input, outs[i] (host array of n device pointers)
+ * receives stage i's map [B, cfg.C, cfg.H, cfg.W] and is stage i + 1's input.  Everything is enqueued on `stream` alone: one chain in a
+ * captured graph.  ws: cffm_mit_infer_ws_floats(stages, n) floats = the MAXIMUM over the stages of cffm_mit_stage_infer_ws_floats (the
+ * stages run one after another), 16-byte aligned; every byte of it that is read is written by the same call.
+ * Errors (nothing is enqueued; cffm_mit_infer_ws_floats returns < 0): n outside 1..4, anything cffm_patch_embed_fwd or cffm_mit_stage_infer
+ * refuses, a cfg whose (H, W, C) is not the convolution's output shape, a stage whose input is not the previous stage's output,
+ * outputs that alias each other or the input. */
+typedef struct {
+    cffm_mit_stage_cfg cfg;                         /* C = the convolution's Cout, (H, W) = its output size */
+    int Cin, Hin, Win, k, stride;                   /* patch_embed.proj: its input map and (kernel, stride) */
+    const float *conv_w, *conv_b;                   /* patch_embed.proj weight [C][Cin][k][k] and bias [C] */
+    const float *embed_g, *embed_b, *out_g, *out_b; /* patch_embed.norm and norm_i */
+    const cffm_mit_block_params* blocks;            /* host [cfg.depth] */
+} cffm_mit_stage;
+long cffm_mit_infer_ws_floats(const cffm_mit_stage* stages /* host [n] */, int n);          /* < 0: refused */
+int cffm_mit_infer(const cffm_mit_stage* stages /* host [n] */, int n, const float* x_nchw, float* const* outs /* host [n] */, float* ws,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

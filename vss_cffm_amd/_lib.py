@@ -55,8 +55,15 @@ class MitStageCfg(C.Structure):
                 + [(n, cf) for n in ('scale', 'eps_embed', 'eps_block', 'eps_sr', 'eps_out')])
 
 
+class MitStage(C.Structure):
+    """cffm_mit_stage"""
+    _fields_ = ([('cfg', MitStageCfg)] + [(n, ci) for n in ('Cin', 'Hin', 'Win', 'k', 'stride')]
+                + [(n, vp) for n in ('conv_w', 'conv_b', 'embed_g', 'embed_b', 'out_g', 'out_b')] + [('blocks', C.POINTER(MitBlockPtrs))])
+
+
 GP, BP = C.POINTER(Geom), C.POINTER(BlockPtrs)
 MBP, MCP = C.POINTER(MitBlockPtrs), C.POINTER(MitStageCfg)
+MSP = C.POINTER(MitStage)
 GTP = C.POINTER(GtcPtrs)
 CBP = C.POINTER(CffaBwdBlock)
 P4 = vp * 4
@@ -171,6 +178,9 @@ SIGNATURES = {
     'cffm_ln_rows_nchw': (ci, [vp, vp, vp, vp, ci, ci, ci, ci, cf, vp]),
     'cffm_mit_stage_infer_ws_floats': (cl, [MCP]),
     'cffm_mit_stage_infer': (ci, [MCP, MBP, vp, vp, vp, vp, vp, vp, vp, vp]),
+    'cffm_patch_embed_fwd': (ci, [vp] * 6 + [ci] * 7 + [cf, vp]),
+    'cffm_mit_infer_ws_floats': (cl, [MSP, ci]),
+    'cffm_mit_infer': (ci, [MSP, ci, vp, C.POINTER(vp), vp, vp]),
 }
 
 

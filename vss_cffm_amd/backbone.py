@@ -27,6 +27,11 @@ LayerNorm, every block, the stage's LayerNorm and the change to an NCHW map -- a
 cffm_mit_stage_infer), the Linear layers as the library's bf16-split GEMMs.  ``'torch'`` (the default) is the path described above.  A
 stage takes the call only when nothing would be differentiated and it is inside the library's limits (`_stage_fused`); any other stage
 takes the path above, stage by stage and silently.  `dwconv_impl`, `attn_impl` and `sr_impl` have no say in the stage call.
+
+With ``MixVisionTransformer.embed_impl = 'hip'`` on top of ``stage_impl = 'hip'`` the patch-embedding convolutions join in: every maximal
+run of consecutive stages that take the stage call and whose ``patch_embed.proj`` is inside the limits of the library's patch-embedding
+kernel goes out as ONE call (``ops.mit_infer`` -> cffm_mit_infer) -- for ``mit_b0`` .. ``mit_b5`` the whole evaluation forward, with one
+workspace (the largest stage's) and the same bits on every call.  ``'torch'`` (the default) leaves the convolutions to stock Conv2d.
 """
 import math
 from functools import partial
@@ -36,7 +41,8 @@ import torch.nn as nn
 
 from . import _lib
 from .checkpoint import load_reference_checkpoint
-from .ops import dwconv_gelu, mit_stage_cfg, mit_stage_infer, mit_stage_supported, mit_stage_tensors, sr_reduce, sr_reduce_supported, sra_attention
+from .ops import (dwconv_gelu, mit_infer, mit_stage_cfg, mit_stage_infer, mit_stage_supported, mit_stage_tensors, mit_stages, patch_embed_out_hw,
+                  patch_embed_supported, sr_reduce, sr_reduce_supported, sra_attention)
 from .registry import BACKBONES
 
 
@@ -219,6 +225,10 @@ class MixVisionTransformer(nn.Module):
     # libcffm_hip.so for fp32 GPU tensors inside the library's limits (it raises when the library is missing); 'torch': the modules'
     # own forward, what everything else gets -- and the default: whether the call is faster is measured, not assumed
     stage_impl = 'torch'
+    # 'hip' (with stage_impl = 'hip'): consecutive stages that take the stage call and whose patch-embedding convolution is inside the
+    # library's limits are ONE call, convolutions included; 'torch': stock Conv2d in front of every stage call -- the default
+    # (DESIGN section 3t has the measurements: not faster at model level)
+    embed_impl = 'torch'
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dims=[64, 128, 256, 512], num_heads=[1, 2, 4, 8],
                  mlp_ratios=[4, 4, 4, 4], qkv_bias=False, qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.,
@@ -275,6 +285,10 @@ class MixVisionTransformer(nn.Module):
 
     def _stage_fused(self, i, x):
         """whether stage i takes the one-call inference path for this input (the convolution's output shape decides the sizes)"""
+        return self._stage_fused_at(i, tuple(x.shape), x)
+
+    def _stage_fused_at(self, i, shape, x):
+        """_stage_fused for an input of `shape` that is like x in everything else (device, dtype, requires_grad)"""
         pe, blocks, norm = getattr(self, 'patch_embed%d' % i), getattr(self, 'block%d' % i), getattr(self, 'norm%d' % i)
         if self.stage_impl != 'hip' or not (x.is_cuda or _lib._override is not None) or x.dtype != torch.float32 or len(blocks) == 0:
             return False
@@ -304,8 +318,44 @@ class MixVisionTransformer(nn.Module):
         conv = pe.proj
         if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in ts + list(conv.parameters()))):
             return False
-        hw = [(x.shape[2 + d] + 2 * conv.padding[d] - conv.dilation[d] * (conv.kernel_size[d] - 1) - 1) // conv.stride[d] + 1 for d in (0, 1)]
-        return mit_stage_supported(mit_stage_cfg((x.shape[0], conv.out_channels, hw[0], hw[1]), blocks, pe.norm, norm))
+        hw = [(shape[2 + d] + 2 * conv.padding[d] - conv.dilation[d] * (conv.kernel_size[d] - 1) - 1) // conv.stride[d] + 1 for d in (0, 1)]
+        return mit_stage_supported(mit_stage_cfg((shape[0], conv.out_channels, hw[0], hw[1]), blocks, pe.norm, norm))
+
+    def _embed_fused_at(self, i, shape, x):
+        """whether stage i's patch-embedding convolution, on an input of `shape` that is like x in everything else, is inside the limits
+        of the library's kernel (asked only of a stage that passes _stage_fused_at)"""
+        conv = getattr(self, 'patch_embed%d' % i).proj
+        if self.embed_impl != 'hip' or not patch_embed_supported(conv, shape):
+            return False
+        return not any(t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous() or t.data_ptr() % 16 for t in (conv.weight, conv.bias))
+
+    def _run_from(self, i, x):
+        """the maximal run of consecutive stages from stage i on that go out as one cffm_mit_infer call for this input (may be empty), and
+        the shapes of their outputs"""
+        run, shapes, shape = [], [], tuple(x.shape)
+        while i + len(run) <= 4:
+            j = i + len(run)
+            if not (self._stage_fused_at(j, shape, x) and self._embed_fused_at(j, shape, x)):
+                break
+            conv = getattr(self, 'patch_embed%d' % j).proj
+            shape = (shape[0], conv.out_channels) + patch_embed_out_hw(conv, shape[2], shape[3])
+            run.append(j)
+            shapes.append(shape)
+        return run, shapes
+
+    def _run_ws(self, run, x, shapes, stages):
+        """the workspace of a run's call: one per (first stage, device), the last shapes'; a plain attribute as _stage_workspaces"""
+        key = (run[0], x.device, tuple(x.shape)) + tuple(shapes)
+        cache = self.__dict__.setdefault('_run_workspaces', {})
+        if key not in cache:
+            arr, keep, _ = mit_stages(x.shape, stages)
+            need = _lib.get().cffm_mit_infer_ws_floats(arr, len(stages))
+            if need < 0:
+                raise _lib.CffmError('libcffm_hip: %s' % _lib.get().cffm_last_error().decode())
+            for k in [k for k in cache if k[0] == run[0] and k[1] == x.device]:
+                del cache[k]
+            cache[key] = torch.empty(need, dtype=torch.float32, device=x.device)
+        return cache[key]
 
     def _stage_ws(self, i, y):
         """the stage call's workspace: allocated once per (stage, device, cfg), kept on the module as a plain attribute (no buffer, no
@@ -326,7 +376,18 @@ class MixVisionTransformer(nn.Module):
     def forward_features(self, x):
         B = x.shape[0]
         outs = []
+        skip = 0
         for i in range(1, 5):
+            if skip:                                  # (part of the run a call below has finished)
+                skip -= 1
+                continue
+            run, shapes = self._run_from(i, x) if self.embed_impl == 'hip' and self.stage_impl == 'hip' else ([], [])
+            if run:
+                stages = [(getattr(self, 'patch_embed%d' % j), getattr(self, 'block%d' % j), getattr(self, 'norm%d' % j)) for j in run]
+                with torch.no_grad():
+                    outs += mit_infer(x, stages, ws=self._run_ws(run, x, shapes, stages))
+                x, skip = outs[-1], len(run) - 1
+                continue
             if self._stage_fused(i, x):
                 pe = getattr(self, 'patch_embed%d' % i)
                 with torch.no_grad():

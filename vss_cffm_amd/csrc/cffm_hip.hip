@@ -14,6 +14,7 @@
 #include "sra_kernels.h"
 #include "srln_kernels.h"
 #include "mitln_kernels.h"
+#include "pembed_kernels.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -3028,6 +3029,132 @@ static int mit_cfg_check(const char* who, const cffm_mit_stage_cfg* c, MitWs* Wo
     if (Wo) *Wo = W;
     return 0;
 }
+// the pointers of a stage: everything cffm_mit_stage_infer and cffm_mit_infer read besides the maps and the workspace
+static int mit_ptr_check(const char* who, const cffm_mit_stage_cfg* c, const cffm_mit_block_params* blocks, const float* embed_g, const float* embed_b,
+                         const float* out_g, const float* out_b) {
+    REQUIRE(blocks, "%s: null block parameters", who);
+    REQUIRE(aligned16(embed_g) && aligned16(embed_b) && aligned16(out_g) && aligned16(out_b),
+            "%s: embed_g / embed_b / out_g / out_b must be non-null and 16-byte aligned", who);
+    const int s = c->sr_ratio;
+    for (int i = 0; i < c->depth; ++i) {
+        const cffm_mit_block_params& p = blocks[i];
+        const float* need[] = {p.n1_g, p.n1_b, p.q_w, p.kv_w, p.proj_w, p.proj_b, p.n2_g, p.n2_b, p.fc1_w, p.fc1_b, p.dw_w, p.dw_b, p.fc2_w, p.fc2_b};
+        for (const float* t : need) REQUIRE(aligned16(t), "%s: block %d: a parameter is null or not 16-byte aligned", who, i);
+        REQUIRE((uintptr_t)p.q_b % 16 == 0 && (uintptr_t)p.kv_b % 16 == 0, "%s: block %d: q_b / kv_b not 16-byte aligned", who, i);
+        const float* sr[] = {p.sr_w, p.sr_b, p.srn_g, p.srn_b};
+        for (const float* t : sr)
+            REQUIRE(s > 1 ? aligned16(t) : !t, "%s: block %d: sr_w / sr_b / srn_g / srn_b must be %s", who, i,
+                    s > 1 ? "non-null and 16-byte aligned (sr_ratio > 1)" : "null (sr_ratio == 1)");
+    }
+    return 0;
+}
+// a stage behind its embedding (checked arguments; the normalised rows of the embedding are in ws + W.xa): the blocks, then norm_i + the change
+// to an NCHW map.  Shared by cffm_mit_stage_infer and cffm_mit_infer.
+static int mit_stage_body(const char* who, const cffm_mit_stage_cfg* c, const MitWs& W, const cffm_mit_block_params* blocks, const float* out_g,
+                          const float* out_b, float* out_nchw, float* ws, hipStream_t st) {
+    const int s = c->sr_ratio;
+    const int B = c->B, H = c->H, Wd = c->W, C = c->C, hid = c->hidden, N = W.N, Nk = W.Nk, M = (int)W.M, Mk = B * Nk;
+    float *xa = ws + W.xa, *xb = ws + W.xb, *z = ws + W.z, *q = ws + W.q, *r = ws + W.r, *kv = ws + W.kv, *h = ws + W.h, *a = ws + W.a;
+    SrGeom SG = {};
+    if (s > 1) TRY(srln_check(who, B, H, Wd, C, s, c->eps_sr, &SG));
+    for (int i = 0; i < c->depth; ++i) {
+        const cffm_mit_block_params& p = blocks[i];
+        mln_launch(0, st, xa, p.n1_g, p.n1_b, z, W.M, 0, C, 1, c->eps_block);
+        bool bad = gemm_split_launch<false, false>(z, p.q_w, q, M, C, C, C, C, C, 1, st, p.q_b);
+        if (s > 1) srln_fwd_launch(s, st, z, p.sr_w, p.sr_b, p.srn_g, p.srn_b, r, nullptr, nullptr, SG, c->eps_sr);
+        bad = bad || gemm_split_launch<false, false>(s > 1 ? r : z, p.kv_w, kv, Mk, 2 * C, C, C, C, 2 * C, 1, st, p.kv_b);
+        sra_fwd_launch(q, kv, z, nullptr, B, N, Nk, c->heads, C / c->heads, c->scale, st);
+        bad = bad || gemm_split_launch<false, false, 2>(z, p.proj_w, xb, M, C, C, C, C, C, 1, st, p.proj_b, xa);
+        mln_launch(0, st, xb, p.n2_g, p.n2_b, z, W.M, 0, C, 1, c->eps_block);
+        bad = bad || gemm_split_launch<false, false>(z, p.fc1_w, h, M, hid, C, C, C, hid, 1, st, p.fc1_b);
+        dwg_fwd_launch(h, p.dw_w, p.dw_b, a, B, H, Wd, hid, st);
+        bad = bad || gemm_split_launch<false, false, 2>(a, p.fc2_w, xa, M, C, hid, hid, hid, C, 1, st, p.fc2_b, xb);
+        REQUIRE(!bad, "%s: gemm failed", who);
+    }
+    mln_launch(2, st, xa, out_g, out_b, out_nchw, W.M, B, C, N, c->eps_out);
+    return 0;
+}
+
+// ---- the overlapping patch embedding (pembed_kernels.h)
+static int pemb_check(const char* who, int B, int Cin, int H, int W, int Cout, int k, int stride, float eps, PembGeom* Go) {
+    REQUIRE((k == 7 && stride == 4) || (k == 3 && stride == 2), "%s: (k, stride) = (%d, %d) is neither (7, 4) nor (3, 2)", who, k, stride);
+    REQUIRE(k == 7 ? (Cin >= 1 && Cin <= 4) : (Cin >= 4 && Cin <= 512 && Cin % 4 == 0),
+            "%s: Cin=%d must be %s", who, Cin, k == 7 ? "in 1..4 (k = 7)" : "a multiple of 4 in 4..512 (k = 3)");
+    REQUIRE(Cout >= 16 && Cout <= 512 && Cout % 16 == 0, "%s: Cout=%d must be a multiple of 16 in 16..512", who, Cout);
+    REQUIRE(B >= 1 && H >= 1 && W >= 1, "%s: bad sizes B=%d H=%d W=%d", who, B, H, W);
+    REQUIRE(eps >= 0.f && eps < INFINITY, "%s: eps %g must be finite and not negative", who, (double)eps);
+    PembGeom G;
+    G.B = B; G.Cin = Cin; G.H = H; G.W = W; G.Cout = Cout; G.K = Cin * k * k;
+    G.Ho = (H + 2 * (k / 2) - k) / stride + 1;
+    G.Wo = (W + 2 * (k / 2) - k) / stride + 1;
+    G.tpr = (G.Wo + 15) / 16;
+    const long nin = (long)B * Cin * H * W, nout = (long)B * G.Ho * G.Wo * Cout;
+    REQUIRE(nin < (1L << 31) && nout < (1L << 31), "%s: B*Cin*H*W = %ld and B*Ho*Wo*Cout = %ld must be below 2^31", who, nin, nout);
+    if (Go) *Go = G;
+    return 0;
+}
+// column tiles per pass of k_pembed_fwd: the largest of (8 with one tile per workgroup,) 5, 4, 2, 1 that divides Cout / 16
+static int pemb_ncw(int Cout, int nt) {
+    const int nc = Cout / 16;
+    return nt == 1 && nc % 8 == 0 ? 8 : nc % 5 == 0 ? 5 : nc % 4 == 0 ? 4 : nc % 2 == 0 ? 2 : 1;
+}
+// tiles per workgroup of 8 waves (pembed_kernels.h): Cout <= 64: 8 tiles, a wave each | Cout <= 128: 4 tiles, two waves each | wider: one
+// tile, its K split over the 8 waves
+template <int KS, int ST, int NT, int WAVES>
+static void pemb_go_nt(hipStream_t st, const float* x, const float* w, const float* b, const float* gamma, const float* beta, float* out,
+                       const PembGeom& G, float eps) {
+    const unsigned grid = (unsigned)(((long)G.B * G.Ho * G.tpr + NT - 1) / NT);
+#define PEMB_FWD(NCW_) CFFM_LAUNCH((k_pembed_fwd<KS, ST, NCW_, NT, WAVES>), (grid), (WAVES * 64), 0, st, x, w, b, gamma, beta, out, G, eps)
+    switch (pemb_ncw(G.Cout, NT)) {
+        case 8: if constexpr (NT == 1) PEMB_FWD(8); break;       // (Cout = 512 at stage 4: 218 us against 275 with NCW = 4)
+        case 5: PEMB_FWD(5); break;
+        case 4: PEMB_FWD(4); break;
+        case 2: PEMB_FWD(2); break;
+        default: PEMB_FWD(1); break;
+    }
+#undef PEMB_FWD
+}
+template <int KS, int ST>
+static void pemb_go(hipStream_t st, const float* x, const float* w, const float* b, const float* gamma, const float* beta, float* out,
+                    const PembGeom& G, float eps) {
+    if (G.Cout <= 64) pemb_go_nt<KS, ST, 8, 8>(st, x, w, b, gamma, beta, out, G, eps);
+    else if (G.Cout <= 128) pemb_go_nt<KS, ST, 4, 8>(st, x, w, b, gamma, beta, out, G, eps);
+    else pemb_go_nt<KS, ST, 1, 8>(st, x, w, b, gamma, beta, out, G, eps);
+}
+// (checked arguments -> the launch: shared with cffm_mit_infer)
+static void pemb_launch(int k, hipStream_t st, const float* x, const float* w, const float* b, const float* gamma, const float* beta, float* out,
+                        const PembGeom& G, float eps) {
+    if (k == 7) pemb_go<7, 4>(st, x, w, b, gamma, beta, out, G, eps);
+    else pemb_go<3, 2>(st, x, w, b, gamma, beta, out, G, eps);
+}
+// n consecutive stages: every limit of both parts, the chain of shapes, and the workspace (the maximum over the stages: they run one
+// after another).  W / PG (host [n]) may be null.
+static int mit_infer_check(const char* who, const cffm_mit_stage* stages, int n, MitWs* W, PembGeom* PG, long* need) {
+    REQUIRE(stages, "%s: null stage list", who);
+    REQUIRE(n >= 1 && n <= 4, "%s: n=%d stages: 1..4 expected", who, n);
+    long most = 0;
+    for (int i = 0; i < n; ++i) {
+        const cffm_mit_stage& s = stages[i];
+        const cffm_mit_stage_cfg& c = s.cfg;
+        MitWs Wi;
+        PembGeom Gi;
+        TRY(mit_cfg_check(who, &c, &Wi));
+        TRY(pemb_check(who, c.B, s.Cin, s.Hin, s.Win, c.C, s.k, s.stride, c.eps_embed, &Gi));
+        REQUIRE(Gi.Ho == c.H && Gi.Wo == c.W, "%s: stage %d: cfg (H, W) = (%d, %d) is not the convolution's output (%d, %d)", who, i, c.H, c.W,
+                Gi.Ho, Gi.Wo);
+        if (i > 0) {
+            const cffm_mit_stage_cfg& p = stages[i - 1].cfg;
+            REQUIRE(c.B == p.B && s.Cin == p.C && s.Hin == p.H && s.Win == p.W,
+                    "%s: stage %d: the input [%d,%d,%d,%d] is not stage %d's output [%d,%d,%d,%d]", who, i, c.B, s.Cin, s.Hin, s.Win, i - 1, p.B,
+                    p.C, p.H, p.W);
+        }
+        most = std::max(most, Wi.total);
+        if (W) W[i] = Wi;
+        if (PG) PG[i] = Gi;
+    }
+    *need = most;
+    return 0;
+}
 extern "C" {
 int cffm_ln_rows(const float* x, const float* gamma, const float* beta, float* out, long M, int C, float eps, void* stream) {
     TRY(mln_check("ln_rows", C, eps));
@@ -3062,44 +3189,57 @@ int cffm_mit_stage_infer(const cffm_mit_stage_cfg* c, const cffm_mit_block_param
                          const float* out_g, const float* out_b, const float* conv_nchw, float* out_nchw, float* ws, void* stream) {
     MitWs W;
     TRY(mit_cfg_check("mit_stage_infer", c, &W));
-    REQUIRE(blocks, "mit_stage_infer: null block parameters");
-    REQUIRE(aligned16(embed_g) && aligned16(embed_b) && aligned16(out_g) && aligned16(out_b) && aligned16(conv_nchw) &&
-            aligned16(out_nchw) && aligned16(ws),
-            "mit_stage_infer: embed_g / embed_b / out_g / out_b / conv_nchw / out_nchw / ws must be non-null and 16-byte aligned");
+    TRY(mit_ptr_check("mit_stage_infer", c, blocks, embed_g, embed_b, out_g, out_b));
+    REQUIRE(aligned16(conv_nchw) && aligned16(out_nchw) && aligned16(ws), "mit_stage_infer: conv_nchw / out_nchw / ws must be non-null and 16-byte aligned");
     REQUIRE(conv_nchw != out_nchw, "mit_stage_infer: input and output must not alias");
-    const int s = c->sr_ratio;
-    for (int i = 0; i < c->depth; ++i) {
-        const cffm_mit_block_params& p = blocks[i];
-        const float* need[] = {p.n1_g, p.n1_b, p.q_w, p.kv_w, p.proj_w, p.proj_b, p.n2_g, p.n2_b, p.fc1_w, p.fc1_b, p.dw_w, p.dw_b, p.fc2_w, p.fc2_b};
-        for (const float* t : need) REQUIRE(aligned16(t), "mit_stage_infer: block %d: a parameter is null or not 16-byte aligned", i);
-        REQUIRE((uintptr_t)p.q_b % 16 == 0 && (uintptr_t)p.kv_b % 16 == 0, "mit_stage_infer: block %d: q_b / kv_b not 16-byte aligned", i);
-        const float* sr[] = {p.sr_w, p.sr_b, p.srn_g, p.srn_b};
-        for (const float* t : sr)
-            REQUIRE(s > 1 ? aligned16(t) : !t, "mit_stage_infer: block %d: sr_w / sr_b / srn_g / srn_b must be %s", i,
-                    s > 1 ? "non-null and 16-byte aligned (sr_ratio > 1)" : "null (sr_ratio == 1)");
+    hipStream_t st = (hipStream_t)stream;
+    mln_launch(1, st, conv_nchw, embed_g, embed_b, ws + W.xa, W.M, c->B, c->C, W.N, c->eps_embed);
+    TRY(mit_stage_body("mit_stage_infer", c, W, blocks, out_g, out_b, out_nchw, ws, st));
+    CHECK_LAUNCH("mit_stage_infer");
+    return 0;
+}
+
+int cffm_patch_embed_fwd(const float* x_nchw, const float* w, const float* b, const float* gamma, const float* beta, float* out_rows, int B,
+                         int Cin, int H, int W, int Cout, int k, int stride, float eps, void* stream) {
+    PembGeom G;
+    TRY(pemb_check("patch_embed_fwd", B, Cin, H, W, Cout, k, stride, eps, &G));
+    REQUIRE(aligned16(x_nchw) && aligned16(w) && aligned16(b) && aligned16(gamma) && aligned16(beta) && aligned16(out_rows),
+            "patch_embed_fwd: x_nchw / w / b / gamma / beta / out_rows must be non-null and 16-byte aligned");
+    REQUIRE((const float*)out_rows != x_nchw, "patch_embed_fwd: input and output must not alias");
+    pemb_launch(k, (hipStream_t)stream, x_nchw, w, b, gamma, beta, out_rows, G, eps);
+    CHECK_LAUNCH("patch_embed_fwd");
+    return 0;
+}
+
+long cffm_mit_infer_ws_floats(const cffm_mit_stage* stages, int n) {
+    long need = 0;
+    return mit_infer_check("mit_infer_ws_floats", stages, n, nullptr, nullptr, &need) ? -1 : need;
+}
+int cffm_mit_infer(const cffm_mit_stage* stages, int n, const float* x_nchw, float* const* outs, float* ws, void* stream) {
+    MitWs W[4];
+    PembGeom PG[4];
+    long need = 0;
+    TRY(mit_infer_check("mit_infer", stages, n, W, PG, &need));
+    REQUIRE(outs, "mit_infer: null output list");
+    REQUIRE(aligned16(x_nchw) && aligned16(ws), "mit_infer: x_nchw / ws must be non-null and 16-byte aligned");
+    for (int i = 0; i < n; ++i) {
+        const cffm_mit_stage& s = stages[i];
+        REQUIRE(aligned16(outs[i]), "mit_infer: stage %d: the output must be non-null and 16-byte aligned", i);
+        REQUIRE((const float*)outs[i] != x_nchw, "mit_infer: stage %d: input and output must not alias", i);
+        for (int j = 0; j < i; ++j) REQUIRE(outs[i] != outs[j], "mit_infer: outputs %d and %d alias", j, i);
+        REQUIRE(aligned16(s.conv_w) && aligned16(s.conv_b), "mit_infer: stage %d: conv_w / conv_b must be non-null and 16-byte aligned", i);
+        TRY(mit_ptr_check("mit_infer", &s.cfg, s.blocks, s.embed_g, s.embed_b, s.out_g, s.out_b));
     }
     hipStream_t st = (hipStream_t)stream;
-    const int B = c->B, H = c->H, Wd = c->W, C = c->C, hid = c->hidden, N = W.N, Nk = W.Nk, M = (int)W.M, Mk = B * Nk;
-    float *xa = ws + W.xa, *xb = ws + W.xb, *z = ws + W.z, *q = ws + W.q, *r = ws + W.r, *kv = ws + W.kv, *h = ws + W.h, *a = ws + W.a;
-    SrGeom SG = {};
-    if (s > 1) TRY(srln_check("mit_stage_infer", B, H, Wd, C, s, c->eps_sr, &SG));
-    mln_launch(1, st, conv_nchw, embed_g, embed_b, xa, W.M, B, C, N, c->eps_embed);
-    for (int i = 0; i < c->depth; ++i) {
-        const cffm_mit_block_params& p = blocks[i];
-        mln_launch(0, st, xa, p.n1_g, p.n1_b, z, W.M, 0, C, 1, c->eps_block);
-        bool bad = gemm_split_launch<false, false>(z, p.q_w, q, M, C, C, C, C, C, 1, st, p.q_b);
-        if (s > 1) srln_fwd_launch(s, st, z, p.sr_w, p.sr_b, p.srn_g, p.srn_b, r, nullptr, nullptr, SG, c->eps_sr);
-        bad = bad || gemm_split_launch<false, false>(s > 1 ? r : z, p.kv_w, kv, Mk, 2 * C, C, C, C, 2 * C, 1, st, p.kv_b);
-        sra_fwd_launch(q, kv, z, nullptr, B, N, Nk, c->heads, C / c->heads, c->scale, st);
-        bad = bad || gemm_split_launch<false, false, 2>(z, p.proj_w, xb, M, C, C, C, C, C, 1, st, p.proj_b, xa);
-        mln_launch(0, st, xb, p.n2_g, p.n2_b, z, W.M, 0, C, 1, c->eps_block);
-        bad = bad || gemm_split_launch<false, false>(z, p.fc1_w, h, M, hid, C, C, C, hid, 1, st, p.fc1_b);
-        dwg_fwd_launch(h, p.dw_w, p.dw_b, a, B, H, Wd, hid, st);
-        bad = bad || gemm_split_launch<false, false, 2>(a, p.fc2_w, xa, M, C, hid, hid, hid, C, 1, st, p.fc2_b, xb);
-        REQUIRE(!bad, "mit_stage_infer: gemm failed");
+    const float* in = x_nchw;
+    for (int i = 0; i < n; ++i) {
+        const cffm_mit_stage& s = stages[i];
+        // the embedding's normalised rows go straight into the residual buffer the first block reads
+        pemb_launch(s.k, st, in, s.conv_w, s.conv_b, s.embed_g, s.embed_b, ws + W[i].xa, PG[i], s.cfg.eps_embed);
+        TRY(mit_stage_body("mit_infer", &s.cfg, W[i], s.blocks, s.out_g, s.out_b, outs[i], ws, st));
+        in = outs[i];
     }
-    mln_launch(2, st, xa, out_g, out_b, out_nchw, W.M, B, C, N, c->eps_out);
-    CHECK_LAUNCH("mit_stage_infer");
+    CHECK_LAUNCH("mit_infer");
     return 0;
 }
 

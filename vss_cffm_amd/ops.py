@@ -1676,3 +1676,145 @@ def mit_stage_infer(conv_out, embed_norm, blocks, out_norm, ws=None, out=None):
             setattr(structs[i], f, t.data_ptr() if t is not None else None)
     _lib.check(lib.cffm_mit_stage_infer(C.byref(cfg), structs, *(_ptr(t) for t in tensors[-4:]), _ptr(x), _ptr(out), _ptr(ws), _stream(x)), lib)
     return out
+
+
+# ---------------------------------------------------------------------------------------------- the overlapping patch embedding + n stages per call (inference)
+# The limits of cffm_patch_embed_fwd: a copy of pemb_check in csrc/cffm_hip.hip (stated in include/cffm_hip.h); change both together.
+PEMB_KERNELS = ((7, 4), (3, 2))
+
+
+def patch_embed_out_hw(proj, h, w):
+    """the output size of a Conv2d `proj` on an h x w map"""
+    return tuple((s + 2 * proj.padding[d] - proj.dilation[d] * (proj.kernel_size[d] - 1) - 1) // proj.stride[d] + 1 for d, s in ((0, h), (1, w)))
+
+
+def patch_embed_supported(proj, shape):
+    """whether the Conv2d `proj` on an fp32 input of `shape` = (B, Cin, H, W) is inside the limits of cffm_patch_embed_fwd (the module's
+    configuration and the sizes; where its tensors lie is the caller's to check)"""
+    if type(proj) is not torch.nn.Conv2d or len(shape) != 4:
+        return False
+    b, cin, h, w = (int(v) for v in shape)
+    k, s = proj.kernel_size[0], proj.stride[0]
+    if (tuple(proj.kernel_size) != (k, k) or tuple(proj.stride) != (s, s) or (k, s) not in PEMB_KERNELS or proj.padding != (k // 2, k // 2)
+            or tuple(proj.dilation) != (1, 1) or proj.groups != 1 or proj.bias is None or proj.padding_mode != 'zeros' or proj.in_channels != cin):
+        return False
+    cout = proj.out_channels
+    if not (1 <= cin <= 4 if k == 7 else (cin % 4 == 0 and 4 <= cin <= 512)) or cout % 16 or not LN_MIN_C <= cout <= LN_MAX_C:
+        return False
+    if b < 1 or h < 1 or w < 1:
+        return False
+    ho, wo = patch_embed_out_hw(proj, h, w)
+    return b * cin * h * w < 2 ** 31 and b * ho * wo * cout < 2 ** 31
+
+
+def _pemb_operands(what, x, proj, norm):
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise _lib.CffmError('%s: x must be a [B,Cin,H,W] tensor' % what)
+    if type(proj) is not torch.nn.Conv2d or proj.bias is None or norm.weight is None or norm.bias is None:
+        raise _lib.CffmError('%s: a Conv2d with a bias and a LayerNorm with weight and bias expected' % what)
+    ts = (x, proj.weight, proj.bias, norm.weight, norm.bias)
+    for t in ts:
+        _require_device(t, what)
+        if t.device != x.device:
+            raise _lib.CffmError('%s: every tensor must be on %s' % (what, x.device))
+    _infer_only(ts, what)
+    if (tuple(proj.kernel_size) != (proj.kernel_size[0],) * 2 or tuple(proj.stride) != (proj.stride[0],) * 2 or tuple(proj.dilation) != (1, 1)
+            or proj.groups != 1 or proj.padding != (proj.kernel_size[0] // 2,) * 2 or proj.padding_mode != 'zeros'
+            or proj.in_channels != x.shape[1] or tuple(norm.normalized_shape) != (proj.out_channels,)):
+        raise _lib.CffmError('%s: a square Conv2d(Cin, Cout, k, stride, padding=k // 2) without dilation or groups, on x [B,Cin,H,W], and '
+                             'LayerNorm(Cout) expected' % what)
+    return tuple(_sra_operand(t.detach()) for t in ts)
+
+
+def patch_embed(x, proj, norm, out=None):
+    """``OverlapPatchEmbed.forward`` in eval mode as one kernel (``cffm_patch_embed_fwd``): norm(proj(x).flatten(2).transpose(1, 2)) of an
+    fp32 map x [B,Cin,H,W] -> (token rows [B, Ho*Wo, Cout], Ho, Wo).  `proj`: Conv2d(Cin, Cout, k, stride, padding=k // 2) with (k, stride) =
+    (7, 4) or (3, 2) and a bias, `norm`: LayerNorm(Cout); both are read where they lie.  The products are three-pass bf16-split (the
+    accuracy class of the library's Linear GEMMs); the same bits on every call.  Inference only: it raises when an input or a parameter
+    requires grad while grad mode is on."""
+    xs, w, b, g, beta = _pemb_operands('patch_embed', x, proj, norm)
+    bsz, cin, h, wd = xs.shape
+    ho, wo = patch_embed_out_hw(proj, h, wd)
+    cout = proj.out_channels
+    out = _ln_out('patch_embed', out, (bsz, max(ho, 0) * max(wo, 0), cout), xs)
+    lib = _lib.get()
+    _lib.check(lib.cffm_patch_embed_fwd(_ptr(xs), _ptr(w), _ptr(b), _ptr(g), _ptr(beta), _ptr(out), bsz, cin, h, wd, cout,
+                                        int(proj.kernel_size[0]), int(proj.stride[0]), float(norm.eps), _stream(xs)), lib)
+    return out, ho, wo
+
+
+def mit_stages(shape, stages):
+    """(the cffm_mit_stage array of `stages` on an input of `shape` = (B, Cin, H, W), the objects it points into, the output shapes);
+    `stages`: (patch_embed, blocks, out_norm) per stage, patch_embed with .proj and .norm"""
+    b, cin, h, w = (int(v) for v in shape)
+    arr, keep, shapes = (_lib.MitStage * len(stages))(), [], []
+    n = len(_MIT_FIELDS)
+    for i, (pe, blocks, out_norm) in enumerate(stages):
+        blocks = list(blocks)
+        if not blocks:
+            raise _lib.CffmError('mit_infer: a stage needs at least one block')
+        ho, wo = patch_embed_out_hw(pe.proj, h, w)
+        cout = int(pe.proj.out_channels)
+        tensors = mit_stage_tensors(blocks, pe.norm, out_norm)
+        structs = (_lib.MitBlockPtrs * len(blocks))()
+        for j in range(len(blocks)):
+            for f, t in zip(_MIT_FIELDS, tensors[j * n:(j + 1) * n]):
+                setattr(structs[j], f, t.data_ptr() if t is not None else None)
+        s = arr[i]
+        s.cfg = mit_stage_cfg((b, cout, ho, wo), blocks, pe.norm, out_norm)
+        s.Cin, s.Hin, s.Win, s.k, s.stride = cin, h, w, int(pe.proj.kernel_size[0]), int(pe.proj.stride[0])
+        s.conv_w, s.conv_b = pe.proj.weight.data_ptr(), pe.proj.bias.data_ptr() if pe.proj.bias is not None else None
+        s.embed_g, s.embed_b, s.out_g, s.out_b = (t.data_ptr() if t is not None else None for t in tensors[-4:])
+        s.blocks = structs
+        keep.append((structs, tensors))
+        shapes.append((b, cout, ho, wo))
+        cin, h, w = cout, ho, wo
+    return arr, keep, shapes
+
+
+def mit_infer(x, stages, ws=None, outs=None):
+    """n = 1..4 consecutive MiT stages in eval mode, patch embeddings included, as ONE library call (``cffm_mit_infer``): x [B,Cin,H,W] fp32
+    -> the list of the stages' NCHW maps.  `stages`: (patch_embed, blocks, out_norm) per stage -- an OverlapPatchEmbed (``.proj``,
+    ``.norm``), the stage's Block modules, its final LayerNorm; every parameter is read where it lies (fp32, contiguous, 16-byte aligned).
+    ``ws`` / ``outs``: optional caller-owned workspace (``cffm_mit_infer_ws_floats`` floats: the largest stage's, not the sum) and results,
+    e.g. the static buffers of a captured graph.  Everything goes to the current stream as a single chain.  Inference only: it raises when
+    an input or a parameter requires grad while grad mode is on."""
+    lib = _lib.get()
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise _lib.CffmError('mit_infer: x must be a [B,Cin,H,W] tensor')
+    _require_device(x, 'mit_infer x')
+    stages = [(pe, list(blocks), norm) for pe, blocks, norm in stages]
+    if not 1 <= len(stages) <= 4:
+        raise _lib.CffmError('mit_infer: 1..4 stages expected, got %d' % len(stages))
+    dev = x.device
+    every = [x]
+    for pe, blocks, norm in stages:
+        if type(pe.proj) is not torch.nn.Conv2d or pe.proj.bias is None:
+            raise _lib.CffmError('mit_infer: patch_embed.proj must be a Conv2d with a bias')
+        ts = [pe.proj.weight, pe.proj.bias] + (mit_stage_tensors(blocks, pe.norm, norm) if blocks else [])
+        for t in ts:
+            if t is None:
+                continue
+            _require_device(t, 'mit_infer parameter')
+            if t.device != dev or not t.is_contiguous():
+                raise _lib.CffmError('mit_infer: every parameter must be contiguous and on %s' % dev)
+        every += ts
+    _infer_only(every, 'mit_infer')
+    xs = _sra_operand(x.detach())
+    arr, keep, shapes = mit_stages(xs.shape, stages)
+    need = lib.cffm_mit_infer_ws_floats(arr, len(stages))
+    if need < 0:
+        raise _lib.CffmError('libcffm_hip: %s' % lib.cffm_last_error().decode())
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.float32, device=dev)
+    elif ws.dtype != torch.float32 or ws.numel() < need or ws.device != dev or not ws.is_contiguous():
+        raise _lib.CffmError('mit_infer workspace: %d contiguous fp32 values on %s expected' % (need, dev))
+    if outs is None:
+        outs = [None] * len(stages)
+    if len(outs) != len(stages):
+        raise _lib.CffmError('mit_infer: %d outputs expected' % len(stages))
+    outs = [_ln_out('mit_infer', o, s, xs) for o, s in zip(outs, shapes)]
+    ptrs = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+    _lib.check(lib.cffm_mit_infer(arr, len(stages), _ptr(xs), ptrs, _ptr(ws), _stream(xs)), lib)
+    del keep
+    return outs
