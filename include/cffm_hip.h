@@ -193,6 +193,21 @@ int cffm_mlp_fwd(const float* ao, const float* xt, long xt_bs, int rows_per_batc
 int cffm_mlp_bwd(const float* dout, const float* hraw, const float* b1, const float* x1, const float* mean2,
                  const float* rstd2, const float* g2, const float* w2_n, const float* w1_n, const float* wp_n, float* dhs,
                  float* dx1, float* dao, float* dg2, float* dbe2, float* db1, float* db2, float* dbp, long NP, void* stream);
+/* added under ABI 13, additive: cffm_mlp_fwd whose x2 leaves as NCHW images instead of token rows (what the layer's last block runs,
+ * so that no layout pass follows it): row m is pixel m % rows_per_batch of image m / rows_per_batch, and feature n of it goes to
+ * x2_nchw[(m / rows_per_batch) * x2_bs + n * rows_per_batch + m % rows_per_batch]; x2_bs >= 256 * rows_per_batch floats, nothing
+ * between the images is touched.  Same arithmetic: the values (and every other output) are those of cffm_mlp_fwd, bit for bit. */
+int cffm_mlp_fwd_nchw(const float* ao, const float* xt, long xt_bs, int rows_per_batch, const float* wp_f, const float* w1_f,
+                      const float* w2_f, const float* bp, const float* b1, const float* b2, const float* g2, const float* be2,
+                      float* x1, float* z2s, float* mean2, float* rstd2, float* hraw, float* acts, float* x2_nchw, long x2_bs,
+                      long NP, void* stream);
+/* ... and cffm_mlp_bwd whose upstream gradient is read from NCHW images (same indexing, dy_bs >= 256 * rows_per_batch) instead of from
+ * token rows; the rows [NP,256] of it are written to dout_rows (inside a block the fc2 weight gradient reads them).  Every output
+ * equals cffm_mlp_bwd's on the transposed gradient, bit for bit. */
+int cffm_mlp_bwd_nchw(const float* dy_nchw, long dy_bs, int rows_per_batch, float* dout_rows, const float* hraw, const float* b1,
+                      const float* x1, const float* mean2, const float* rstd2, const float* g2, const float* w2_n, const float* w1_n,
+                      const float* wp_n, float* dhs, float* dx1, float* dao, float* dg2, float* dbe2, float* db1, float* db2,
+                      float* dbp, long NP, void* stream);
 int cffm_colsum(const float* a, long rows, int cols /* multiple of 4 */, float* out /* overwritten */, void* stream);
 /* added under ABI 13, additive: the block's q|k|v Linear as a stage -- qkv16 [M,768] f16 = x w^T + b with the q third times 32^-0.5, from
  * x in split-4 storage ([M,256]) and w in fragment order (cffm_panel_pack_weight of w [768,256], form 0).  Each workgroup computes one of

@@ -119,6 +119,8 @@ SIGNATURES = {
     'cffm_bias_scatter': (ci, [vp, vp, vp, C.POINTER(vp), vp]),
     'cffm_mlp_fwd': (ci, [vp, vp, cl, ci] + [vp] * 15 + [cl, vp]),
     'cffm_mlp_bwd': (ci, [vp] * 18 + [cl, vp]),
+    'cffm_mlp_fwd_nchw': (ci, [vp, vp, cl, ci] + [vp] * 15 + [cl, cl, vp]),
+    'cffm_mlp_bwd_nchw': (ci, [vp, cl, ci] + [vp] * 18 + [cl, vp]),
     'cffm_block_forward': (ci, [GP, BP, vp, cl, vp, cl, vp, vp, vp, vp, vp]),
     'cffm_block_backward': (ci, [GP, BP, BP, vp, cl, vp, cl, vp, vp, vp, vp, vp, vp, vp, cl, ci, vp, cl, vp, vp]),
     'cffm_layer_forward': (ci, [GP, ci, BP, vp, vp, vp, vp, vp, vp, vp]),

@@ -1159,7 +1159,8 @@ int cffm_gtc_attn_bwd(const float* q_raw, const float* q_b, const float* kv_raw,
 #define MLP_D 4
 static int mlp_lds_grant() {
     static int lds_have = 0;
-    return lds_grant(lds_have, {{(const void*)k_mlp_fwd<MLP_MT, MLP_D>, PNL_FUSED_LDS(MLP_MT)}, {(const void*)k_mlp_bwd<MLP_MT, MLP_D>, PNL_FUSED_LDS(MLP_MT)}}) ? 0 : -1;
+    return lds_grant(lds_have, {{(const void*)k_mlp_fwd<MLP_MT, MLP_D>, PNL_FUSED_LDS(MLP_MT)}, {(const void*)k_mlp_fwd<MLP_MT, MLP_D, false, true>, PNL_FUSED_LDS(MLP_MT)},
+                                {(const void*)k_mlp_bwd<MLP_MT, MLP_D>, PNL_FUSED_LDS(MLP_MT)}, {(const void*)k_mlp_bwd<MLP_MT, MLP_D, true>, PNL_FUSED_LDS_NCHW(MLP_MT)}}) ? 0 : -1;
 }
 // The q|k|v input gradient (and the prototype block's q projection) as row-panel GEMMs (weights in fragment order): rows per workgroup
 // (32 or 48) chosen so that the grid wastes the least of its last round on 256 CUs
@@ -1260,13 +1261,16 @@ int cffm_panel_qkv_bwd_input(const float* dqkv, const float* w_frag, float* dx, 
 }
 
 // z2s / acts: split-4 copies (what the LDS-staged weight-gradient kernels read), ao_t / z2_t / act_t: T-frag copies (what the streaming one
-// reads, cffm_tfrag_floats(NP, 256 | 256 | 1024) floats each); every one of the five may be NULL
+// reads, cffm_tfrag_floats(NP, 256 | 256 | 1024) floats each); every one of the five may be NULL.
+// x2_nchw (with x2 NULL): x2 leaves as NCHW images of rows_per_batch pixels, x2_bs floats apart, instead of as rows (k_mlp_fwd's NCHW form)
 static int cffm_mlp_fwd_tfrag(const float* ao, const float* xt, long xt_bs, int rows_per_batch, const float* wp_f, const float* w1_f, const float* w2_f,
                               const float* bp, const float* b1, const float* b2, const float* g2, const float* be2, float* x1, float* z2s, float* mean2,
-                              float* rstd2, float* hraw, float* acts, float* x2, float* ao_t, float* z2_t, float* act_t, long NP, void* stream) {
+                              float* rstd2, float* hraw, float* acts, float* x2, float* ao_t, float* z2_t, float* act_t, long NP, void* stream,
+                              float* x2_nchw = nullptr, long x2_bs = 0) {
     REQUIRE(NP >= 0 && NP < (1L << 21) && rows_per_batch >= 1, "mlp_fwd: bad sizes");
     if (!NP) return 0;
-    REQUIRE(ao && xt && wp_f && w1_f && w2_f && bp && b1 && b2 && g2 && be2 && x1 && mean2 && rstd2 && hraw && x2, "mlp_fwd: null");
+    REQUIRE(ao && xt && wp_f && w1_f && w2_f && bp && b1 && b2 && g2 && be2 && x1 && mean2 && rstd2 && hraw && (x2 || x2_nchw), "mlp_fwd: null");
+    REQUIRE(!x2_nchw || (!x2 && x2_bs >= 256L * rows_per_batch), "mlp_fwd: bad NCHW destination");
     REQUIRE(!mlp_lds_grant(), "mlp_fwd: LDS grant failed");
     PROF2(ST_MLP_FWD);
     MlpFwdArgs a;
@@ -1275,7 +1279,12 @@ static int cffm_mlp_fwd_tfrag(const float* ao, const float* xt, long xt_bs, int 
     a.bp = bp; a.b1 = b1; a.b2 = b2; a.g2 = g2; a.be2 = be2;
     a.x1 = x1; a.z2s = z2s; a.mean2 = mean2; a.rstd2 = rstd2; a.hraw = hraw; a.acts = acts; a.x2 = x2; a.NP = (int)NP;
     a.ao_t = (f32x4*)ao_t; a.z2_t = (f32x4*)z2_t; a.act_t = (f32x4*)act_t;
-    CFFM_LAUNCH((k_mlp_fwd<MLP_MT, MLP_D>), ((unsigned)cffm_mlp_records(NP)), (PNL_THREADS), PNL_FUSED_LDS(MLP_MT), (hipStream_t)stream, a);
+    a.x2_nchw = x2_nchw; a.x2_bs = x2_bs;
+    if (x2_nchw) {
+        CFFM_LAUNCH((k_mlp_fwd<MLP_MT, MLP_D, false, true>), ((unsigned)cffm_mlp_records(NP)), (PNL_THREADS), PNL_FUSED_LDS(MLP_MT), (hipStream_t)stream, a);
+    } else {
+        CFFM_LAUNCH((k_mlp_fwd<MLP_MT, MLP_D>), ((unsigned)cffm_mlp_records(NP)), (PNL_THREADS), PNL_FUSED_LDS(MLP_MT), (hipStream_t)stream, a);
+    }
     CHECK_LAUNCH("mlp_fwd");
     return 0;
 }
@@ -1286,14 +1295,26 @@ int cffm_mlp_fwd(const float* ao, const float* xt, long xt_bs, int rows_per_batc
     return cffm_mlp_fwd_tfrag(ao, xt, xt_bs, rows_per_batch, wp_f, w1_f, w2_f, bp, b1, b2, g2, be2, x1, z2s, mean2, rstd2, hraw, acts, x2, nullptr, nullptr,
                               nullptr, NP, stream);
 }
+// cffm_mlp_fwd with x2 written as NCHW images: row m = pixel m % rows_per_batch of image m / rows_per_batch, images x2_bs floats apart
+int cffm_mlp_fwd_nchw(const float* ao, const float* xt, long xt_bs, int rows_per_batch, const float* wp_f, const float* w1_f, const float* w2_f,
+                      const float* bp, const float* b1, const float* b2, const float* g2, const float* be2, float* x1, float* z2s, float* mean2,
+                      float* rstd2, float* hraw, float* acts, float* x2_nchw, long x2_bs, long NP, void* stream) {
+    REQUIRE((z2s && x2_nchw) || !NP, "mlp_fwd_nchw: null");
+    return cffm_mlp_fwd_tfrag(ao, xt, xt_bs, rows_per_batch, wp_f, w1_f, w2_f, bp, b1, b2, g2, be2, x1, z2s, mean2, rstd2, hraw, acts, nullptr, nullptr, nullptr,
+                              nullptr, NP, stream, x2_nchw, x2_bs);
+}
 
-// dhs: split-4 copy of dh; dout_t / dh_t / dx1_t: T-frag copies of dout, dh, dx1 (cffm_tfrag_floats(NP, 256 | 1024 | 256) floats); each may be NULL
+// dhs: split-4 copy of dh; dout_t / dh_t / dx1_t: T-frag copies of dout, dh, dx1 (cffm_tfrag_floats(NP, 256 | 1024 | 256) floats); each may be NULL.
+// dy_nchw (with dout NULL): the gradient arrives as NCHW images of rows_per_batch pixels, dy_bs floats apart, and its rows [NP][256] are
+// written to dout_rows (k_mlp_bwd's NCHW form)
 static int cffm_mlp_bwd_tfrag(const float* dout, const float* hraw, const float* b1, const float* x1, const float* mean2, const float* rstd2,
                               const float* g2, const float* w2_n, const float* w1_n, const float* wp_n, float* dhs, float* dx1, float* dao, float* dg2,
-                              float* dbe2, float* db1, float* db2, float* dbp, float* dout_t, float* dh_t, float* dx1_t, long NP, void* stream) {
+                              float* dbe2, float* db1, float* db2, float* dbp, float* dout_t, float* dh_t, float* dx1_t, long NP, void* stream,
+                              const float* dy_nchw = nullptr, long dy_bs = 0, int rows_per_batch = 0, float* dout_rows = nullptr) {
     REQUIRE(NP >= 0 && NP < (1L << 21), "mlp_bwd: bad sizes");
     if (!NP) return 0;
-    REQUIRE(dout && hraw && b1 && x1 && mean2 && rstd2 && g2 && w2_n && w1_n && wp_n && dx1 && dao, "mlp_bwd: null");
+    REQUIRE((dout || dy_nchw) && hraw && b1 && x1 && mean2 && rstd2 && g2 && w2_n && w1_n && wp_n && dx1 && dao, "mlp_bwd: null");
+    REQUIRE(!dy_nchw || (!dout && dout_rows && rows_per_batch >= 1 && dy_bs >= 256L * rows_per_batch), "mlp_bwd: bad NCHW source");
     REQUIRE(!mlp_lds_grant(), "mlp_bwd: LDS grant failed");
     PROF2(ST_MLP_BWD);
     hipStream_t st = (hipStream_t)stream;
@@ -1305,7 +1326,12 @@ static int cffm_mlp_bwd_tfrag(const float* dout, const float* hraw, const float*
     a.w2n = (const f32x4*)w2_n; a.w1n = (const f32x4*)w1_n; a.wpn = (const f32x4*)wp_n;
     a.dhs = dhs; a.dx1 = dx1; a.dao = dao; a.rec_b1 = rec; a.rec_ln = rec + (size_t)nrec * 1024; a.NP = (int)NP;
     a.dout_t = (f32x4*)dout_t; a.dh_t = (f32x4*)dh_t; a.dx1_t = (f32x4*)dx1_t;
-    CFFM_LAUNCH((k_mlp_bwd<MLP_MT, MLP_D>), ((unsigned)nrec), (PNL_THREADS), PNL_FUSED_LDS(MLP_MT), st, a);
+    a.dy_nchw = dy_nchw; a.dy_bs = dy_bs; a.pix = rows_per_batch; a.dout_rows = dout_rows;
+    if (dy_nchw) {
+        CFFM_LAUNCH((k_mlp_bwd<MLP_MT, MLP_D, true>), ((unsigned)nrec), (PNL_THREADS), PNL_FUSED_LDS_NCHW(MLP_MT), st, a);
+    } else {
+        CFFM_LAUNCH((k_mlp_bwd<MLP_MT, MLP_D>), ((unsigned)nrec), (PNL_THREADS), PNL_FUSED_LDS(MLP_MT), st, a);
+    }
     RedSegs s1, s2;
     s1.nseg = 0;
     seg_add(s1, 0, CFFM_HID, db1, 0);
@@ -1325,6 +1351,15 @@ int cffm_mlp_bwd(const float* dout, const float* hraw, const float* b1, const fl
     REQUIRE(dhs || !NP, "mlp_bwd: null");
     return cffm_mlp_bwd_tfrag(dout, hraw, b1, x1, mean2, rstd2, g2, w2_n, w1_n, wp_n, dhs, dx1, dao, dg2, dbe2, db1, db2, dbp, nullptr, nullptr, nullptr, NP,
                               stream);
+}
+// cffm_mlp_bwd with the gradient read as NCHW images: row m = pixel m % rows_per_batch of image m / rows_per_batch, images dy_bs floats
+// apart; its rows [NP][256] are written to dout_rows
+int cffm_mlp_bwd_nchw(const float* dy_nchw, long dy_bs, int rows_per_batch, float* dout_rows, const float* hraw, const float* b1, const float* x1,
+                      const float* mean2, const float* rstd2, const float* g2, const float* w2_n, const float* w1_n, const float* wp_n, float* dhs,
+                      float* dx1, float* dao, float* dg2, float* dbe2, float* db1, float* db2, float* dbp, long NP, void* stream) {
+    REQUIRE((dhs && dy_nchw) || !NP, "mlp_bwd_nchw: null");
+    return cffm_mlp_bwd_tfrag(nullptr, hraw, b1, x1, mean2, rstd2, g2, w2_n, w1_n, wp_n, dhs, dx1, dao, dg2, dbe2, db1, db2, dbp, nullptr, nullptr, nullptr, NP,
+                              stream, dy_nchw, dy_bs, rows_per_batch, dout_rows);
 }
 
 // ------------------------------------------------------------------------------------------- CFFM++ (GTC) block, fused (round 5)
@@ -1515,7 +1550,7 @@ static int param_prep(const cffm_block_params* params, int n, float* ws0, long w
 
 static int block_forward_impl(const cffm_geom* g, const cffm_block_params* p, const float* x_ref, long ref_bs,
                               const float* x_tgt, long tgt_bs, const int* key_src, const int* q_dst, float* ws,
-                              float* scratch, void* stream);
+                              float* scratch, void* stream, float* x2_rows = nullptr, float* x2_nchw = nullptr, long x2_bs = 0);
 int cffm_block_forward(const cffm_geom* g, const cffm_block_params* p, const float* x_ref, long ref_bs,
                        const float* x_tgt, long tgt_bs, const int* key_src, const int* q_dst, float* ws,
                        float* scratch, void* stream) {
@@ -1527,9 +1562,11 @@ int cffm_block_forward(const cffm_geom* g, const cffm_block_params* p, const flo
 }
 // the block after its parameter-only inputs (ws.bias, ws.biasT, ws.M) have been prepared
 static struct { bool pending; hipStream_t side; } g_prep_join = {false, nullptr};
+// The block's output rows go to ws + L.x2, or where the layer's last block is told to put them (its ws.x2 is then not written: nothing reads
+// it): x2_rows = rows somewhere else, x2_nchw = NCHW images x2_bs floats apart (k_mlp_fwd's NCHW form)
 static int block_forward_impl(const cffm_geom* g, const cffm_block_params* p, const float* x_ref, long ref_bs,
                               const float* x_tgt, long tgt_bs, const int* key_src, const int* q_dst, float* ws,
-                              float* scratch, void* stream) {
+                              float* scratch, void* stream, float* x2_rows, float* x2_nchw, long x2_bs) {
     cffm_block_ws L;
     cffm_block_ws_layout(g, &L);
     const long NR = (long)g->B * g->RC, NP = (long)g->B * g->HW;
@@ -1553,14 +1590,15 @@ static int block_forward_impl(const cffm_geom* g, const cffm_block_params* p, co
         // proj + residual + norm2 + Mlp in one row-panel launch (panel_kernels.h); weights in fragment order from k_param_prep
         const float* wf = ws + L.w_frag;
         PROF(ST_GEMM);
+        float* x2 = x2_nchw ? nullptr : x2_rows ? x2_rows : ws + L.x2;
         if (dw_stream_sw())     // z2 / act (and a copy of ao) in T-frag storage: operands of the streaming weight gradients
             TRY(cffm_mlp_fwd_tfrag(ws + L.ao, x_tgt, tgt_bs, g->HW, wf + 768 * 256, wf + 768 * 256 + 256 * 256, wf + 768 * 256 + 256 * 256 + 1024 * 256,
                                    p->proj_b, p->fc1_b, p->fc2_b, p->norm2_w, p->norm2_b, ws + L.x1, nullptr, ws + L.mean2, ws + L.rstd2, ws + L.hraw,
-                                   nullptr, ws + L.x2, ws + L.ao_t, ws + L.z2, ws + L.act, NP, stream));
+                                   nullptr, x2, ws + L.ao_t, ws + L.z2, ws + L.act, NP, stream, x2_nchw, x2_bs));
         else
-        TRY(cffm_mlp_fwd(ws + L.ao, x_tgt, tgt_bs, g->HW, wf + 768 * 256, wf + 768 * 256 + 256 * 256, wf + 768 * 256 + 256 * 256 + 1024 * 256,
-                         p->proj_b, p->fc1_b, p->fc2_b, p->norm2_w, p->norm2_b, ws + L.x1, ws + L.z2, ws + L.mean2, ws + L.rstd2, ws + L.hraw,
-                         ws + L.act, ws + L.x2, NP, stream));
+        TRY(cffm_mlp_fwd_tfrag(ws + L.ao, x_tgt, tgt_bs, g->HW, wf + 768 * 256, wf + 768 * 256 + 256 * 256, wf + 768 * 256 + 256 * 256 + 1024 * 256,
+                               p->proj_b, p->fc1_b, p->fc2_b, p->norm2_w, p->norm2_b, ws + L.x1, ws + L.z2, ws + L.mean2, ws + L.rstd2, ws + L.hraw,
+                               ws + L.act, x2, nullptr, nullptr, nullptr, NP, stream, x2_nchw, x2_bs));
         CHECK_LAUNCH("block_forward");
     }
     (void)scratch;
@@ -1570,7 +1608,8 @@ static int block_forward_impl(const cffm_geom* g, const cffm_block_params* p, co
 static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, const cffm_block_grads* gr,
                                const float* x_ref, long ref_bs, const float* x_tgt, long tgt_bs, const int* key_src,
                                const int* q_dst, const int* inv_ptr, const int* inv_idx, const float* ws, const float* dout,
-                               float* dx_tgt, long dtgt_bs, float* scratch, int defer, int par, int slot, int nslots, void* stream);
+                               float* dx_tgt, long dtgt_bs, float* scratch, int defer, int par, int slot, int nslots, void* stream,
+                               const float* dy_nchw = nullptr, long dy_bs = 0);
 // The parameter-gradient tail of a block backward (record reductions, pooling-matrix backward), LAUNCHED LATE: its fork point is the end
 // of ln_pool_bwd (event fork[3]), but the launches happen only after the chain's next kernel has been launched (tail_flush), so that
 // under stream capture the chain's kernel is ln_pool_bwd's FIRST dependant and keeps its place on the graph's first stream (the graph
@@ -1611,10 +1650,13 @@ int cffm_block_backward(const cffm_geom* g, const cffm_block_params* p, const cf
 // the scratch operands the NEXT block overwrites (the weight-gradient GEMMs).  The next block_backward_impl waits for the rest where
 // it needs it; the caller ends the sequence with side_join_all().  (Measured on the round-3 timeline: the chain idled ~32 us per
 // block between ln_pool_bwd and the next block's first kernel, behind four small side kernels.)
+// dy_nchw (the layer's last block): the gradient of the block's output as NCHW images dy_bs floats apart; `dout` is then where the fused
+// Mlp kernel WRITES its rows (a buffer of `scratch`), for the fc2 weight gradient
 static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, const cffm_block_grads* gr,
                                const float* x_ref, long ref_bs, const float* x_tgt, long tgt_bs, const int* key_src,
                                const int* q_dst, const int* inv_ptr, const int* inv_idx, const float* ws, const float* dout,
-                               float* dx_tgt, long dtgt_bs, float* scratch, int defer, int par, int slot, int nslots, void* stream) {
+                               float* dx_tgt, long dtgt_bs, float* scratch, int defer, int par, int slot, int nslots, void* stream,
+                               const float* dy_nchw, long dy_bs) {
     REQUIRE(g && p && gr && ws && dout && scratch, "block_backward: null");
     cffm_block_ws L;
     cffm_block_ws_layout(g, &L);
@@ -1683,14 +1725,16 @@ static int block_backward_impl(const cffm_geom* g, const cffm_block_params* p, c
         // gradient records come out of it for the weight-gradient groups and the reductions below
         const float* wfn = ws + L.w_frag + PREP_WFLOATS;
         PROF(ST_GEMM);
+        const float* dout_in = dy_nchw ? nullptr : dout;
+        float* dout_rows = dy_nchw ? (float*)dout : nullptr;
         if (stream_dw)
-            TRY(cffm_mlp_bwd_tfrag(dout, ws + L.hraw, p->fc1_b, ws + L.x1, ws + L.mean2, ws + L.rstd2, p->norm2_w, wfn + 768 * 256 + 256 * 256 + 1024 * 256,
+            TRY(cffm_mlp_bwd_tfrag(dout_in, ws + L.hraw, p->fc1_b, ws + L.x1, ws + L.mean2, ws + L.rstd2, p->norm2_w, wfn + 768 * 256 + 256 * 256 + 1024 * 256,
                                    wfn + 768 * 256 + 256 * 256, wfn + 768 * 256, nullptr, dx1, dao, gr->norm2_w, gr->norm2_b, gr->fc1_b, gr->fc2_b, gr->proj_b,
-                                   dout_t, dact, dx1_t, NP, stream));
+                                   dout_t, dact, dx1_t, NP, stream, dy_nchw, dy_bs, g->HW, dout_rows));
         else
-        TRY(cffm_mlp_bwd(dout, ws + L.hraw, p->fc1_b, ws + L.x1, ws + L.mean2, ws + L.rstd2, p->norm2_w, wfn + 768 * 256 + 256 * 256 + 1024 * 256,
-                         wfn + 768 * 256 + 256 * 256, wfn + 768 * 256, dact, dx1, dao, gr->norm2_w, gr->norm2_b, gr->fc1_b, gr->fc2_b, gr->proj_b, NP,
-                         stream));
+        TRY(cffm_mlp_bwd_tfrag(dout_in, ws + L.hraw, p->fc1_b, ws + L.x1, ws + L.mean2, ws + L.rstd2, p->norm2_w, wfn + 768 * 256 + 256 * 256 + 1024 * 256,
+                               wfn + 768 * 256 + 256 * 256, wfn + 768 * 256, dact, dx1, dao, gr->norm2_w, gr->norm2_b, gr->fc1_b, gr->fc2_b, gr->proj_b,
+                               nullptr, nullptr, nullptr, NP, stream, dy_nchw, dy_bs, g->HW, dout_rows));
         TRY(tail_flush(st));    // the previous block's parameter-gradient tail, now that this block's first kernel is ln_pool_bwd's first dependant
         if (!one_group) {
             sa = side_fork(st, 0);
@@ -2280,10 +2324,9 @@ int cffm_layer_forward_rows(const cffm_geom* g, int depth, const cffm_block_para
         float* ws = blk0 + (long)i * L.total;
         const float* tgt = (i == 0) ? x_rows + 3 * img : blk0 + (long)(i - 1) * L.total + L.x2;
         const long tgt_bs = (i == 0) ? 4 * img : img;
-        TRY(block_forward_impl(g, &params[i], x_rows, 4 * img, tgt, tgt_bs, key_src, q_dst, ws, scratch, stream));
+        // the last block writes its output rows straight into the caller's (as layer_infer_blocks does)
+        TRY(block_forward_impl(g, &params[i], x_rows, 4 * img, tgt, tgt_bs, key_src, q_dst, ws, scratch, stream, i == depth - 1 ? y_rows : nullptr));
     }
-    REQUIRE(hipMemcpyAsync(y_rows, blk0 + (long)(depth - 1) * L.total + L.x2, (size_t)g->B * img * sizeof(float), hipMemcpyDeviceToDevice,
-                           (hipStream_t)stream) == hipSuccess, "layer_forward_rows: copy failed");
     return 0;
 }
 // dy_rows [B,HW,256] -> dx_rows [B,4,HW,256] and every parameter gradient; x_rows as given to cffm_layer_forward_rows
@@ -2362,9 +2405,11 @@ static int layer_forward_impl(const cffm_geom* g, int depth, const cffm_block_pa
         float* ws = blk0 + (long)i * L.total;
         const float* tgt = (i == 0) ? xs + 3 * img : blk0 + (long)(i - 1) * L.total + L.x2;
         const long tgt_bs = (i == 0) ? 4 * img : img;
-        TRY(block_forward_impl(g, &params[i], xs, 4 * img, tgt, tgt_bs, key_src, q_dst, ws, scratch, stream));
+        // the last block's fused Mlp kernel writes the target frame in NCHW itself (no rows, no transpose behind it)
+        const bool last = i == depth - 1;
+        TRY(block_forward_impl(g, &params[i], xs, 4 * img, tgt, tgt_bs, key_src, q_dst, ws, scratch, stream, nullptr, last ? y_tgt_nchw : nullptr,
+                               last ? y_bs : 0));
     }
-    TRY(cffm_transpose(blk0 + (long)(depth - 1) * L.total + L.x2, y_tgt_nchw, g->B, (int)HW, CFFM_C, img, y_bs, stream));
     return 0;
 }
 int cffm_layer_forward(const cffm_geom* g, int depth, const cffm_block_params* params, const float* x_nchw,
@@ -2418,7 +2463,7 @@ long cffm_layer_infer_ws_floats(const cffm_geom* g) { return (!g || g->B < 1 || 
 
 static int infer_lds_grant() {
     static int lds_have = 0;
-    return lds_grant(lds_have, {{(const void*)k_mlp_fwd<MLP_MT, MLP_D, true>, PNL_FUSED_LDS(MLP_MT)}}) ? 0 : -1;
+    return lds_grant(lds_have, {{(const void*)k_mlp_fwd<MLP_MT, MLP_D, true>, PNL_FUSED_LDS(MLP_MT)}, {(const void*)k_mlp_fwd<MLP_MT, MLP_D, true, true>, PNL_FUSED_LDS(MLP_MT)}}) ? 0 : -1;
 }
 // Panel height of the inference Mlp kernel.  The training choice (MLP_MT = 2: 32 rows) leaves more than half of the 256 CUs idle when a
 // call has under 4096 rows (B = 1 on the 60 x 60 grid: 113 workgroups); 16-row panels then still fit one round (225 workgroups).  Measured
@@ -2455,9 +2500,10 @@ int cffm_layer_prepare(int depth, const cffm_block_params* params, float* prepar
     return 0;
 }
 
-// the blocks of one call: `stack` = NHWC frames [B,4,HW,256]; the last block's output rows [B,HW,256] go to `y_rows`
+// the blocks of one call: `stack` = NHWC frames [B,4,HW,256]; the last block's output rows [B,HW,256] go to `y_rows`, or (y_rows NULL) as
+// NCHW images y_bs floats apart to `y_nchw` (k_mlp_fwd's NCHW form)
 static int layer_infer_blocks(const cffm_geom* g, int depth, const cffm_block_params* params, const float* prepared, const float* stack,
-                              float* y_rows, const int* key_src, const int* q_dst, float* ws, void* stream) {
+                              float* y_rows, const int* key_src, const int* q_dst, float* ws, void* stream, float* y_nchw = nullptr, long y_bs = 0) {
     REQUIRE(!infer_lds_grant(), "layer_infer: LDS grant failed");
     const PreparedLayout P = prepared_layout();
     const InferWs W = infer_ws_layout(g);
@@ -2495,10 +2541,14 @@ static int layer_infer_blocks(const cffm_geom* g, int depth, const cffm_block_pa
             a.wp = (const f32x4*)(wf + 768 * 256); a.w1 = (const f32x4*)(wf + 768 * 256 + 256 * 256); a.w2 = (const f32x4*)(wf + 768 * 256 + 256 * 256 + 1024 * 256);
             a.bp = p->proj_b; a.b1 = p->fc1_b; a.b2 = p->fc2_b; a.g2 = p->norm2_w; a.be2 = p->norm2_b;
             a.x2 = x2; a.NP = (int)NP;
+            const bool nchw = i == depth - 1 && !y_rows;
+            if (nchw) { a.x2 = nullptr; a.x2_nchw = y_nchw; a.x2_bs = y_bs; }
             if (infer_mlp_mt(NP) == 1) {
-                CFFM_LAUNCH((k_mlp_fwd<1, MLP_D, true>), ((unsigned)((NP + 15) / 16)), (PNL_THREADS), PNL_FUSED_LDS(1), st, a);
+                if (nchw) CFFM_LAUNCH((k_mlp_fwd<1, MLP_D, true, true>), ((unsigned)((NP + 15) / 16)), (PNL_THREADS), PNL_FUSED_LDS(1), st, a);
+                else CFFM_LAUNCH((k_mlp_fwd<1, MLP_D, true>), ((unsigned)((NP + 15) / 16)), (PNL_THREADS), PNL_FUSED_LDS(1), st, a);
             } else {
-                CFFM_LAUNCH((k_mlp_fwd<MLP_MT, MLP_D, true>), ((unsigned)cffm_mlp_records(NP)), (PNL_THREADS), PNL_FUSED_LDS(MLP_MT), st, a);
+                if (nchw) CFFM_LAUNCH((k_mlp_fwd<MLP_MT, MLP_D, true, true>), ((unsigned)cffm_mlp_records(NP)), (PNL_THREADS), PNL_FUSED_LDS(MLP_MT), st, a);
+                else CFFM_LAUNCH((k_mlp_fwd<MLP_MT, MLP_D, true>), ((unsigned)cffm_mlp_records(NP)), (PNL_THREADS), PNL_FUSED_LDS(MLP_MT), st, a);
             }
         }
         CHECK_LAUNCH("layer_infer block");
@@ -2527,12 +2577,15 @@ int cffm_layer_infer_full(const cffm_geom* g, int depth, const cffm_block_params
     const long HW = g->HW, img = HW * CFFM_C;
     float* stack = y_full_nchw;
     TRY(transpose_add(x_nchw, stack, g->B * 4, CFFM_C, (int)HW, img, img, nullptr, 1, -1, stream));
-    float* last = ws + W.x2[(depth - 1) & 1];
-    TRY(layer_infer_blocks(g, depth, params, prepared, stack, last, key_src, q_dst, ws, stream));
+    // From depth 2 on the last block's fused Mlp kernel writes frame 3 in NCHW itself: the stack was last read by that block's
+    // k_ln_pool_fwd, and its residual rows are the block before's x2 in `ws`.  At depth 1 the residual rows ARE frame 3 of the stack,
+    // which other workgroups of the launch still read: rows + a transpose, as before.
+    float* last = depth > 1 ? nullptr : ws + W.x2[0];
+    TRY(layer_infer_blocks(g, depth, params, prepared, stack, last, key_src, q_dst, ws, stream, y_full_nchw + 3 * img, 4 * img));
     for (int b = 0; b < g->B; ++b)
         REQUIRE(hipMemcpyAsync(y_full_nchw + (long)b * 4 * img, x_nchw + (long)b * 4 * img, (size_t)3 * img * sizeof(float), hipMemcpyDeviceToDevice,
                                (hipStream_t)stream) == hipSuccess, "layer_infer_full: copy failed");
-    TRY(cffm_transpose(last, y_full_nchw + 3 * img, g->B, (int)HW, CFFM_C, img, 4 * img, stream));
+    if (last) TRY(cffm_transpose(last, y_full_nchw + 3 * img, g->B, (int)HW, CFFM_C, img, 4 * img, stream));
     return 0;
 }
 
@@ -2556,7 +2609,6 @@ static int layer_backward_impl(const cffm_geom* g, int depth, const cffm_block_p
     const float* blk0 = saved + up((long)g->B * 4 * img);
     float* dxs = scratch + S.dxs;   // NHWC gradient stack [B,4,HW,C]
     REQUIRE(dy_bs >= img, "layer_backward: dy batch stride %ld < %ld", dy_bs, img);
-    if (first_block == depth - 1) TRY(cffm_transpose(dy_tgt_nchw, scratch + S.a, g->B, CFFM_C, (int)HW, dy_bs, img, stream));
     tail_reset();
     for (int i = first_block; i >= last_block; --i) {
         const float* ws = blk0 + (long)i * L.total;
@@ -2568,8 +2620,10 @@ static int layer_backward_impl(const cffm_geom* g, int depth, const cffm_block_p
         float* dcur = scratch + (((depth - 1 - i) & 1) ? S.a2 : S.a);
         float* dtgt = (i == 0) ? dxs + 3 * img : scratch + (((depth - i) & 1) ? S.a2 : S.a);
         const long dtgt_bs = (i == 0) ? 4 * img : img;
+        // the last block's fused Mlp kernel reads dy in NCHW itself and leaves its rows in `dcur` (no transpose in front of it)
+        const bool from_dy = i == depth - 1;
         TRY(block_backward_impl(g, &params[i], &grads[i], xs, 4 * img, tgt, tgt_bs, key_src, q_dst, inv_ptr, inv_idx, ws, dcur, dtgt, dtgt_bs, scratch,
-                                1, (depth - 1 - i) & 1, i, depth, stream));
+                                1, (depth - 1 - i) & 1, i, depth, stream, from_dy ? dy_tgt_nchw : nullptr, from_dy ? dy_bs : 0));
     }
     // The reference frames of every block of the range in ONE pass (they pass through the layer unchanged: one read of x_ref, one write
     // of dx_ref per range instead of a read + read-modify-write per block) and the range's CFFA parameter gradients.  A caller that

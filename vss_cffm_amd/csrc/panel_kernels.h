@@ -453,13 +453,23 @@ struct MlpFwdArgs {
     float *x1, *z2s /* split-4, or NULL */, *mean2, *rstd2, *hraw, *acts /* split-4, or NULL: not stored (the fc2 weight gradient re-applies bias + GELU to hraw) */, *x2;
     f32x4 *ao_t, *z2_t, *act_t;         // T-frag copies of ao [NP][256], z2 [NP][256], act [NP][1024] for the streaming weight gradients (each may be NULL)
     int NP;
+    // NCHW instantiations only (x2 is not read there): row m is pixel m % rows_per_batch of image m / rows_per_batch, and its feature n
+    // goes to x2_nchw[(m / rows_per_batch) * x2_bs + n * rows_per_batch + m % rows_per_batch]
+    float* x2_nchw; long x2_bs;
 };
+
+// The finished x2 tile of the NCHW instantiations, [256 channels][16 MT pixels] fp32 in LDS: the pitch keeps a channel's pixels 16-byte
+// aligned, and the four channel groups g of a wave's scalar writes (4 g channels apart: 4 g PITCH = 16 g mod 64 words) in four bank groups
+#define PNL_NCHW_PITCH(MT) (16 * (MT) + 4)
 
 // INFER = true: the forward of a call that keeps nothing for a backward (the inference forward of the layer) -- of everything below
 // only x2 is stored (x1, the LayerNorm statistics, hraw and the split-4 / T-frag operand copies of the weight gradients are not, and
 // their pointers are not read).  Selected at compile time: the training instantiation is the kernel it was, and the arithmetic of the
 // two is the same, instruction for instruction.
-template <int MT, int D, bool INFER = false>
+// NCHW = true: the layer's last block -- x2 leaves as the target frame of the layer's NCHW output (a.x2_nchw) instead of as token rows,
+// which nothing but a layout pass would read.  The tile (one 64- or 128-byte run of pixels per channel) goes through LDS so that a lane
+// stores four consecutive pixels of one channel; the values are those of the rows form.  Also selected at compile time.
+template <int MT, int D, bool INFER = false, bool NCHW = false>
 __global__ void __launch_bounds__(PNL_THREADS) k_mlp_fwd(MlpFwdArgs a) {
     CFFM_DYN_SMEM(smem);
     bf16* P = (bf16*)smem;                         // ao panel, later the z2 panel
@@ -638,15 +648,56 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_fwd(MlpFwdArgs a) {
         const int cn = c < 3 ? c + 1 : 0;
         pnl_chunk_mma<MT, 2, 2, D>(acc2, ring, Ah, Ah + PNL_IMG(MT), s2, 2 * wave, 8 * c, l15, g, s1, 16 * cn + 2 * wave, 0);
     }
+    if constexpr (!NCHW) {
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int n = 32 * wave + 16 * t + 4 * g;
-        const f32x4 bv = b2v[t];
+        for (int t = 0; t < 2; ++t) {
+            const int n = 32 * wave + 16 * t + 4 * g;
+            const f32x4 bv = b2v[t];
 #pragma unroll
-        for (int i = 0; i < MT; ++i)
-            if (valid[i]) *(f32x4*)(a.x2 + mrow[i] * 256 + n) = x1v[t][i] + acc2[t][i] + bv;
+            for (int i = 0; i < MT; ++i)
+                if (valid[i]) *(f32x4*)(a.x2 + mrow[i] * 256 + n) = x1v[t][i] + acc2[t][i] + bv;
+        }
+    } else {
+        // The tile is assembled over the z2 image and the FIRST pair of hidden-chunk images: every wave read them for the last time in
+        // front of chunk 3's barrier (chunk 3's fc1 product, chunk 2's fc2 product); the last product, which slower waves may still be
+        // in, reads the second pair only -- so no barrier is needed in front of these writes
+        constexpr int PITCH = PNL_NCHW_PITCH(MT), QPC = 4 * MT;      // quads of pixels per channel
+        static_assert(256 * PITCH * 4 <= 4 * PNL_IMG(MT) * 2, "the x2 tile does not fit the z2 image + one pair of hidden-chunk images");
+        float* tile = (float*)smem;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int n = 32 * wave + 16 * t + 4 * g;
+            const f32x4 bv = b2v[t];
+#pragma unroll
+            for (int i = 0; i < MT; ++i) {
+                const f32x4 v = x1v[t][i] + acc2[t][i] + bv;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) tile[(n + e) * PITCH + 16 * i + l15] = v[e];
+            }
+        }
+        pnl_lds_barrier();
+        // a lane stores four consecutive pixels of one channel (a wave instruction: whole 16 MT-pixel runs of 32 / MT channels); a quad
+        // that crosses into the next image, runs past NP or is not 16-byte aligned (pixels per image not a multiple of 4) goes out pixel by pixel
+        const int HW = a.rows_per_batch;
+#pragma unroll
+        for (int it = 0; it < 256 * QPC / PNL_THREADS; ++it) {
+            const int u = tid + PNL_THREADS * it, ch = u / QPC, q = u % QPC, m = m0 + 4 * q;
+            if (m >= NP) continue;
+            const f32x4 v = *(const f32x4*)(tile + ch * PITCH + 4 * q);
+            int b = m / HW, pix = m % HW;
+            float* dst = a.x2_nchw + (long)b * a.x2_bs + (long)ch * HW + pix;
+            if (m + 3 < NP && pix + 3 < HW && ((uintptr_t)dst & 15) == 0) {
+                *(f32x4*)dst = v;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (m + e < NP) a.x2_nchw[(long)b * a.x2_bs + (long)ch * HW + pix] = v[e];
+                    if (++pix == HW) { pix = 0; ++b; }
+                }
+            }
+        }
     }
-    if (a.NP < 0) (INFER ? a.x2 : a.mean2)[tid] = (float)touch;     // (never taken: keeps the warm-up loads)
+    if (a.NP < 0) (INFER ? (NCHW ? a.x2_nchw : a.x2) : a.mean2)[tid] = (float)touch;     // (never taken: keeps the warm-up loads)
 }
 
 struct MlpBwdArgs {
@@ -661,14 +712,26 @@ struct MlpBwdArgs {
     float* rec_b1;                      // [workgroups][1024] column sums of dh (fc1 bias gradient records)
     float* rec_ln;                      // [workgroups][1024] dgamma2 | dbeta2 | colsum(dout) | colsum(dx1) records
     int NP;
+    // NCHW instantiation only (dout is not read there): the gradient arrives as NCHW images of `pix` pixels, dy_bs floats apart -- row m is
+    // pixel m % pix of image m / pix, its feature n is dy_nchw[(m / pix) * dy_bs + n * pix + m % pix] -- and the kernel writes the rows
+    // [NP][256] to dout_rows itself (the fc2 weight gradient reads them)
+    const float* dy_nchw; long dy_bs; int pix; float* dout_rows;
 };
+#define PNL_FUSED_LDS_NCHW(MT) (PNL_FUSED_LDS(MT) + 256 * PNL_NCHW_PITCH(MT) * 4)   // + the fp32 dout tile, which lives to the LayerNorm backward
 
-template <int MT, int D>
+// NCHW = true: the layer's last block -- the upstream gradient is read as the target frame of the layer's NCHW gradient (a.dy_nchw), which
+// nothing but a layout pass would turn into rows first.  The panel arrives as 16-byte units of four consecutive pixels of a channel and
+// is turned in LDS (fp32 tile [256 channels][16 MT pixels], as in k_mlp_fwd's NCHW form); from there every wave takes its rows in
+// accumulator layout: for the panel image, for the rows it writes to a.dout_rows, and again for the LayerNorm backward.  Same values, same
+// order of every sum as the rows form.  Selected at compile time: the rows instantiation is the kernel it was.
+template <int MT, int D, bool NCHW = false>
 __global__ void __launch_bounds__(PNL_THREADS) k_mlp_bwd(MlpBwdArgs a) {
     CFFM_DYN_SMEM(smem);
     bf16* P = (bf16*)smem;                         // dout panel, later the dx1 panel
     bf16* DH = P + 2 * PNL_IMG(MT);                // two hidden-chunk images of dh
     float* red = (float*)(DH + 4 * PNL_IMG(MT));   // [2][8 waves][16 MT]
+    float* T = red + 2 * PNL_WAVES * 16 * MT;      // (NCHW) fp32 dout tile [256][PNL_NCHW_PITCH]
+    constexpr int TP = PNL_NCHW_PITCH(MT);
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6), l15 = lane & 15, g = lane >> 4;
     const int m0 = blockIdx.x * 16 * MT, NP = a.NP;
     PnlStream s2, s1, sp;
@@ -680,7 +743,6 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_bwd(MlpBwdArgs a) {
     for (int s = 0; s < D - 1; ++s) pnl_ring_load<2, D>(ring, s, s2, 2 * wave, s);
     uint32_t touch = 0;
     pnl_pin_vmem();
-    const buf_t rs_dout = buf_make(a.dout, (uint32_t)((long)NP * 256 * 4));
     const f32x4 z4 = (f32x4){0.f, 0.f, 0.f, 0.f};
     bool valid[MT];
     long mrow[MT];
@@ -690,6 +752,13 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_bwd(MlpBwdArgs a) {
         valid[i] = m < NP;
         mrow[i] = m;
     }
+    // (NCHW) rows 16 i + l15, features n .. n + 3 of the dout tile: accumulator layout (conflict-free: see PNL_NCHW_PITCH)
+    const auto tile_get = [&](int n, int i) {
+        f32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = T[(n + e) * TP + 16 * i + l15];
+        return v;
+    };
     // Operand prefetch.  The CU's vector-memory path is one in-order queue and vmcnt counts a wave's loads in issue order (see
     // pnl_chunk_mma), so a B-ring slot is consumed only after every load issued before it has returned: an HBM read (2-3 us under
     // this load) requested in front of a product, or between two, stalls the weight stream (D - 1 k-steps, about 1 us of lead) until
@@ -707,7 +776,8 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_bwd(MlpBwdArgs a) {
             for (int i = 0; i < MT; ++i)
                 hr[c & 1][t][i] = valid[i] ? *(const f32x4*)(a.hraw + mrow[i] * 1024 + 256 * c + 32 * wave + 16 * t + 4 * g) : z4;
     };
-    {
+    if constexpr (!NCHW) {
+        const buf_t rs_dout = buf_make(a.dout, (uint32_t)((long)NP * 256 * 4));
         PnlStage<MT> sr;
         pnl_stage_load<MT>(sr, rs_dout, 256, m0, 0, tid);
         hr_request(0);
@@ -717,8 +787,59 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_bwd(MlpBwdArgs a) {
         pnl_pin_vmem();
         pnl_stage_store<MT, false>(sr, P, P + PNL_IMG(MT), tid);
         touch = t0 ^ t1 ^ t2;
+    } else {
+        // a thread loads the same four pixels (quad q of the panel) of 2 MT channels; pixels at and past NP read as zeros (as the rows
+        // form's rows past NP do); a quad that crosses into the next image or is not 16-byte aligned is read pixel by pixel
+        constexpr int QPC = 4 * MT;
+        const int HW = a.pix, q = tid % QPC, m = m0 + 4 * q;
+        const int b0 = m < NP ? m / HW : 0, pix0 = m < NP ? m % HW : 0;
+        const bool whole = m + 3 < NP && pix0 + 3 < HW;
+        f32x4 qv[2 * MT];
+#pragma unroll
+        for (int it = 0; it < 2 * MT; ++it) {
+            const int ch = tid / QPC + (PNL_THREADS / QPC) * it;
+            const float* src = a.dy_nchw + (long)b0 * a.dy_bs + (long)ch * HW + pix0;
+            if (whole && ((uintptr_t)src & 15) == 0) {
+                qv[it] = *(const f32x4*)src;
+            } else {
+                qv[it] = z4;
+                int b = b0, pix = pix0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (m + e < NP) qv[it][e] = a.dy_nchw[(long)b * a.dy_bs + (long)ch * HW + pix];
+                    if (++pix == HW) { pix = 0; ++b; }
+                }
+            }
+        }
+        hr_request(0);
+        // L2 warm-up (pnl_l2_touch), behind the panel's loads in the memory queue
+        pnl_pin_vmem();
+        const uint32_t t0 = pnl_l2_touch(a.w2n, 1024L * 256 * 4, tid), t1 = pnl_l2_touch(a.w1n, 1024L * 256 * 4, tid), t2 = pnl_l2_touch(a.wpn, 256L * 256 * 4, tid);
+        pnl_pin_vmem();
+#pragma unroll
+        for (int it = 0; it < 2 * MT; ++it) *(f32x4*)(T + (tid / QPC + (PNL_THREADS / QPC) * it) * TP + 4 * q) = qv[it];
+        touch = t0 ^ t1 ^ t2;
+        pnl_lds_barrier();
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int i = 0; i < MT; ++i) {
+                const int n = 32 * wave + 16 * t + 4 * g;
+                bf16x4 h, l;
+                split4(tile_get(n, i), h, l);
+                pnl_img_put(P, P + PNL_IMG(MT), 16 * i + l15, n, h, l);
+            }
     }
     pnl_lds_barrier();
+    // (NCHW) the dout rows leave beside the first product, one 16-byte store per thread and step (a burst in front of it would hold up the
+    // B-fragment loads queued behind it, see pnl_chunk_mma)
+    const auto rows_put = [&](int sc) {
+        if (sc < 2 * MT) {
+            const int t = sc / MT, i = sc % MT, n = 32 * wave + 16 * t + 4 * g;
+            const f32x4 v = tile_get(n, i);
+            if (valid[i]) *(f32x4*)(a.dout_rows + mrow[i] * 256 + n) = v;
+        }
+    };
     const long NP32 = ((long)NP + 31) / 32 * 32;
     if (a.dout_t) pnl_tfrag_store<MT>(P, P + PNL_IMG(MT), a.dout_t, m0, 0, 16, NP, NP32, wave, lane);
     f32x4 dz[2][MT];
@@ -740,7 +861,10 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_bwd(MlpBwdArgs a) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) b1v[t] = *(const f32x4*)(a.b1 + 256 * c + 32 * wave + 16 * t + 4 * g);
         pnl_pin_vmem();
-        pnl_chunk_mma<MT, 2, 2, D>(da, ring, P, P + PNL_IMG(MT), s2, 16 * c + 2 * wave, 0, l15, g, s1, 2 * wave, 8 * c);
+        if (NCHW && c == 0)
+            pnl_chunk_mma<MT, 2, 2, D, decltype(rows_put)>(da, ring, P, P + PNL_IMG(MT), s2, 16 * c + 2 * wave, 0, l15, g, s1, 2 * wave, 8 * c, rows_put);
+        else
+            pnl_chunk_mma<MT, 2, 2, D>(da, ring, P, P + PNL_IMG(MT), s2, 16 * c + 2 * wave, 0, l15, g, s1, 2 * wave, 8 * c);
         const bool more = c < 3;
         if (more) {
             hr_request(c + 1);
@@ -759,8 +883,9 @@ __global__ void __launch_bounds__(PNL_THREADS) k_mlp_bwd(MlpBwdArgs a) {
                     hr[(c + 1) & 1][t][i] = dr[t][i] = z4;
                     if (valid[i]) {
                         hr[(c + 1) & 1][t][i] = *(const f32x4*)(a.x1 + mrow[i] * 256 + n);
-                        dr[t][i] = *(const f32x4*)(a.dout + mrow[i] * 256 + n);
+                        if (!NCHW) dr[t][i] = *(const f32x4*)(a.dout + mrow[i] * 256 + n);
                     }
+                    if (NCHW) dr[t][i] = tile_get(n, i);     // (pixels past NP are zeros in the tile)
                 }
             }
         }
