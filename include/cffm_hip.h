@@ -601,8 +601,8 @@ int cffm_sr_ln_bwd(const float* x, const float* w, const float* gamma, const flo
 /* ---- added under ABI 13, additive: LayerNorm of token rows at any width, and one MiT stage's inference forward per call ----
  * LayerNorm over the C channels of fp32 token rows, C a multiple of 4 in 16..512 (csrc/mitln_kernels.h): a row is held in registers, the
  * mean is taken first and the variance from the centred values, rstd = 1 / sqrt(var + eps); fixed summation order, no atomics: the same
- * bits run after run.  Inference only (nothing is saved).
- *   cffm_ln_rows        out[M][C] = LN(x[M][C])
+ * bits run after run.  The forwards save nothing; the backwards below recompute mean and rstd from the input.
+ *   cffm_ln_rows       out[M][C] = LN(x[M][C])
  *   cffm_nchw_ln_rows   x_nchw [B][C][H][W] -> out_rows [B][H*W][C], normalised: OverlapPatchEmbed's flatten(2).transpose(1, 2) + norm
  *   cffm_ln_rows_nchw   x_rows [B][H*W][C] -> out_nchw [B][C][H][W], normalised: a stage's norm + reshape(B, H, W, C).permute(0, 3, 1, 2)
  * Errors (nothing is enqueued, the outputs stay as they are): C outside the limits, M / B / H / W < 1, M*C or B*C*H*W >= 2^31, eps
@@ -612,6 +612,23 @@ int cffm_nchw_ln_rows(const float* x_nchw, const float* gamma, const float* beta
                       void* stream);
 int cffm_ln_rows_nchw(const float* x_rows, const float* gamma, const float* beta, float* out_nchw, int B, int C, int H, int W, float eps,
                       void* stream);
+
+/* added under ABI 13, additive: the backwards of the three calls above.  x is the forward's input in the forward's layout, dout the gradient
+ * of its output in the output's layout, dx the gradient of x in x's layout; dgamma [C], dbeta [C].  Nothing was saved: mean and rstd are
+ * recomputed from x with the forward's arithmetic (xhat has the forward's bits);  g = gamma * dout,  dx = rstd * (g - mean(g) - xhat *
+ * mean(g * xhat)),  dgamma = sum over rows of dout * xhat,  dbeta = sum over rows of dout.  dgamma / dbeta are summed without atomics: every
+ * workgroup writes one record [2][C] to the workspace and a second kernel adds the records; how many there are and the order they are added
+ * in depend on (M, C, H*W) only, never on the device: the same bits run after run.  workspace: cffm_ln_bwd_workspace_bytes(M, C, HW) bytes,
+ * 16-byte aligned, need not be initialised; M = B*H*W and HW = H*W for the two map calls, HW = 1 for cffm_ln_rows_bwd (a map of one pixel
+ * per image is a set of rows and runs as such); < 0 when C is outside the limits, M < 1, HW < 1, M is no multiple of HW or M*C >= 2^31.
+ * Limits and errors as the forwards (nothing is enqueued, every output stays as it is).  No allocation, no host round trip. */
+long cffm_ln_bwd_workspace_bytes(long M, int C, int HW);
+int cffm_ln_rows_bwd(const float* x, const float* gamma, const float* dout, float* dx, float* dgamma, float* dbeta, void* ws, long M, int C,
+                     float eps, void* stream);
+int cffm_nchw_ln_rows_bwd(const float* x_nchw, const float* gamma, const float* dout_rows, float* dx_nchw, float* dgamma, float* dbeta, void* ws,
+                          int B, int C, int H, int W, float eps, void* stream);
+int cffm_ln_rows_nchw_bwd(const float* x_rows, const float* gamma, const float* dout_nchw, float* dx_rows, float* dgamma, float* dbeta, void* ws,
+                          int B, int C, int H, int W, float eps, void* stream);
 
 /* One stage of a Mix Transformer (backbones/mix_transformer.py forward_features, one iteration of its loop) in eval mode, behind the
  * patch embedding's convolution: conv_nchw [B,C,H,W] (patch_embed.proj's output) -> out_nchw [B,C,H,W] (what the stage hands to the head):

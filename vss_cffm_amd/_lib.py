@@ -178,6 +178,10 @@ SIGNATURES = {
     'cffm_ln_rows': (ci, [vp, vp, vp, vp, cl, ci, cf, vp]),
     'cffm_nchw_ln_rows': (ci, [vp, vp, vp, vp, ci, ci, ci, ci, cf, vp]),
     'cffm_ln_rows_nchw': (ci, [vp, vp, vp, vp, ci, ci, ci, ci, cf, vp]),
+    'cffm_ln_bwd_workspace_bytes': (cl, [cl, ci, ci]),
+    'cffm_ln_rows_bwd': (ci, [vp] * 7 + [cl, ci, cf, vp]),
+    'cffm_nchw_ln_rows_bwd': (ci, [vp] * 7 + [ci, ci, ci, ci, cf, vp]),
+    'cffm_ln_rows_nchw_bwd': (ci, [vp] * 7 + [ci, ci, ci, ci, cf, vp]),
     'cffm_mit_stage_infer_ws_floats': (cl, [MCP]),
     'cffm_mit_stage_infer': (ci, [MCP, MBP, vp, vp, vp, vp, vp, vp, vp, vp]),
     'cffm_patch_embed_fwd': (ci, [vp] * 6 + [ci] * 7 + [cf, vp]),

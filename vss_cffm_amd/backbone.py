@@ -32,6 +32,12 @@ With ``MixVisionTransformer.embed_impl = 'hip'`` on top of ``stage_impl = 'hip'`
 run of consecutive stages that take the stage call and whose ``patch_embed.proj`` is inside the limits of the library's patch-embedding
 kernel goes out as ONE call (``ops.mit_infer`` -> cffm_mit_infer) -- for ``mit_b0`` .. ``mit_b5`` the whole evaluation forward, with one
 workspace (the largest stage's) and the same bits on every call.  ``'torch'`` (the default) leaves the convolutions to stock Conv2d.
+
+On the modules' own path -- the one a training pass takes -- ``norm_impl = 'hip'`` (``MixVisionTransformer.set_norm_impl``) hands every
+LayerNorm to the library in both directions (``ops.layer_norm_rows`` / ``nchw_layer_norm_rows`` / ``layer_norm_rows_nchw`` -> cffm_ln_rows* and
+their ``_bwd`` partners): the embedding's flatten / transpose and the stage's reshape / permute / contiguous happen inside the same pass, the
+backward recomputes mean and rstd from the saved input, and the weight / bias gradients are summed in a fixed order.  ``'torch'`` (the
+default) is stock nn.LayerNorm, which is also what any norm outside the kernels' limits gets.
 """
 import math
 from functools import partial
@@ -41,13 +47,29 @@ import torch.nn as nn
 
 from . import _lib
 from .checkpoint import load_reference_checkpoint
-from .ops import (dwconv_gelu, mit_infer, mit_stage_cfg, mit_stage_infer, mit_stage_supported, mit_stage_tensors, mit_stages, patch_embed_out_hw,
-                  patch_embed_supported, sr_reduce, sr_reduce_supported, sra_attention)
+from .ops import (dwconv_gelu, layer_norm_rows, layer_norm_rows_nchw, ln_supported, mit_infer, mit_stage_cfg, mit_stage_infer, mit_stage_supported,
+                  mit_stage_tensors, mit_stages, nchw_layer_norm_rows, patch_embed_out_hw, patch_embed_supported, sr_reduce, sr_reduce_supported,
+                  sra_attention)
 from .registry import BACKBONES
 
 
 def _pair(v):
     return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def _norm_fused(impl, norm, x, c):
+    """whether `norm` of x, whose rows are c wide, takes the library's LayerNorm (norm_impl = 'hip'): a plain affine nn.LayerNorm over the
+    last c channels, fp32 tensors on the GPU (or under the emulator override), inside the kernels' limits.  Anything else: the stock line."""
+    return (impl == 'hip' and type(norm) is nn.LayerNorm and norm.elementwise_affine and norm.bias is not None
+            and tuple(norm.normalized_shape) == (c,) and (x.is_cuda or _lib._override is not None) and x.dtype == torch.float32
+            and norm.weight.dtype == torch.float32 and norm.weight.device == x.device and ln_supported(c, x.numel()))
+
+
+def _norm_rows(impl, norm, x):
+    """norm(x) of token rows [..., C]: one library call per direction with norm_impl = 'hip', the module's own forward otherwise"""
+    if _norm_fused(impl, norm, x, x.shape[-1]):
+        return layer_norm_rows(x, norm.weight, norm.bias, norm.eps)
+    return norm(x)
 
 
 def _init_weights(m):
@@ -137,6 +159,8 @@ class Attention(nn.Module):
     # limits (it raises when the library is missing); 'torch': the reference's op sequence, what everything else gets -- and the
     # default: as measured the fused pass does not make a mit_b1 training pass faster
     sr_impl = 'torch'
+    # 'hip': the LayerNorm behind the stock `sr` convolution is the library's, forward and backward (see MixVisionTransformer.norm_impl)
+    norm_impl = 'torch'
 
     def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, attn_drop=0., proj_drop=0., sr_ratio=1):
         super().__init__()
@@ -168,7 +192,7 @@ class Attention(nn.Module):
         B, N, C = x.shape
         if self._sr_fused(x, H, W):
             return sr_reduce(x, self.sr.weight, self.sr.bias, self.norm.weight, self.norm.bias, H, W, self.sr_ratio, self.norm.eps)
-        return self.norm(self.sr(x.permute(0, 2, 1).reshape(B, C, H, W)).reshape(B, C, -1).permute(0, 2, 1))
+        return _norm_rows(self.norm_impl, self.norm, self.sr(x.permute(0, 2, 1).reshape(B, C, H, W)).reshape(B, C, -1).permute(0, 2, 1))
 
     def forward(self, x, H, W):
         B, N, C = x.shape
@@ -185,6 +209,8 @@ class Attention(nn.Module):
 
 
 class Block(nn.Module):
+    norm_impl = 'torch'        # 'hip': norm1 / norm2 are the library's LayerNorm, forward and backward (see MixVisionTransformer.norm_impl)
+
     def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, qk_scale=None, drop=0., attn_drop=0., drop_path=0.,
                  act_layer=nn.GELU, norm_layer=nn.LayerNorm, sr_ratio=1):
         super().__init__()
@@ -197,12 +223,14 @@ class Block(nn.Module):
         self.apply(_init_weights)
 
     def forward(self, x, H, W):
-        x = x + self.drop_path(self.attn(self.norm1(x), H, W))
-        return x + self.drop_path(self.mlp(self.norm2(x), H, W))
+        x = x + self.drop_path(self.attn(_norm_rows(self.norm_impl, self.norm1, x), H, W))
+        return x + self.drop_path(self.mlp(_norm_rows(self.norm_impl, self.norm2, x), H, W))
 
 
 class OverlapPatchEmbed(nn.Module):
     """image (or the previous stage's map) -> token rows: a strided convolution with overlapping windows, then LayerNorm"""
+    # 'hip': flatten / transpose + norm are one library call per direction, no transposed copy (see MixVisionTransformer.norm_impl)
+    norm_impl = 'torch'
 
     def __init__(self, img_size=224, patch_size=7, stride=4, in_chans=3, embed_dim=768):
         super().__init__()
@@ -217,6 +245,8 @@ class OverlapPatchEmbed(nn.Module):
     def forward(self, x):
         x = self.proj(x)
         H, W = x.shape[2:]
+        if _norm_fused(self.norm_impl, self.norm, x, x.shape[1]):
+            return nchw_layer_norm_rows(x, self.norm.weight, self.norm.bias, self.norm.eps), H, W
         return self.norm(x.flatten(2).transpose(1, 2)), H, W
 
 
@@ -229,6 +259,13 @@ class MixVisionTransformer(nn.Module):
     # library's limits are ONE call, convolutions included; 'torch': stock Conv2d in front of every stage call -- the default
     # (DESIGN section 3t has the measurements: not faster at model level)
     embed_impl = 'torch'
+    # 'hip': on the modules' own path (the one a training pass takes) every LayerNorm -- the embeddings', the blocks' norm1 / norm2, the
+    # one behind a stock `sr` convolution, the stages' -- is the library's, forward and backward, the embeddings' and the stages' with
+    # their change of layout in the same pass (ops.layer_norm_rows / nchw_layer_norm_rows / layer_norm_rows_nchw): fp32 GPU tensors and
+    # plain affine nn.LayerNorms of a width inside the kernels' limits; any other norm takes the stock line, silently.  'torch': stock
+    # F.layer_norm -- the default (DESIGN section 3v has the measurements).  The owners of the call sites carry an attribute of the same
+    # name; set_norm_impl sets them all.
+    norm_impl = 'torch'
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dims=[64, 128, 256, 512], num_heads=[1, 2, 4, 8],
                  mlp_ratios=[4, 4, 4, 4], qkv_bias=False, qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.,
@@ -275,6 +312,14 @@ class MixVisionTransformer(nn.Module):
         for i, rates in enumerate(self._rates(drop_path_rate)):
             for blk, r in zip(getattr(self, 'block%d' % (i + 1)), rates):
                 blk.drop_path.drop_prob = r
+
+    def set_norm_impl(self, impl):
+        """norm_impl of the model and of every submodule that owns a LayerNorm call site"""
+        if impl not in ('torch', 'hip'):
+            raise ValueError("norm_impl must be 'torch' or 'hip', got %r" % (impl,))
+        for m in self.modules():
+            if hasattr(type(m), 'norm_impl'):
+                m.norm_impl = impl
 
     def freeze_patch_emb(self):
         self.patch_embed1.requires_grad = False      # (as in the reference: an attribute on the module, the parameters keep theirs)
@@ -398,8 +443,11 @@ class MixVisionTransformer(nn.Module):
             x, H, W = getattr(self, 'patch_embed%d' % i)(x)
             for blk in getattr(self, 'block%d' % i):
                 x = blk(x, H, W)
-            x = getattr(self, 'norm%d' % i)(x)
-            x = x.reshape(B, H, W, -1).permute(0, 3, 1, 2).contiguous()
+            norm = getattr(self, 'norm%d' % i)
+            if _norm_fused(self.norm_impl, norm, x, x.shape[-1]):
+                x = layer_norm_rows_nchw(x, norm.weight, norm.bias, H, W, norm.eps)
+            else:
+                x = norm(x).reshape(B, H, W, -1).permute(0, 3, 1, 2).contiguous()
             outs.append(x)
         return outs
 

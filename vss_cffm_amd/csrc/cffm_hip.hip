@@ -3038,6 +3038,44 @@ static void mln_launch(int which, hipStream_t st, const float* x, const float* g
     }
 }
 
+// records [2][C] the backward of M rows leaves in its workspace.  HW = 1: the rows form, one per workgroup of a capped grid; HW > 1: the
+// map forms, one per tile.  (A map of one pixel per image IS [B][C] rows: it runs as the rows form.)
+static long mln_bwd_records(long M, int C, int HW) {
+    if (HW == 1) {
+        const long RPB = 4 * (64 / mln_pw(C));
+        return std::min((long)MLN_BWD_GRID_CAP, (M + RPB - 1) / RPB);
+    }
+    return M / HW * mln_geom(C, HW).tiles;
+}
+// which: as mln_go, the forward whose backward runs
+template <int PW, int V>
+static void mln_bwd_go(int which, hipStream_t st, const float* x, const float* g, const float* dy, float* dx, float* rec, long M, int nimg,
+                       const MlnGeom& G, float eps) {
+    const size_t lds = mln_bwd_lds_floats(G, V) * sizeof(float);
+    if (which == 0) {
+        CFFM_LAUNCH((k_ln_rows_bwd<PW, V>), ((unsigned)mln_bwd_records(M, G.C, 1)), (256), 0, st, x, g, dy, dx, rec, M, G, eps);
+    } else if (which == 1) {
+        CFFM_LAUNCH((k_nchw_ln_rows_bwd<PW, V>), ((unsigned)(nimg * G.tiles)), (256), lds, st, x, g, dy, dx, rec, G, eps);
+    } else {
+        CFFM_LAUNCH((k_ln_rows_nchw_bwd<PW, V>), ((unsigned)(nimg * G.tiles)), (256), lds, st, x, g, dy, dx, rec, G, eps);
+    }
+}
+// (checked arguments -> the two launches)
+static void mln_bwd_launch(int which, hipStream_t st, const float* x, const float* g, const float* dy, float* dx, float* dgamma, float* dbeta,
+                           float* rec, long M, int nimg, int C, int HW, float eps) {
+    if (HW == 1) which = 0;
+    const MlnGeom G = mln_geom(C, HW);
+    if (G.C4 > 64) mln_bwd_go<64, 2>(which, st, x, g, dy, dx, rec, M, nimg, G, eps);
+    else switch (mln_pw(C)) {
+        case 4: mln_bwd_go<4, 1>(which, st, x, g, dy, dx, rec, M, nimg, G, eps); break;
+        case 8: mln_bwd_go<8, 1>(which, st, x, g, dy, dx, rec, M, nimg, G, eps); break;
+        case 16: mln_bwd_go<16, 1>(which, st, x, g, dy, dx, rec, M, nimg, G, eps); break;
+        case 32: mln_bwd_go<32, 1>(which, st, x, g, dy, dx, rec, M, nimg, G, eps); break;
+        default: mln_bwd_go<64, 1>(which, st, x, g, dy, dx, rec, M, nimg, G, eps);
+    }
+    CFFM_LAUNCH((k_ln_bwd_final), ((unsigned)(C / 2)), (MLN_FIN_SLICES), 0, st, rec, dgamma, dbeta, (int)mln_bwd_records(M, C, HW), C);
+}
+
 // workspace of one stage call (floats).  The residual stream alternates between xa and xb inside a block (xa -> proj + residual -> xb ->
 // fc2 + residual -> xa), so every block reads and leaves its rows in xa, whatever the depth.  z: the LayerNorm outputs and, once q and kv
 // are made from it, the attention output.  q | r (the reduced map) | kv are dead when fc1 runs: they share their room with h.
@@ -3232,6 +3270,41 @@ int cffm_ln_rows_nchw(const float* x_rows, const float* gamma, const float* beta
             "ln_rows_nchw: x_rows / gamma / beta / out_nchw must be non-null and 16-byte aligned");
     mln_launch(2, (hipStream_t)stream, x_rows, gamma, beta, out_nchw, (long)B * H * W, B, C, H * W, eps);
     CHECK_LAUNCH("ln_rows_nchw");
+    return 0;
+}
+
+long cffm_ln_bwd_workspace_bytes(long M, int C, int HW) {
+    if (mln_check("ln_bwd_workspace_bytes", C, 0.f)) return -1;
+    if (!(M >= 1 && HW >= 1 && M % HW == 0 && M * C < (1L << 31)))
+        return fail(-1, "ln_bwd_workspace_bytes: M=%ld rows of C=%d, HW=%d: M must be a positive multiple of HW >= 1 and M*C below 2^31", M, C, HW);
+    return mln_bwd_records(M, C, HW) * 2 * C * (long)sizeof(float);
+}
+int cffm_ln_rows_bwd(const float* x, const float* gamma, const float* dout, float* dx, float* dgamma, float* dbeta, void* ws, long M, int C,
+                     float eps, void* stream) {
+    TRY(mln_check("ln_rows_bwd", C, eps));
+    REQUIRE(M >= 1 && M * C < (1L << 31), "ln_rows_bwd: M=%ld rows of C=%d: M must be at least 1 and M*C below 2^31", M, C);
+    REQUIRE(aligned16(x) && aligned16(gamma) && aligned16(dout) && aligned16(dx) && aligned16(dgamma) && aligned16(dbeta) && aligned16(ws),
+            "ln_rows_bwd: x / gamma / dout / dx / dgamma / dbeta / ws must be non-null and 16-byte aligned");
+    mln_bwd_launch(0, (hipStream_t)stream, x, gamma, dout, dx, dgamma, dbeta, (float*)ws, M, 0, C, 1, eps);
+    CHECK_LAUNCH("ln_rows_bwd");
+    return 0;
+}
+int cffm_nchw_ln_rows_bwd(const float* x_nchw, const float* gamma, const float* dout_rows, float* dx_nchw, float* dgamma, float* dbeta, void* ws,
+                          int B, int C, int H, int W, float eps, void* stream) {
+    TRY(mln_check_map("nchw_ln_rows_bwd", B, C, H, W, eps));
+    REQUIRE(aligned16(x_nchw) && aligned16(gamma) && aligned16(dout_rows) && aligned16(dx_nchw) && aligned16(dgamma) && aligned16(dbeta) && aligned16(ws),
+            "nchw_ln_rows_bwd: x_nchw / gamma / dout_rows / dx_nchw / dgamma / dbeta / ws must be non-null and 16-byte aligned");
+    mln_bwd_launch(1, (hipStream_t)stream, x_nchw, gamma, dout_rows, dx_nchw, dgamma, dbeta, (float*)ws, (long)B * H * W, B, C, H * W, eps);
+    CHECK_LAUNCH("nchw_ln_rows_bwd");
+    return 0;
+}
+int cffm_ln_rows_nchw_bwd(const float* x_rows, const float* gamma, const float* dout_nchw, float* dx_rows, float* dgamma, float* dbeta, void* ws,
+                          int B, int C, int H, int W, float eps, void* stream) {
+    TRY(mln_check_map("ln_rows_nchw_bwd", B, C, H, W, eps));
+    REQUIRE(aligned16(x_rows) && aligned16(gamma) && aligned16(dout_nchw) && aligned16(dx_rows) && aligned16(dgamma) && aligned16(dbeta) && aligned16(ws),
+            "ln_rows_nchw_bwd: x_rows / gamma / dout_nchw / dx_rows / dgamma / dbeta / ws must be non-null and 16-byte aligned");
+    mln_bwd_launch(2, (hipStream_t)stream, x_rows, gamma, dout_nchw, dx_rows, dgamma, dbeta, (float*)ws, (long)B * H * W, B, C, H * W, eps);
+    CHECK_LAUNCH("ln_rows_nchw_bwd");
     return 0;
 }
 

@@ -1,6 +1,7 @@
 // mitln_kernels.h -- LayerNorm of fp32 token rows at any width C = 4 * C4, 16 <= C <= 512, and the two layout changes at the ends of a MiT
 // stage (backbones/mix_transformer.py: OverlapPatchEmbed.forward's flatten(2).transpose(1, 2) + norm; forward_features' norm_i +
-// reshape(B, H, W, C).permute(0, 3, 1, 2).contiguous()).  Inference only: nothing is saved.
+// reshape(B, H, W, C).permute(0, 3, 1, 2).contiguous()), forward and backward.  The forwards save nothing: the backwards (second half of
+// this file) recompute mean and rstd from the input with the forward's own arithmetic.
 //
 // One row lives in the registers of a GROUP of PW lanes of one wave (PW a power of two, 4..64): lane j of the group holds the 16-byte
 // chunks j, j + L, ... (V of them) of the row, L = ceil(C4 / V) <= PW lanes of the group have work, the others carry zeros.  V = 1 up
@@ -69,9 +70,10 @@ __device__ __forceinline__ float mln_sum(float v) {
     return v;
 }
 
-// LayerNorm of the row held by this lane's group: x[k] = chunk (j + k L) of the row (zeros where !act[k]) -> the normalised chunks
+// mean, one re-centring and variance of the row held by this lane's group: x[k] = chunk (j + k L) of the row (zeros where !act[k]) -> the
+// centred values (zeros where !act[k]); returns rstd.  The forward and the backwards share it: xhat = x[k] * rstd on both sides.
 template <int PW, int V>
-__device__ __forceinline__ void mln_row(f32x4 (&x)[V], const bool (&act)[V], const f32x4 (&g)[V], const f32x4 (&b)[V], int C, float eps) {
+__device__ __forceinline__ float mln_centre(f32x4 (&x)[V], const bool (&act)[V], int C, float eps) {
     const float n = (float)C;
     float s = 0.f;
 #pragma unroll
@@ -92,7 +94,13 @@ __device__ __forceinline__ void mln_row(f32x4 (&x)[V], const bool (&act)[V], con
         for (int e = 0; e < 4; ++e) x[k][e] = act[k] ? x[k][e] - m1 : 0.f;
         s += (x[k][0] * x[k][0] + x[k][1] * x[k][1]) + (x[k][2] * x[k][2] + x[k][3] * x[k][3]);
     }
-    const float rstd = 1.f / sqrtf(mln_sum<PW>(s) / n + eps);
+    return 1.f / sqrtf(mln_sum<PW>(s) / n + eps);
+}
+
+// LayerNorm of the row held by this lane's group: x[k] as for mln_centre -> the normalised chunks
+template <int PW, int V>
+__device__ __forceinline__ void mln_row(f32x4 (&x)[V], const bool (&act)[V], const f32x4 (&g)[V], const f32x4 (&b)[V], int C, float eps) {
+    const float rstd = mln_centre<PW, V>(x, act, C, eps);
 #pragma unroll
     for (int k = 0; k < V; ++k)
 #pragma unroll
@@ -257,4 +265,250 @@ __global__ void __launch_bounds__(256) k_ln_rows_nchw(const float* __restrict__ 
                     if (4 * i + e < np) dst[e] = v[e];
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------ backward
+// dx = rstd * (g - mean(g) - xhat * mean(g * xhat)), g = gamma * dy, in the row layout of the forwards.  mean and rstd are NOT saved by the
+// forward: mln_centre recomputes them from x, so xhat has the forward's bits.  dgamma[c] = sum over rows of dy * xhat, dbeta[c] = sum
+// over rows of dy: a lane adds up its channels over the rows it handles, the workgroup adds its row groups in a fixed order through LDS
+// (mln_record) and writes ONE record [2][C] to the workspace; k_ln_bwd_final adds the records.  How many records there are and the
+// order they are added in follow from (M, C, HW) alone: the same bits run after run, on any device.
+
+#define MLN_BWD_GRID_CAP 1024                      // rows form: workgroups = records at most (the map forms: one record per tile)
+#define MLN_RED_FLOATS(V) (2048 * (V))             // LDS of mln_record: 256 lanes x (dgamma | dbeta) x V chunks
+
+// this lane's chunks of gamma
+template <int V>
+__device__ __forceinline__ void mln_gamma(const float* __restrict__ gamma, const MlnGeom& G, int j, bool (&act)[V], f32x4 (&g)[V]) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        const int ch = j + k * G.L;
+        act[k] = j < G.L && ch < G.C4;
+        g[k] = act[k] ? *(const f32x4*)(gamma + 4 * ch) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+}
+
+// backward of the row held by this lane's group: x[k] / dy[k] = this lane's chunks of the row and of its output gradient (zeros where
+// !act[k] or the row is not live) -> dx in x[k]; dg / db take the row's terms of dgamma / dbeta
+template <int PW, int V>
+__device__ __forceinline__ void mln_row_bwd(f32x4 (&x)[V], f32x4 (&dy)[V], const bool (&act)[V], const f32x4 (&g)[V], bool live, int C, float eps,
+                                            f32x4 (&dg)[V], f32x4 (&db)[V]) {
+    const float n = (float)C;
+    const float rstd = mln_centre<PW, V>(x, act, C, eps);
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float xh = x[k][e] * rstd, d = dy[k][e];
+            dg[k][e] += live ? d * xh : 0.f;        // (a row past the end: x = 0 and, at eps = 0, rstd = inf)
+            db[k][e] += d;
+            x[k][e] = xh;
+            dy[k][e] = g[k][e] * d;
+        }
+        s1 += (dy[k][0] + dy[k][1]) + (dy[k][2] + dy[k][3]);
+        s2 += (dy[k][0] * x[k][0] + dy[k][1] * x[k][1]) + (dy[k][2] * x[k][2] + dy[k][3] * x[k][3]);
+    }
+    const float a = mln_sum<PW>(s1) / n, c = mln_sum<PW>(s2) / n;
+#pragma unroll
+    for (int k = 0; k < V; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[k][e] = rstd * (dy[k][e] - a - x[k][e] * c);
+}
+
+// the workgroup's record: R[row group][dgamma | dbeta][k][lane of the group] <- every lane's sums; then lane (which, k, j) adds the row
+// groups in their order and writes chunk j + k L of rec[which][C].  R: MLN_RED_FLOATS(V) floats of LDS that nobody reads or writes any
+// more when the first lane gets here (the caller's barrier)
+template <int PW, int V>
+__device__ __forceinline__ void mln_record(f32x4* R, const f32x4 (&dg)[V], const f32x4 (&db)[V], const MlnGeom& G, float* __restrict__ rec) {
+    constexpr int RPB = 4 * (64 / PW);
+    const int j = threadIdx.x & (PW - 1), sub = threadIdx.x / PW;
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        R[((sub * 2 + 0) * V + k) * PW + j] = dg[k];
+        R[((sub * 2 + 1) * V + k) * PW + j] = db[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * V * PW) {
+        const int k = (threadIdx.x / PW) % V, which = threadIdx.x / (PW * V);
+        f32x4 s = R[(which * V + k) * PW + j];
+        for (int r = 1; r < RPB; ++r) s += R[((r * 2 + which) * V + k) * PW + j];
+        const int ch = j + k * G.L;
+        if (j < G.L && ch < G.C4) *(f32x4*)(rec + which * G.C + 4 * ch) = s;
+    }
+}
+
+// dx[M][C] of out = LN(x[M][C]) from dy[M][C]; rec[gridDim.x][2][C].  Block and row walk of k_ln_rows; the grid is at most
+// MLN_BWD_GRID_CAP workgroups.
+template <int PW, int V>
+__global__ void __launch_bounds__(256) k_ln_rows_bwd(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ dy,
+                                                      float* __restrict__ dx, float* __restrict__ rec, long M, MlnGeom G, float eps) {
+    constexpr int RPB = 4 * (64 / PW);
+    __shared__ f32x4 R[MLN_RED_FLOATS(V) / 4];
+    const int j = threadIdx.x & (PW - 1), sub = threadIdx.x / PW;
+    const f32x4 z = (f32x4){0.f, 0.f, 0.f, 0.f};
+    bool act[V];
+    f32x4 g[V], dg[V], db[V];
+    mln_gamma<V>(gamma, G, j, act, g);
+#pragma unroll
+    for (int k = 0; k < V; ++k) dg[k] = db[k] = z;
+    for (long row0 = (long)blockIdx.x * RPB; row0 < M; row0 += (long)gridDim.x * RPB) {   // (uniform over the workgroup)
+        const long row = row0 + sub;
+        const bool live = row < M;
+        f32x4 v[V], d[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            v[k] = (live && act[k]) ? *(const f32x4*)(x + row * G.C + 4 * (j + k * G.L)) : z;
+            d[k] = (live && act[k]) ? *(const f32x4*)(dy + row * G.C + 4 * (j + k * G.L)) : z;
+        }
+        mln_row_bwd<PW, V>(v, d, act, g, live, G.C, eps, dg, db);
+#pragma unroll
+        for (int k = 0; k < V; ++k)
+            if (live && act[k]) *(f32x4*)(dx + row * G.C + 4 * (j + k * G.L)) = v[k];
+    }
+    mln_record<PW, V>(R, dg, db, G, rec + (long)blockIdx.x * 2 * G.C);
+}
+
+// one image's NCHW pixels p0 .. p0 + np - 1 (src = channel 0, pixel p0) -> T[pixel][LD]: the input side of k_nchw_ln_rows
+__device__ __forceinline__ void mln_tile_in(float* T, const float* __restrict__ src0, const MlnGeom& G, int np) {
+    const int q = threadIdx.x & 3, PG = G.TP / 4, items = MLN_ITEMS(G);
+    for (int it0 = 0; it0 < items; it0 += 64) {               // (uniform over the workgroup: the exchanges need whole waves)
+        const int it = it0 + (threadIdx.x >> 2);
+        const bool live = it < items;
+        const int cq = it / PG, i = it % PG;
+        f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (live && 4 * i < np) {
+            const float* src = src0 + (long)(4 * cq + q) * G.HW + 4 * i;
+            if (4 * i + 3 < np) v = *(const f32x4u*)src;
+            else
+                for (int e = 0; e < 4; ++e)
+                    if (4 * i + e < np) v[e] = src[e];
+        }
+        v = mln_quad_transpose(v, q);
+        if (live) *(f32x4*)(T + (4 * i + q) * G.LD + 4 * cq) = v;   // (pixels past np: zeros, never read back)
+    }
+}
+// T[pixel][LD], rows 0 .. np - 1 -> one image's NCHW pixels p0 .. p0 + np - 1 (dst0 = channel 0, pixel p0): the output side of k_ln_rows_nchw
+__device__ __forceinline__ void mln_tile_out(const float* T, float* __restrict__ dst0, const MlnGeom& G, int np) {
+    const int q = threadIdx.x & 3, PG = G.TP / 4, items = MLN_ITEMS(G);
+    for (int it0 = 0; it0 < items; it0 += 64) {
+        const int it = it0 + (threadIdx.x >> 2);
+        const bool live = it < items;
+        const int cq = it / PG, i = it % PG;
+        f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (live && 4 * i + q < np) v = *(const f32x4*)(T + (4 * i + q) * G.LD + 4 * cq);
+        v = mln_quad_transpose(v, q);
+        if (live && 4 * i < np) {
+            float* dst = dst0 + (long)(4 * cq + q) * G.HW + 4 * i;
+            if (4 * i + 3 < np) *(f32x4u*)dst = v;
+            else
+                for (int e = 0; e < 4; ++e)
+                    if (4 * i + e < np) dst[e] = v[e];
+        }
+    }
+}
+
+// dynamic LDS of the two transposing backwards (floats): the tile, and room for mln_record once the tile is dead
+static inline size_t mln_bwd_lds_floats(const MlnGeom& G, int V) {
+    const size_t tile = (size_t)G.TP * G.LD, red = MLN_RED_FLOATS(V);
+    return tile > red ? tile : red;
+}
+
+// backward of k_ln_rows_nchw (a stage's norm + the NCHW map): x [B][HW][C] rows, dy [B][C][HW] through the tile -> dx [B][HW][C] rows;
+// rec[B * tiles][2][C].  grid = B * tiles, 256 threads, dynamic LDS = mln_bwd_lds_floats.
+template <int PW, int V>
+__global__ void __launch_bounds__(256) k_ln_rows_nchw_bwd(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ dy,
+                                                           float* __restrict__ dx, float* __restrict__ rec, MlnGeom G, float eps) {
+    CFFM_DYN_SMEM(smem);
+    float* T = (float*)smem;
+    const int img = blockIdx.x / G.tiles, p0 = (blockIdx.x % G.tiles) * G.TP;
+    const int np = G.HW - p0 < G.TP ? G.HW - p0 : G.TP;
+    mln_tile_in(T, dy + (long)img * G.C * G.HW + p0, G, np);
+    __syncthreads();
+    constexpr int RPB = 4 * (64 / PW);
+    const int j = threadIdx.x & (PW - 1), sub = threadIdx.x / PW;
+    const f32x4 z = (f32x4){0.f, 0.f, 0.f, 0.f};
+    bool act[V];
+    f32x4 g[V], dg[V], db[V];
+    mln_gamma<V>(gamma, G, j, act, g);
+#pragma unroll
+    for (int k = 0; k < V; ++k) dg[k] = db[k] = z;
+    const long base = ((long)img * G.HW + p0) * G.C;
+    for (int r0 = 0; r0 < G.TP; r0 += RPB) {
+        const int r = r0 + sub;
+        const bool live = r < np;
+        f32x4 v[V], d[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            v[k] = (live && act[k]) ? *(const f32x4*)(x + base + (long)r * G.C + 4 * (j + k * G.L)) : z;
+            d[k] = (live && act[k]) ? *(const f32x4*)(T + r * G.LD + 4 * (j + k * G.L)) : z;
+        }
+        mln_row_bwd<PW, V>(v, d, act, g, live, G.C, eps, dg, db);
+#pragma unroll
+        for (int k = 0; k < V; ++k)
+            if (live && act[k]) *(f32x4*)(dx + base + (long)r * G.C + 4 * (j + k * G.L)) = v[k];
+    }
+    __syncthreads();                                          // (the tile is dead: mln_record takes its room)
+    mln_record<PW, V>((f32x4*)T, dg, db, G, rec + (long)blockIdx.x * 2 * G.C);
+}
+
+// backward of k_nchw_ln_rows (the embedding's flatten / transpose + norm): x [B][C][HW] through the tile, dy [B][HW][C] rows; every row
+// group overwrites its own tile row with dx, and the tile leaves as dx [B][C][HW].  Grid, block, LDS and rec as k_ln_rows_nchw_bwd.
+template <int PW, int V>
+__global__ void __launch_bounds__(256) k_nchw_ln_rows_bwd(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ dy,
+                                                           float* __restrict__ dx, float* __restrict__ rec, MlnGeom G, float eps) {
+    CFFM_DYN_SMEM(smem);
+    float* T = (float*)smem;
+    const int img = blockIdx.x / G.tiles, p0 = (blockIdx.x % G.tiles) * G.TP;
+    const int np = G.HW - p0 < G.TP ? G.HW - p0 : G.TP;
+    mln_tile_in(T, x + (long)img * G.C * G.HW + p0, G, np);
+    __syncthreads();
+    constexpr int RPB = 4 * (64 / PW);
+    const int j = threadIdx.x & (PW - 1), sub = threadIdx.x / PW;
+    const f32x4 z = (f32x4){0.f, 0.f, 0.f, 0.f};
+    bool act[V];
+    f32x4 g[V], dg[V], db[V];
+    mln_gamma<V>(gamma, G, j, act, g);
+#pragma unroll
+    for (int k = 0; k < V; ++k) dg[k] = db[k] = z;
+    const long base = ((long)img * G.HW + p0) * G.C;
+    for (int r0 = 0; r0 < G.TP; r0 += RPB) {
+        const int r = r0 + sub;
+        const bool live = r < np;
+        f32x4 v[V], d[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            v[k] = (live && act[k]) ? *(const f32x4*)(T + r * G.LD + 4 * (j + k * G.L)) : z;
+            d[k] = (live && act[k]) ? *(const f32x4*)(dy + base + (long)r * G.C + 4 * (j + k * G.L)) : z;
+        }
+        mln_row_bwd<PW, V>(v, d, act, g, live, G.C, eps, dg, db);
+#pragma unroll
+        for (int k = 0; k < V; ++k)
+            if (live && act[k]) *(f32x4*)(T + r * G.LD + 4 * (j + k * G.L)) = v[k];   // (a lane rewrites the chunks it read, nobody else's)
+    }
+    __syncthreads();
+    mln_tile_out(T, dx + (long)img * G.C * G.HW + p0, G, np);
+    __syncthreads();                                          // (the tile has left: mln_record takes its room)
+    mln_record<PW, V>((f32x4*)T, dg, db, G, rec + (long)blockIdx.x * 2 * G.C);
+}
+
+// dgamma[C] | dbeta[C] = the sum of R records [2][C].  A workgroup takes ONE of the record's C / 2 16-byte chunks, its 256 lanes are 256
+// slices: slice s adds the records s, s + 256, s + 512, ... in that order (1800 records: 8 loads a lane, independent of each other),
+// then the slices are added as a binary tree through LDS -- a fixed shape, whatever R.  grid = C / 2, 256 threads.  (8 chunks x 32
+// slices per workgroup, the first form, walked 57 records per lane one load after the other: 18.5 us at stage 1, more than the backward.)
+#define MLN_FIN_SLICES 256
+__global__ void __launch_bounds__(MLN_FIN_SLICES) k_ln_bwd_final(const float* __restrict__ rec, float* __restrict__ dgamma,
+                                                                  float* __restrict__ dbeta, int R, int C) {
+    __shared__ f32x4 S[MLN_FIN_SLICES];
+    const int s = threadIdx.x, ch = blockIdx.x;               // slice; chunk of the record
+    f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int r = s; r < R; r += MLN_FIN_SLICES) acc += *(const f32x4*)(rec + (long)r * 2 * C + 4 * ch);
+    S[s] = acc;
+    __syncthreads();
+    for (int h = MLN_FIN_SLICES / 2; h >= 1; h >>= 1) {
+        if (s < h) S[s] += S[s + h];
+        __syncthreads();
+    }
+    if (s == 0) *(f32x4*)(4 * ch < C ? dgamma + 4 * ch : dbeta + (4 * ch - C)) = S[0];
 }

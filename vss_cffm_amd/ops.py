@@ -1530,7 +1530,18 @@ def _infer_only(ts, what):
         raise _lib.CffmError('%s is inference only: call it under torch.no_grad() or with tensors that do not require grad' % what)
 
 
+def ln_supported(c, numel):
+    """whether rows of width c, numel elements in all, are inside the limits of the LayerNorm calls"""
+    return c % 4 == 0 and LN_MIN_C <= c <= LN_MAX_C and 0 < numel < 2 ** 31
+
+
 def _ln_operands(what, x, weight, bias, c):
+    _ln_checked(what, x, weight, bias, c)
+    _infer_only((x, weight, bias), what)
+    return tuple(_sra_operand(t.detach()) for t in (x, weight, bias))
+
+
+def _ln_checked(what, x, weight, bias, c):
     for t, name in ((x, 'x'), (weight, 'weight'), (bias, 'bias')):
         if not isinstance(t, torch.Tensor):
             raise _lib.CffmError('%s: %s must be a tensor' % (what, name))
@@ -1539,8 +1550,6 @@ def _ln_operands(what, x, weight, bias, c):
         raise _lib.CffmError('%s: weight and bias must be [%d] tensors on %s' % (what, c, x.device))
     if c % 4 or not LN_MIN_C <= c <= LN_MAX_C:
         raise _lib.CffmError('%s: C=%d must be a multiple of 4 in %d..%d' % (what, c, LN_MIN_C, LN_MAX_C))
-    _infer_only((x, weight, bias), what)
-    return tuple(_sra_operand(t.detach()) for t in (x, weight, bias))
 
 
 def _ln_out(what, out, shape, x):
@@ -1590,6 +1599,88 @@ def ln_rows_nchw(x, weight, bias, H, W, eps=1e-5, out=None):
     lib = _lib.get()
     _lib.check(lib.cffm_ln_rows_nchw(_ptr(xs), _ptr(w), _ptr(b), _ptr(out), b_, c, int(H), int(W), float(eps), _stream(xs)), lib)
     return out
+
+
+# ---------------------------------------------------------------------------------------------- the same three LayerNorms, differentiable
+_LN_ROWS, _LN_FROM_NCHW, _LN_TO_NCHW = 0, 1, 2
+
+
+class _LayerNormFn(torch.autograd.Function):
+    """The three LayerNorm calls above with their backwards (csrc/mitln_kernels.h).  `form`: rows -> rows (dims = (M, C)), NCHW -> rows,
+    rows -> NCHW (dims = (B, C, H, W)).  The forward is the inference call; saved: x, weight, bias -- mean and rstd are recomputed in the
+    backward, whose workspace (the dgamma / dbeta records) lives only inside it."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, form, dims, eps):
+        lib = _lib.get()
+        # every input contiguous BEFORE the stream is looked up or anything is enqueued: a copy made later would be ordered against nothing
+        x, weight, bias = _sra_operand(x), _sra_operand(weight), _sra_operand(bias)
+        if form == _LN_ROWS:
+            out = torch.empty_like(x)
+            rc = lib.cffm_ln_rows(_ptr(x), _ptr(weight), _ptr(bias), _ptr(out), *dims, eps, _stream(x))
+        elif form == _LN_FROM_NCHW:
+            b, c, h, w = dims
+            out = torch.empty((b, h * w, c), dtype=torch.float32, device=x.device)
+            rc = lib.cffm_nchw_ln_rows(_ptr(x), _ptr(weight), _ptr(bias), _ptr(out), *dims, eps, _stream(x))
+        else:
+            b, c, h, w = dims
+            out = torch.empty((b, c, h, w), dtype=torch.float32, device=x.device)
+            rc = lib.cffm_ln_rows_nchw(_ptr(x), _ptr(weight), _ptr(bias), _ptr(out), *dims, eps, _stream(x))
+        _lib.check(rc, lib)
+        ctx.save_for_backward(x, weight, bias)
+        ctx.form, ctx.dims, ctx.eps = form, dims, eps
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        lib = _lib.get()
+        x, weight, bias = ctx.saved_tensors
+        form, dims, eps = ctx.form, ctx.dims, ctx.eps
+        dout = _sra_operand(dout)
+        dx, dgamma, dbeta = torch.empty_like(x), torch.empty_like(weight), torch.empty_like(bias)
+        if form == _LN_ROWS:
+            rows, c, hw = dims[0], dims[1], 1
+        else:
+            rows, c, hw = dims[0] * dims[2] * dims[3], dims[1], dims[2] * dims[3]
+        nbytes = lib.cffm_ln_bwd_workspace_bytes(rows, c, hw)
+        if nbytes < 0:
+            raise _lib.CffmError('libcffm_hip: %s' % lib.cffm_last_error().decode())
+        ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
+        fn = (lib.cffm_ln_rows_bwd, lib.cffm_nchw_ln_rows_bwd, lib.cffm_ln_rows_nchw_bwd)[form]
+        _lib.check(fn(_ptr(x), _ptr(weight), _ptr(dout), _ptr(dx), _ptr(dgamma), _ptr(dbeta), _ptr(ws), *dims, eps, _stream(x)), lib)
+        return dx, dgamma, dbeta, None, None, None
+
+
+def layer_norm_rows(x, weight, bias, eps=1e-5):
+    """``ln_rows`` with a backward: F.layer_norm(x, (C,), weight, bias, eps) of fp32 token rows x [..., C], C a multiple of 4 in 16..512,
+    differentiable in x, weight and bias (``cffm_ln_rows`` / ``cffm_ln_rows_bwd``; dweight / dbias bit-reproducible).  The output has the
+    bits of ``ln_rows``; x, weight and bias are all that is saved, and under no_grad nothing is.  Launches on the current stream."""
+    if not isinstance(x, torch.Tensor) or x.dim() < 1:
+        raise _lib.CffmError('layer_norm_rows: x must be a [..., C] tensor')
+    c = x.shape[-1]
+    _ln_checked('layer_norm_rows', x, weight, bias, c)
+    if x.numel() == 0:
+        raise _lib.CffmError('layer_norm_rows: x is empty')
+    return _LayerNormFn.apply(x, weight, bias, _LN_ROWS, (x.numel() // c, c), float(eps))
+
+
+def nchw_layer_norm_rows(x, weight, bias, eps=1e-5):
+    """``nchw_ln_rows`` with a backward: F.layer_norm(x.flatten(2).transpose(1, 2), (C,), weight, bias, eps) of an fp32 map x [B,C,H,W] ->
+    token rows [B, H*W, C]; neither direction makes a transposed copy (``cffm_nchw_ln_rows`` / ``cffm_nchw_ln_rows_bwd``)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise _lib.CffmError('nchw_layer_norm_rows: x must be a [B,C,H,W] tensor')
+    _ln_checked('nchw_layer_norm_rows', x, weight, bias, x.shape[1])
+    return _LayerNormFn.apply(x, weight, bias, _LN_FROM_NCHW, tuple(x.shape), float(eps))
+
+
+def layer_norm_rows_nchw(x, weight, bias, H, W, eps=1e-5):
+    """``ln_rows_nchw`` with a backward: F.layer_norm(x, (C,), weight, bias, eps).reshape(B, H, W, C).permute(0, 3, 1, 2).contiguous() of
+    fp32 token rows x [B, H*W, C] -> the map [B,C,H,W] (``cffm_ln_rows_nchw`` / ``cffm_ln_rows_nchw_bwd``)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != int(H) * int(W):
+        raise _lib.CffmError('layer_norm_rows_nchw: x must be a [B, H*W, C] tensor')
+    _ln_checked('layer_norm_rows_nchw', x, weight, bias, x.shape[2])
+    return _LayerNormFn.apply(x, weight, bias, _LN_TO_NCHW, (x.shape[0], x.shape[2], int(H), int(W)), float(eps))
 
 
 MIT_HEAD_SIZES = (32, 64)
