@@ -675,6 +675,28 @@ int cffm_mit_stage_infer(const cffm_mit_stage_cfg* c, const cffm_mit_block_param
 int cffm_patch_embed_fwd(const float* x_nchw, const float* w, const float* b, const float* gamma, const float* beta, float* out_rows, int B,
                          int Cin, int H, int W, int Cout, int k, int stride, float eps, void* stream);
 
+/* added under ABI 13, additive: the patch embedding for a training pass (csrc/pembed_kernels.h, second half).
+ *   cffm_patch_embed_fwd_train   cffm_patch_embed_fwd that also stores z_rows [B][Ho*Wo][Cout], the pre-LayerNorm rows (convolution + bias:
+ *                                the values the LayerNorm epilogue reads); out_rows has the bits of cffm_patch_embed_fwd.
+ *   cffm_patch_embed_bwd         dout_rows [B][Ho*Wo][Cout] -> dgamma, dbeta [Cout] and dz (cffm_ln_rows_bwd's kernels on z_rows: mean and rstd
+ *                                recomputed), then dw [Cout][Cin][k][k] = sum over the output pixels of dz x patch and db [Cout] = sum of dz,
+ *                                and -- (k, stride) = (3, 2) and dx_nchw non-null -- dx_nchw [B][Cin][H][W] = the taps of dz that reach each
+ *                                input pixel, times w (a pixel no tap reaches: exact zero).  dx_nchw == NULL skips the input gradient; with
+ *                                (7, 4) a non-null dx_nchw is refused.
+ * Products in dw and dx: the forward's three-pass bf16 split, fp32 accumulation; db, dgamma, dbeta: fp32 sums.  No atomics: the contraction
+ * over the output pixels is split into slabs whose count and order follow from the shapes alone, a second kernel adds them in slab order:
+ * the same bits on every call, on any device.  workspace: cffm_patch_embed_bwd_workspace_bytes(..., with_dx) bytes (with_dx = whether
+ * dx_nchw will be non-null), 16-byte aligned, need not be initialised: every byte that is read is written by the same call; dz lives there.
+ * Limits as cffm_patch_embed_fwd.  Errors (nothing is enqueued, every output stays as it is; the workspace query returns < 0): these limits,
+ * a null pointer (dx_nchw excepted) or one that is not 16-byte aligned, (7, 4) with dx.  No allocation, no host round trip, everything on
+ * `stream` alone. */
+int cffm_patch_embed_fwd_train(const float* x_nchw, const float* w, const float* b, const float* gamma, const float* beta, float* out_rows,
+                               float* z_rows, int B, int Cin, int H, int W, int Cout, int k, int stride, float eps, void* stream);
+long cffm_patch_embed_bwd_workspace_bytes(int B, int Cin, int H, int W, int Cout, int k, int stride, int with_dx);   /* < 0: refused */
+int cffm_patch_embed_bwd(const float* x_nchw, const float* w, const float* gamma, const float* z_rows, const float* dout_rows,
+                         float* dx_nchw /* may be NULL */, float* dw, float* db, float* dgamma, float* dbeta, void* workspace, int B, int Cin,
+                         int H, int W, int Cout, int k, int stride, float eps, void* stream);
+
 /* n = 1..4 consecutive MiT stages, each WITH its patch embedding, as one call: per stage cffm_patch_embed_fwd's kernel writes the
  * normalised rows straight into the stage's residual buffer (cffm_nchw_ln_rows does not run), then the blocks and cffm_ln_rows_nchw exactly as
  * cffm_mit_stage_infer enqueues them.  x_nchw [B, stages[0].Cin, Hin, Win] is stage 0's input, outs[i] (host array of n device pointers)

@@ -185,6 +185,9 @@ SIGNATURES = {
     'cffm_mit_stage_infer_ws_floats': (cl, [MCP]),
     'cffm_mit_stage_infer': (ci, [MCP, MBP, vp, vp, vp, vp, vp, vp, vp, vp]),
     'cffm_patch_embed_fwd': (ci, [vp] * 6 + [ci] * 7 + [cf, vp]),
+    'cffm_patch_embed_fwd_train': (ci, [vp] * 7 + [ci] * 7 + [cf, vp]),
+    'cffm_patch_embed_bwd_workspace_bytes': (cl, [ci] * 8),
+    'cffm_patch_embed_bwd': (ci, [vp] * 11 + [ci] * 7 + [cf, vp]),
     'cffm_mit_infer_ws_floats': (cl, [MSP, ci]),
     'cffm_mit_infer': (ci, [MSP, ci, vp, C.POINTER(vp), vp, vp]),
 }

@@ -38,6 +38,11 @@ LayerNorm to the library in both directions (``ops.layer_norm_rows`` / ``nchw_la
 their ``_bwd`` partners): the embedding's flatten / transpose and the stage's reshape / permute / contiguous happen inside the same pass, the
 backward recomputes mean and rstd from the saved input, and the weight / bias gradients are summed in a fixed order.  ``'torch'`` (the
 default) is stock nn.LayerNorm, which is also what any norm outside the kernels' limits gets.
+
+On the same path ``conv_impl = 'hip'`` (``MixVisionTransformer.set_conv_impl``) hands each overlapping patch embedding -- the strided
+convolution, flatten / transpose and its LayerNorm -- to the library as one call per direction (``ops.overlap_patch_embed`` ->
+cffm_patch_embed_fwd_train / cffm_patch_embed_bwd): bf16-split products, every gradient summed in a fixed order.  ``'torch'`` (the default)
+is stock Conv2d, which is also what a convolution outside the kernel's limits and a 7 x 7 embedding whose input requires grad get.
 """
 import math
 from functools import partial
@@ -48,8 +53,8 @@ import torch.nn as nn
 from . import _lib
 from .checkpoint import load_reference_checkpoint
 from .ops import (dwconv_gelu, layer_norm_rows, layer_norm_rows_nchw, ln_supported, mit_infer, mit_stage_cfg, mit_stage_infer, mit_stage_supported,
-                  mit_stage_tensors, mit_stages, nchw_layer_norm_rows, patch_embed_out_hw, patch_embed_supported, sr_reduce, sr_reduce_supported,
-                  sra_attention)
+                  mit_stage_tensors, mit_stages, nchw_layer_norm_rows, overlap_patch_embed, patch_embed_out_hw, patch_embed_supported, sr_reduce,
+                  sr_reduce_supported, sra_attention)
 from .registry import BACKBONES
 
 
@@ -231,6 +236,8 @@ class OverlapPatchEmbed(nn.Module):
     """image (or the previous stage's map) -> token rows: a strided convolution with overlapping windows, then LayerNorm"""
     # 'hip': flatten / transpose + norm are one library call per direction, no transposed copy (see MixVisionTransformer.norm_impl)
     norm_impl = 'torch'
+    # 'hip': convolution + flatten / transpose + norm are one library call per direction (see MixVisionTransformer.conv_impl)
+    conv_impl = 'torch'
 
     def __init__(self, img_size=224, patch_size=7, stride=4, in_chans=3, embed_dim=768):
         super().__init__()
@@ -242,7 +249,25 @@ class OverlapPatchEmbed(nn.Module):
         self.norm = nn.LayerNorm(embed_dim)
         self.apply(_init_weights)
 
+    def _conv_fused(self, x):
+        """whether this input takes the library's embedding (conv_impl = 'hip'): fp32 tensors on the GPU (or under the emulator override), a
+        convolution inside the kernel's limits, a plain affine nn.LayerNorm, parameters where the kernels can read them, and no input
+        gradient through a 7 x 7 convolution.  Anything else: the stock line."""
+        proj, norm = self.proj, self.norm
+        if self.conv_impl != 'hip' or not (x.is_cuda or _lib._override is not None) or x.dtype != torch.float32:
+            return False
+        if not patch_embed_supported(proj, x.shape) or type(norm) is not nn.LayerNorm or not norm.elementwise_affine or norm.bias is None:
+            return False
+        if tuple(norm.normalized_shape) != (proj.out_channels,):
+            return False
+        ts = (proj.weight, proj.bias, norm.weight, norm.bias)
+        if any(t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous() or t.data_ptr() % 16 for t in ts):
+            return False
+        return not (proj.kernel_size[0] == 7 and x.requires_grad and torch.is_grad_enabled())
+
     def forward(self, x):
+        if self._conv_fused(x):
+            return overlap_patch_embed(x, self.proj, self.norm)
         x = self.proj(x)
         H, W = x.shape[2:]
         if _norm_fused(self.norm_impl, self.norm, x, x.shape[1]):
@@ -266,6 +291,11 @@ class MixVisionTransformer(nn.Module):
     # F.layer_norm -- the default (DESIGN section 3v has the measurements).  The owners of the call sites carry an attribute of the same
     # name; set_norm_impl sets them all.
     norm_impl = 'torch'
+    # 'hip': on the modules' own path each OverlapPatchEmbed -- convolution, flatten / transpose, LayerNorm -- is one library call per
+    # direction (ops.overlap_patch_embed): fp32 GPU tensors, a convolution inside the kernel's limits; anything else, and a 7 x 7
+    # embedding whose input requires grad, takes the stock line, silently.  'torch': stock Conv2d -- the default (DESIGN section 3w has
+    # the measurements).  The inference paths (stage_impl, embed_impl) are not touched and win where they apply.
+    conv_impl = 'torch'
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dims=[64, 128, 256, 512], num_heads=[1, 2, 4, 8],
                  mlp_ratios=[4, 4, 4, 4], qkv_bias=False, qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.,
@@ -320,6 +350,14 @@ class MixVisionTransformer(nn.Module):
         for m in self.modules():
             if hasattr(type(m), 'norm_impl'):
                 m.norm_impl = impl
+
+    def set_conv_impl(self, impl):
+        """conv_impl of the model and of every patch embedding"""
+        if impl not in ('torch', 'hip'):
+            raise ValueError("conv_impl must be 'torch' or 'hip', got %r" % (impl,))
+        for m in self.modules():
+            if hasattr(type(m), 'conv_impl'):
+                m.conv_impl = impl
 
     def freeze_patch_emb(self):
         self.patch_embed1.requires_grad = False      # (as in the reference: an attribute on the module, the parameters keep theirs)

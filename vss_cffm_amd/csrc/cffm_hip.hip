@@ -3191,12 +3191,12 @@ static int pemb_ncw(int Cout, int nt) {
     return nt == 1 && nc % 8 == 0 ? 8 : nc % 5 == 0 ? 5 : nc % 4 == 0 ? 4 : nc % 2 == 0 ? 2 : 1;
 }
 // tiles per workgroup of 8 waves (pembed_kernels.h): Cout <= 64: 8 tiles, a wave each | Cout <= 128: 4 tiles, two waves each | wider: one
-// tile, its K split over the 8 waves
-template <int KS, int ST, int NT, int WAVES>
-static void pemb_go_nt(hipStream_t st, const float* x, const float* w, const float* b, const float* gamma, const float* beta, float* out,
+// tile, its K split over the 8 waves.  TRAIN: the instantiation that also stores the pre-LayerNorm rows z
+template <int KS, int ST, int NT, int WAVES, bool TRAIN>
+static void pemb_go_nt(hipStream_t st, const float* x, const float* w, const float* b, const float* gamma, const float* beta, float* out, float* z,
                        const PembGeom& G, float eps) {
     const unsigned grid = (unsigned)(((long)G.B * G.Ho * G.tpr + NT - 1) / NT);
-#define PEMB_FWD(NCW_) CFFM_LAUNCH((k_pembed_fwd<KS, ST, NCW_, NT, WAVES>), (grid), (WAVES * 64), 0, st, x, w, b, gamma, beta, out, G, eps)
+#define PEMB_FWD(NCW_) CFFM_LAUNCH((k_pembed_fwd<KS, ST, NCW_, NT, WAVES, TRAIN>), (grid), (WAVES * 64), 0, st, x, w, b, gamma, beta, out, z, G, eps)
     switch (pemb_ncw(G.Cout, NT)) {
         case 8: if constexpr (NT == 1) PEMB_FWD(8); break;       // (Cout = 512 at stage 4: 218 us against 275 with NCW = 4)
         case 5: PEMB_FWD(5); break;
@@ -3206,18 +3206,67 @@ static void pemb_go_nt(hipStream_t st, const float* x, const float* w, const flo
     }
 #undef PEMB_FWD
 }
-template <int KS, int ST>
-static void pemb_go(hipStream_t st, const float* x, const float* w, const float* b, const float* gamma, const float* beta, float* out,
+template <int KS, int ST, bool TRAIN>
+static void pemb_go(hipStream_t st, const float* x, const float* w, const float* b, const float* gamma, const float* beta, float* out, float* z,
                     const PembGeom& G, float eps) {
-    if (G.Cout <= 64) pemb_go_nt<KS, ST, 8, 8>(st, x, w, b, gamma, beta, out, G, eps);
-    else if (G.Cout <= 128) pemb_go_nt<KS, ST, 4, 8>(st, x, w, b, gamma, beta, out, G, eps);
-    else pemb_go_nt<KS, ST, 1, 8>(st, x, w, b, gamma, beta, out, G, eps);
+    if (G.Cout <= 64) pemb_go_nt<KS, ST, 8, 8, TRAIN>(st, x, w, b, gamma, beta, out, z, G, eps);
+    else if (G.Cout <= 128) pemb_go_nt<KS, ST, 4, 8, TRAIN>(st, x, w, b, gamma, beta, out, z, G, eps);
+    else pemb_go_nt<KS, ST, 1, 8, TRAIN>(st, x, w, b, gamma, beta, out, z, G, eps);
 }
 // (checked arguments -> the launch: shared with cffm_mit_infer)
 static void pemb_launch(int k, hipStream_t st, const float* x, const float* w, const float* b, const float* gamma, const float* beta, float* out,
                         const PembGeom& G, float eps) {
-    if (k == 7) pemb_go<7, 4>(st, x, w, b, gamma, beta, out, G, eps);
-    else pemb_go<3, 2>(st, x, w, b, gamma, beta, out, G, eps);
+    if (k == 7) pemb_go<7, 4, false>(st, x, w, b, gamma, beta, out, nullptr, G, eps);
+    else pemb_go<3, 2, false>(st, x, w, b, gamma, beta, out, nullptr, G, eps);
+}
+// workspace of cffm_patch_embed_bwd (floats; every carve 256-byte aligned): dz [M][Cout] | the LayerNorm backward's records | the dw slabs
+// [nslab][Cout][KP] | the db records [ndb][Cout] | with dx: the transposed weight [9][Cin][Cout].
+// The M split of k_pembed_dw: its grid has ncb * nkb workgroups per slab (64 x 64 output tiles); nslab = ceil(PEMB_DW_WG_TARGET / (ncb * nkb)),
+// at most PEMB_DW_SLAB_CAP and at most one slab per PEMB_DW_ROWS rows; a slab is RS = ceil(M / nslab) rows and the count is then ceil(M / RS).
+struct PembBwdWs { long dz, rec, slab, dbrec, wt, total; int M, nslab, RS, KP, ncb, nkb, ndb, RB; };
+static PembBwdWs pemb_bwd_layout(const PembGeom& G, int with_dx) {
+    PembBwdWs W;
+    W.M = G.B * G.Ho * G.Wo;
+    W.KP = (G.K + 15) / 16 * 16;
+    W.ncb = (G.Cout + 63) / 64;
+    W.nkb = (W.KP + 63) / 64;
+    const int blocks = W.ncb * W.nkb, steps = (W.M + PEMB_DW_ROWS - 1) / PEMB_DW_ROWS;
+    int n = (PEMB_DW_WG_TARGET + blocks - 1) / blocks;
+    n = std::max(1, std::min(n, std::min(PEMB_DW_SLAB_CAP, steps)));
+    W.RS = (W.M + n - 1) / n;
+    W.nslab = (W.M + W.RS - 1) / W.RS;
+    const int nb = std::max(1, std::min(PEMB_DB_CAP, (W.M + 63) / 64));
+    W.RB = (W.M + nb - 1) / nb;
+    W.ndb = (W.M + W.RB - 1) / W.RB;
+    long p = 0;
+    W.dz = p; p += up((long)W.M * G.Cout);
+    W.rec = p; p += up(mln_bwd_records(W.M, G.Cout, 1) * 2 * G.Cout);
+    W.slab = p; p += up((long)W.nslab * G.Cout * W.KP);
+    W.dbrec = p; p += up((long)W.ndb * G.Cout);
+    W.wt = p; p += with_dx ? up(9L * G.Cin * G.Cout) : 0;
+    W.total = p;
+    return W;
+}
+template <int KS, int ST>
+static void pemb_dw_go(hipStream_t st, const float* x, const float* dz, float* slab, const PembGeom& G, const PembBwdWs& W) {
+    CFFM_LAUNCH((k_pembed_dw<KS, ST>), ((unsigned)W.nslab, (unsigned)W.ncb, (unsigned)W.nkb), (256), 0, st, x, dz, slab, G, W.RS, W.KP);
+}
+// (checked arguments -> the launches, all on st, one after the other)
+static void pemb_bwd_launch(int k, hipStream_t st, const float* x, const float* w, const float* gamma, const float* z, const float* dout, float* dx,
+                            float* dw, float* db, float* dgamma, float* dbeta, float* ws, const PembGeom& G, float eps) {
+    const PembBwdWs W = pemb_bwd_layout(G, dx != nullptr);
+    float* dz = ws + W.dz;
+    mln_bwd_launch(0, st, z, gamma, dout, dz, dgamma, dbeta, ws + W.rec, W.M, 0, G.Cout, 1, eps);
+    if (k == 7) pemb_dw_go<7, 4>(st, x, dz, ws + W.slab, G, W);
+    else pemb_dw_go<3, 2>(st, x, dz, ws + W.slab, G, W);
+    CFFM_LAUNCH(k_pembed_db, ((unsigned)W.ndb), (256), 0, st, (const float*)dz, ws + W.dbrec, W.M, G.Cout, W.RB);
+    const long chunks = (long)G.Cout * W.KP / 4 + G.Cout / 4;
+    CFFM_LAUNCH(k_pembed_dw_final, ((unsigned)((chunks + 255) / 256)), (256), 0, st, (const float*)(ws + W.slab), (const float*)(ws + W.dbrec), dw, db,
+                W.nslab, W.ndb, G.Cout, G.K, W.KP);
+    if (dx) {
+        CFFM_LAUNCH(k_pembed_wt, ((unsigned)((9L * G.Cin * G.Cout + 255) / 256)), (256), 0, st, w, ws + W.wt, G.Cin, G.Cout);
+        CFFM_LAUNCH(k_pembed_dx, ((unsigned)((long)G.B * G.H * ((G.W + 31) / 32))), (256), 0, st, (const float*)dz, (const float*)(ws + W.wt), dx, G);
+    }
 }
 // n consecutive stages: every limit of both parts, the chain of shapes, and the workspace (the maximum over the stages: they run one
 // after another).  W / PG (host [n]) may be null.
@@ -3335,6 +3384,41 @@ int cffm_patch_embed_fwd(const float* x_nchw, const float* w, const float* b, co
     REQUIRE((const float*)out_rows != x_nchw, "patch_embed_fwd: input and output must not alias");
     pemb_launch(k, (hipStream_t)stream, x_nchw, w, b, gamma, beta, out_rows, G, eps);
     CHECK_LAUNCH("patch_embed_fwd");
+    return 0;
+}
+
+int cffm_patch_embed_fwd_train(const float* x_nchw, const float* w, const float* b, const float* gamma, const float* beta, float* out_rows,
+                               float* z_rows, int B, int Cin, int H, int W, int Cout, int k, int stride, float eps, void* stream) {
+    PembGeom G;
+    TRY(pemb_check("patch_embed_fwd_train", B, Cin, H, W, Cout, k, stride, eps, &G));
+    REQUIRE(aligned16(x_nchw) && aligned16(w) && aligned16(b) && aligned16(gamma) && aligned16(beta) && aligned16(out_rows) && aligned16(z_rows),
+            "patch_embed_fwd_train: x_nchw / w / b / gamma / beta / out_rows / z_rows must be non-null and 16-byte aligned");
+    REQUIRE((const float*)out_rows != x_nchw && (const float*)z_rows != x_nchw && out_rows != z_rows,
+            "patch_embed_fwd_train: input and outputs must not alias");
+    hipStream_t st = (hipStream_t)stream;
+    if (k == 7) pemb_go<7, 4, true>(st, x_nchw, w, b, gamma, beta, out_rows, z_rows, G, eps);
+    else pemb_go<3, 2, true>(st, x_nchw, w, b, gamma, beta, out_rows, z_rows, G, eps);
+    CHECK_LAUNCH("patch_embed_fwd_train");
+    return 0;
+}
+long cffm_patch_embed_bwd_workspace_bytes(int B, int Cin, int H, int W, int Cout, int k, int stride, int with_dx) {
+    PembGeom G;
+    if (pemb_check("patch_embed_bwd_workspace_bytes", B, Cin, H, W, Cout, k, stride, 0.f, &G)) return -1;
+    if (with_dx && k != 3) return fail(-1, "patch_embed_bwd_workspace_bytes: the input gradient exists for (k, stride) = (3, 2) only");
+    return pemb_bwd_layout(G, with_dx != 0).total * (long)sizeof(float);
+}
+int cffm_patch_embed_bwd(const float* x_nchw, const float* w, const float* gamma, const float* z_rows, const float* dout_rows, float* dx_nchw,
+                         float* dw, float* db, float* dgamma, float* dbeta, void* workspace, int B, int Cin, int H, int W, int Cout, int k,
+                         int stride, float eps, void* stream) {
+    PembGeom G;
+    TRY(pemb_check("patch_embed_bwd", B, Cin, H, W, Cout, k, stride, eps, &G));
+    REQUIRE(!dx_nchw || k == 3, "patch_embed_bwd: the input gradient exists for (k, stride) = (3, 2) only: pass dx_nchw = NULL");
+    REQUIRE(aligned16(x_nchw) && aligned16(w) && aligned16(gamma) && aligned16(z_rows) && aligned16(dout_rows) && aligned16(dw) && aligned16(db) &&
+            aligned16(dgamma) && aligned16(dbeta) && aligned16(workspace) && (uintptr_t)dx_nchw % 16 == 0,
+            "patch_embed_bwd: x_nchw / w / gamma / z_rows / dout_rows / dw / db / dgamma / dbeta / workspace must be non-null and 16-byte "
+            "aligned, dx_nchw 16-byte aligned or null");
+    pemb_bwd_launch(k, (hipStream_t)stream, x_nchw, w, gamma, z_rows, dout_rows, dx_nchw, dw, db, dgamma, dbeta, (float*)workspace, G, eps);
+    CHECK_LAUNCH("patch_embed_bwd");
     return 0;
 }
 

@@ -1798,7 +1798,7 @@ def patch_embed_supported(proj, shape):
     return b * cin * h * w < 2 ** 31 and b * ho * wo * cout < 2 ** 31
 
 
-def _pemb_operands(what, x, proj, norm):
+def _pemb_operands(what, x, proj, norm, infer_only=True):
     if not isinstance(x, torch.Tensor) or x.dim() != 4:
         raise _lib.CffmError('%s: x must be a [B,Cin,H,W] tensor' % what)
     if type(proj) is not torch.nn.Conv2d or proj.bias is None or norm.weight is None or norm.bias is None:
@@ -1808,13 +1808,14 @@ def _pemb_operands(what, x, proj, norm):
         _require_device(t, what)
         if t.device != x.device:
             raise _lib.CffmError('%s: every tensor must be on %s' % (what, x.device))
-    _infer_only(ts, what)
+    if infer_only:
+        _infer_only(ts, what)
     if (tuple(proj.kernel_size) != (proj.kernel_size[0],) * 2 or tuple(proj.stride) != (proj.stride[0],) * 2 or tuple(proj.dilation) != (1, 1)
             or proj.groups != 1 or proj.padding != (proj.kernel_size[0] // 2,) * 2 or proj.padding_mode != 'zeros'
             or proj.in_channels != x.shape[1] or tuple(norm.normalized_shape) != (proj.out_channels,)):
         raise _lib.CffmError('%s: a square Conv2d(Cin, Cout, k, stride, padding=k // 2) without dilation or groups, on x [B,Cin,H,W], and '
                              'LayerNorm(Cout) expected' % what)
-    return tuple(_sra_operand(t.detach()) for t in ts)
+    return tuple(_sra_operand(t.detach()) for t in ts) if infer_only else ts
 
 
 def patch_embed(x, proj, norm, out=None):
@@ -1832,6 +1833,68 @@ def patch_embed(x, proj, norm, out=None):
     _lib.check(lib.cffm_patch_embed_fwd(_ptr(xs), _ptr(w), _ptr(b), _ptr(g), _ptr(beta), _ptr(out), bsz, cin, h, wd, cout,
                                         int(proj.kernel_size[0]), int(proj.stride[0]), float(norm.eps), _stream(xs)), lib)
     return out, ho, wo
+
+
+class _PatchEmbedFn(torch.autograd.Function):
+    """``patch_embed`` with its backward (csrc/pembed_kernels.h).  The forward is the inference kernel's instantiation that also stores z, the
+    pre-LayerNorm rows; saved: x, the weight, gamma and z -- mean and rstd are recomputed in the backward, whose workspace (dz, the LayerNorm
+    records, the dw slabs, the transposed weight) lives only inside it."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, k, stride, eps):
+        lib = _lib.get()
+        # every input contiguous BEFORE the stream is looked up or anything is enqueued (as _LayerNormFn.forward)
+        x, weight, bias, gamma, beta = (_sra_operand(t) for t in (x, weight, bias, gamma, beta))
+        bsz, cin, h, w = x.shape
+        cout = weight.shape[0]
+        ho, wo = ((v + 2 * (k // 2) - k) // stride + 1 for v in (h, w))
+        out = torch.empty((bsz, max(ho, 0) * max(wo, 0), cout), dtype=torch.float32, device=x.device)
+        z = torch.empty_like(out)
+        _lib.check(lib.cffm_patch_embed_fwd_train(_ptr(x), _ptr(weight), _ptr(bias), _ptr(gamma), _ptr(beta), _ptr(out), _ptr(z), bsz, cin, h, w,
+                                                  cout, k, stride, eps, _stream(x)), lib)
+        ctx.save_for_backward(x, weight, gamma, z)
+        ctx.conv = (k, stride, eps)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        lib = _lib.get()
+        x, weight, gamma, z = ctx.saved_tensors
+        k, stride, eps = ctx.conv
+        dout = _sra_operand(dout)
+        bsz, cin, h, w = x.shape
+        cout = weight.shape[0]
+        want_dx = bool(ctx.needs_input_grad[0])
+        dx = torch.empty_like(x) if want_dx else None
+        dw = torch.empty_like(weight)
+        db, dgamma, dbeta = (torch.empty(cout, dtype=torch.float32, device=x.device) for _ in range(3))
+        nbytes = lib.cffm_patch_embed_bwd_workspace_bytes(bsz, cin, h, w, cout, k, stride, int(want_dx))
+        if nbytes < 0:
+            raise _lib.CffmError('libcffm_hip: %s' % lib.cffm_last_error().decode())
+        ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
+        _lib.check(lib.cffm_patch_embed_bwd(_ptr(x), _ptr(weight), _ptr(gamma), _ptr(z), _ptr(dout), _ptr(dx), _ptr(dw), _ptr(db), _ptr(dgamma),
+                                            _ptr(dbeta), _ptr(ws), bsz, cin, h, w, cout, k, stride, eps, _stream(x)), lib)
+        return dx, dw, db, dgamma, dbeta, None, None, None
+
+
+def overlap_patch_embed(x, proj, norm):
+    """``patch_embed`` with a backward: norm(proj(x).flatten(2).transpose(1, 2)) of an fp32 map x [B,Cin,H,W] -> (token rows [B, Ho*Wo, Cout],
+    Ho, Wo), differentiable in x ((k, stride) = (3, 2) only), proj.weight, proj.bias, norm.weight and norm.bias (``cffm_patch_embed_fwd_train``
+    / ``cffm_patch_embed_bwd``; every gradient bit-reproducible).  The rows have the bits of ``patch_embed``; x, the weight, norm.weight and
+    the pre-LayerNorm rows are all that is saved.  Under no_grad, or with nothing that requires grad, it IS ``patch_embed``.  A 7 x 7
+    embedding whose x requires grad raises: that input gradient is not built.  Launches on the current stream."""
+    what = 'overlap_patch_embed'
+    ts = _pemb_operands(what, x, proj, norm, infer_only=False)
+    if not (torch.is_grad_enabled() and any(t.requires_grad for t in ts)):
+        return patch_embed(x, proj, norm)
+    k, stride = int(proj.kernel_size[0]), int(proj.stride[0])
+    if (k, stride) not in PEMB_KERNELS:
+        raise _lib.CffmError('%s: (k, stride) = (%d, %d) is neither (7, 4) nor (3, 2)' % (what, k, stride))
+    if k != 3 and x.requires_grad:
+        raise _lib.CffmError('%s: the input gradient exists for (k, stride) = (3, 2) only; x must not require grad' % what)
+    ho, wo = patch_embed_out_hw(proj, x.shape[2], x.shape[3])
+    return _PatchEmbedFn.apply(x, proj.weight, proj.bias, norm.weight, norm.bias, k, stride, float(norm.eps)), ho, wo
 
 
 def mit_stages(shape, stages):
