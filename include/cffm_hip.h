@@ -233,6 +233,30 @@ typedef struct cffm_cffa_bwd_block {
 } cffm_cffa_bwd_block;
 int cffm_ln_pool_bwd(const cffm_geom* g, int n, const cffm_cffa_bwd_block* blocks /* host [n] */, const float* x_ref, long ref_bs,
                      float* dx_ref, long dref_bs, int accum_ref, void* stream);
+/* added under ABI 13, additive: the end of a range of block backwards as stages.
+ *
+ * A record set: `count` records `stride` floats apart (rec 16-byte aligned, stride a multiple of 4 and >= total rounded up to 4); column c
+ * < total of the records is summed in a fixed order and written to (accumulate[k] != 0: added to) out[k][c - off[k]] of every segment k with
+ * off[k] <= c < off[k] + width[k] (nseg <= 8).
+ * cffm_reduce_records: up to 10 record sets in one launch (the second stage of every block-partial reduction).
+ * cffm_pool_matrix_bwd: dM [15*49] of n = 1..4 blocks -> their pooling-weight gradients dpool_w (49 / 49 / 9 / 4 floats; dpool_b is not
+ * written, but with cffm_grad_slices_padded(1) the 3 floats behind the first three weights and behind each dpool_b are zeroed).
+ * cffm_bwd_tail: ONE launch of workgroups that do not depend on each other -- the sums of the record sets and the tiles of
+ * dst[z][c][r] = src[z][r][c] (+ addend[z][c][r] unless z % add_mod == add_skip; tr or tr->addend may be NULL).  The bits are those of
+ * cffm_reduce_records and of cffm_transpose (+ one fp32 addition). */
+typedef struct cffm_record_set {
+    const float* rec; int count, stride, total;
+    int nseg, off[8], width[8], accumulate[8];
+    float* out[8];
+} cffm_record_set;
+typedef struct cffm_pool_grads { const float* dM; float *dpool_w[4], *dpool_b[4]; } cffm_pool_grads;
+typedef struct cffm_tail_transpose {
+    const float* src; float* dst; int batch, rows, cols; long src_bs, dst_bs;
+    const float* addend; int add_mod, add_skip;
+} cffm_tail_transpose;
+int cffm_reduce_records(int nsets, const cffm_record_set* sets /* host [nsets] */, void* stream);
+int cffm_pool_matrix_bwd(int n, const cffm_pool_grads* blocks /* host [n] */, void* stream);
+int cffm_bwd_tail(int nsets, const cffm_record_set* sets /* host [nsets] */, const cffm_tail_transpose* tr, void* stream);
 /* the q|k|v input gradient: dx [M,256] = dqkv [M,768] w, dqkv fp32, w in fragment order (cffm_panel_pack_weight of w [768,256], form 1);
  * db (or NULL) [768] = the column sums of dqkv (qkv.bias.grad: records out of the same launch, then one reduction); dqkv_t (or NULL): also
  * writes the T-frag copy of dqkv (cffm_tfrag_floats(M, 768) floats, rows past M zero).  Nothing past row M of dqkv is read. */

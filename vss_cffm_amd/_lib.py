@@ -37,6 +37,23 @@ class CffaBwdBlock(C.Structure):
                 + [('dx_tgt', vp), ('dtgt_bs', cl), ('dgamma', vp), ('dbeta', vp), ('dpool_w', vp * 4), ('dpool_b', vp * 4)])
 
 
+class RecordSet(C.Structure):
+    """cffm_record_set"""
+    _fields_ = [('rec', vp), ('count', ci), ('stride', ci), ('total', ci), ('nseg', ci), ('off', ci * 8), ('width', ci * 8),
+                ('accumulate', ci * 8), ('out', vp * 8)]
+
+
+class PoolGrads(C.Structure):
+    """cffm_pool_grads"""
+    _fields_ = [('dM', vp), ('dpool_w', vp * 4), ('dpool_b', vp * 4)]
+
+
+class TailTranspose(C.Structure):
+    """cffm_tail_transpose"""
+    _fields_ = [('src', vp), ('dst', vp), ('batch', ci), ('rows', ci), ('cols', ci), ('src_bs', cl), ('dst_bs', cl), ('addend', vp),
+                ('add_mod', ci), ('add_skip', ci)]
+
+
 class GtcPtrs(C.Structure):
     """cffm_gtc_params / cffm_gtc_grads (same field order)."""
     _fields_ = [(n, vp) for n in ('norm1_w', 'norm1_b', 'qkv_w', 'qkv_b', 'kv_w', 'kv_b', 'proj_w', 'proj_b', 'norm2_w', 'norm2_b',
@@ -115,6 +132,9 @@ SIGNATURES = {
     'cffm_panel_pack_weight': (ci, [vp, ci, ci, ci, vp, vp]),
     'cffm_panel_qkv_fwd': (ci, [vp, vp, vp, vp, cl, vp, vp]),
     'cffm_ln_pool_bwd': (ci, [GP, ci, CBP, vp, cl, vp, cl, ci, vp]),
+    'cffm_reduce_records': (ci, [ci, C.POINTER(RecordSet), vp]),
+    'cffm_pool_matrix_bwd': (ci, [ci, C.POINTER(PoolGrads), vp]),
+    'cffm_bwd_tail': (ci, [ci, C.POINTER(RecordSet), C.POINTER(TailTranspose), vp]),
     'cffm_panel_qkv_bwd_input': (ci, [vp, vp, vp, vp, vp, cl, vp]),
     'cffm_bias_scatter': (ci, [vp, vp, vp, C.POINTER(vp), vp]),
     'cffm_mlp_fwd': (ci, [vp, vp, cl, ci] + [vp] * 15 + [cl, vp]),

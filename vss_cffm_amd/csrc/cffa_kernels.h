@@ -26,8 +26,8 @@
 __device__ __forceinline__ void transpose_body(const float* __restrict__ src, float* __restrict__ dst,
                                                int rows, int cols, long src_bs, long dst_bs,
                                                const float* __restrict__ addend, int add_mod, int add_skip,
-                                               float* __restrict__ copy_dst, int bx, int by, int bz) {
-    __shared__ float tile[64][65];   // tile[c][r]; odd stride: the scalar LDS accesses below are at most 2-way conflicted
+                                               float* __restrict__ copy_dst, int bx, int by, int bz, float (*tile)[65]) {
+    // tile[c][r] (64 rows of LDS, the caller's); odd stride: the scalar LDS accesses below are at most 2-way conflicted
     const int r0 = by * 64, c0 = bx * 64;
     const float* s = src + (long)bz * src_bs;
     float* d = dst + (long)bz * dst_bs;
@@ -70,7 +70,8 @@ __global__ void __launch_bounds__(256) k_transpose(const float* __restrict__ src
                                                     int rows, int cols, long src_bs, long dst_bs,
                                                     const float* __restrict__ addend, int add_mod, int add_skip,
                                                     float* __restrict__ copy_dst = nullptr) {
-    transpose_body(src, dst, rows, cols, src_bs, dst_bs, addend, add_mod, add_skip, copy_dst, blockIdx.x, blockIdx.y, blockIdx.z);
+    __shared__ float tile[64][65];
+    transpose_body(src, dst, rows, cols, src_bs, dst_bs, addend, add_mod, add_skip, copy_dst, blockIdx.x, blockIdx.y, blockIdx.z, tile);
 }
 
 // --------------------------------------------------------------------------- pooling matrix

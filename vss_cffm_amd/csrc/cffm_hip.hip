@@ -716,6 +716,21 @@ static void cffa_jobs(RedJobs& J, const float* rec, long rows, float* dgamma, fl
     for (int i = 1; i < 4; ++i) seg_add(c, 14 * CFFM_WA + i - 1, 1, dpool_b[i], 0);
     job_add(J, rec + rows * LNP_RSTRIDE + 2 * CFFM_C, (int)rows, LNP_RSTRIDE, LNP_TAIL_REF, c, st);
 }
+// The end of a range: the record reductions of J and the dx transpose's tiles (A.T.gx == 0: none) as ONE launch (k_bwd_tail,
+// rowops_kernels.h).  The forward's k_transpose_prep is the model: work that does not depend on each other shares a launch instead of a
+// side stream, which the graph executor would queue ahead of the weight-gradient groups.  The pooling-matrix backward reads the dM the
+// reductions write, so it stays a launch of its own behind this one.
+static void tail_transpose(TailArgs& A, const float* src, float* dst, int batch, int rows, int cols, long src_bs, long dst_bs, const float* addend,
+                           int add_mod, int add_skip) {
+    A.T = {src, dst, rows, cols, src_bs, dst_bs, add_mod > 0 ? add_mod : 1, add_skip, nullptr, (cols + 63) / 64, (rows + 63) / 64, batch};
+    A.addend = addend;
+}
+static void bwd_tail_launch(TailArgs& A, RedJobs& J, hipStream_t st) {
+    for (int j = 0; j < J.njob; ++j) A.red_end[j] = (j ? A.red_end[j - 1] : 0) + (J.total[j] + 31) / 32;
+    const long grid = (long)A.T.gx * A.T.gy * A.T.gz + (J.njob ? A.red_end[J.njob - 1] : 0);
+    if (grid > 0) CFFM_LAUNCH(k_bwd_tail, ((unsigned)grid), (256), 0, st, A, J);
+    J.njob = 0;
+}
 
 // Library-owned state of the CFFA backward, one SLOT per block of the layer: the block's token-row gradient dzall (written by the q|k|v
 // input-gradient GEMM, its pooled-cell rows are read again by the reference pass at the end of the range), the records of its target
@@ -745,16 +760,20 @@ struct CffaBlk {
 // records of every block are written by now (ln_pool_bwd_tgt).
 // `extra` (or NULL): record reductions of the caller that are due at this point of the stream anyway (the last block's parameter-gradient
 // tail): they join the final reduction launch instead of taking one of their own.
+// `tail` (or NULL): the caller's dx transpose (tail_transpose), which rides in the same launch.
 static int cffa_finish_blocks(const cffm_geom* g, const CffaBlk* blk, int count, const float* x_ref, long ref_bs, float* dx_ref, long dref_bs,
-                              int accum, void* stream, RedJobs* extra = nullptr) {
+                              int accum, void* stream, RedJobs* extra = nullptr, const TailArgs* tail = nullptr) {
     hipStream_t st = (hipStream_t)stream;
     const long rows = cffa_rows(g);
     static_assert(PMB_MAXD == RB_MAXD, "one pooling-matrix launch per reference launch");
     for (int k0 = 0; k0 < count; k0 += RB_MAXD) {
         const int n = count - k0 < RB_MAXD ? count - k0 : RB_MAXD;
+        const bool last = k0 + RB_MAXD >= count;     // the last round's reductions share a launch with the caller's transpose: k_bwd_tail
         CffaRefBlocks Bk;
         PoolWGN pw;
         RedJobs J;
+        TailArgs A;
+        if (tail) A = *tail; else A.T.gx = A.T.gy = A.T.gz = 0;
         Bk.n = n; J.njob = 0;
         for (int d = 0; d < RB_MAXD; ++d) {
             const CffaBlk& b = blk[k0 + (d < n ? d : 0)];
@@ -769,11 +788,12 @@ static int cffa_finish_blocks(const cffm_geom* g, const CffaBlk* blk, int count,
             const CffaBlk& b = blk[k0 + d];
             cffa_jobs(J, b.rec, rows, b.dgamma, b.dbeta, b.dM, b.dpool_b, st);
         }
-        if (extra && k0 + RB_MAXD >= count) {        // (the last launch)
+        if (last && extra) {
             for (int j = 0; j < extra->njob; ++j) job_add(J, extra->part[j], extra->nblk[j], extra->stride[j], extra->total[j], extra->segs[j], st);
             extra->njob = 0;
         }
-        redq_launch(J, st);
+        if (last) bwd_tail_launch(A, J, st);
+        else redq_launch(J, st);
         CHECK_LAUNCH("cffa reductions");
         {
             PROF(ST_POOLMAT);
@@ -787,7 +807,7 @@ static int cffa_finish_blocks(const cffm_geom* g, const CffaBlk* blk, int count,
 // at params[i] / grads[i], its workspace at ws0 + i * ws_stride, its token-row gradient, records and pooling-matrix gradient in slot i).
 static int cffa_finish(const cffm_geom* g, int nslots, const cffm_block_params* params, const cffm_block_grads* grads, int first, int last,
                        const float* ws0, long ws_stride, const float* x_ref, long ref_bs, float* dx_ref, long dref_bs, int accum, void* stream,
-                       RedJobs* extra = nullptr) {
+                       RedJobs* extra = nullptr, const TailArgs* tail = nullptr) {
     cffm_block_ws L;
     cffm_block_ws_layout(g, &L);
     const int count = first - last + 1;
@@ -803,7 +823,7 @@ static int cffa_finish(const cffm_geom* g, int nslots, const cffm_block_params* 
         blk[k] = {params[i].norm1_w, params[i].norm1_b, ws + L.M, ws + L.mean1, ws + L.rstd1, S.dzall, S.rec, S.dM,
                   grads[i].norm1_w, grads[i].norm1_b, grads[i].pool_w, grads[i].pool_b};
     }
-    return cffa_finish_blocks(g, blk, count, x_ref, ref_bs, dx_ref, dref_bs, accum, stream, extra);
+    return cffa_finish_blocks(g, blk, count, x_ref, ref_bs, dx_ref, dref_bs, accum, stream, extra, tail);
 }
 // The CFFA backward as a stage: the target frame of each block (as the block backward runs it), then the end of the range above
 int cffm_ln_pool_bwd(const cffm_geom* g, int n, const cffm_cffa_bwd_block* blocks, const float* x_ref, long ref_bs, float* dx_ref, long dref_bs,
@@ -825,6 +845,63 @@ int cffm_ln_pool_bwd(const cffm_geom* g, int n, const cffm_cffa_bwd_block* block
         blk[d] = {b.gamma, b.beta, b.M, b.mean, b.rstd, b.dzall, S.rec, S.dM, b.dgamma, b.dbeta, b.dpool_w, b.dpool_b};
     }
     return cffa_finish_blocks(g, blk, n, x_ref, ref_bs, dx_ref, dref_bs, accum_ref, stream);
+}
+
+// ---- the end of a range as stages: the one launch, and the launches it replaced -------------------------------------------------------
+static int record_sets(RedJobs& J, int nsets, const cffm_record_set* sets, const char* who) {
+    REQUIRE(nsets >= 0 && nsets <= RED_MAXJOB && (sets || !nsets), "%s: %d record sets (0..%d per call)", who, nsets, RED_MAXJOB);
+    J.njob = 0;
+    for (int j = 0; j < nsets; ++j) {
+        const cffm_record_set& s = sets[j];
+        REQUIRE(aligned16(s.rec) && s.count >= 1 && s.total >= 1 && s.stride % 4 == 0 && s.stride >= (s.total + 3) / 4 * 4 && s.nseg >= 0 &&
+                    s.nseg <= RED_MAXSEG, "%s: bad record set %d", who, j);
+        RedSegs g;
+        g.nseg = 0;
+        for (int k = 0; k < s.nseg; ++k) {
+            REQUIRE(s.out[k] && s.off[k] >= 0 && s.width[k] >= 0 && s.off[k] + s.width[k] <= s.total, "%s: bad segment %d of record set %d", who, k, j);
+            seg_add(g, s.off[k], s.width[k], s.out[k], s.accumulate[k]);
+        }
+        const int i = J.njob++;
+        J.part[i] = s.rec; J.nblk[i] = s.count; J.stride[i] = s.stride; J.total[i] = s.total; J.segs[i] = g;
+        J.blk_end[i] = (i ? J.blk_end[i - 1] : 0) + (s.total + 63) / 64;
+    }
+    return 0;
+}
+int cffm_reduce_records(int nsets, const cffm_record_set* sets, void* stream) {
+    RedJobs J;
+    TRY(record_sets(J, nsets, sets, "reduce_records"));
+    redq_launch(J, (hipStream_t)stream);
+    CHECK_LAUNCH("reduce_records");
+    return 0;
+}
+int cffm_pool_matrix_bwd(int n, const cffm_pool_grads* blocks, void* stream) {
+    REQUIRE(n >= 1 && n <= PMB_MAXD && blocks, "pool_matrix_bwd: %d blocks (1..%d per call)", n, PMB_MAXD);
+    PoolWGN pw;
+    for (int d = 0; d < PMB_MAXD; ++d) {
+        const cffm_pool_grads& b = blocks[d < n ? d : 0];
+        REQUIRE(b.dM, "pool_matrix_bwd: null dM in block %d", d);
+        for (int q = 0; q < 4; ++q) {
+            REQUIRE(b.dpool_w[q] && b.dpool_b[q], "pool_matrix_bwd: null pointer in block %d", d);
+            pw.gw[d].w[q] = b.dpool_w[q]; pw.gw[d].b[q] = g_grad_pads ? b.dpool_b[q] : nullptr;
+        }
+        pw.dM[d] = b.dM;
+    }
+    CFFM_LAUNCH(k_pool_matrix_bwd_n, (111, n), (64), 0, (hipStream_t)stream, pw);
+    CHECK_LAUNCH("pool_matrix_bwd");
+    return 0;
+}
+int cffm_bwd_tail(int nsets, const cffm_record_set* sets, const cffm_tail_transpose* tr, void* stream) {
+    RedJobs J;
+    TailArgs A;
+    TRY(record_sets(J, nsets, sets, "bwd_tail"));
+    A.T.gx = A.T.gy = A.T.gz = 0;
+    if (tr) {
+        REQUIRE(tr->src && tr->dst && tr->batch > 0 && tr->rows > 0 && tr->cols > 0, "bwd_tail: bad transpose");
+        tail_transpose(A, tr->src, tr->dst, tr->batch, tr->rows, tr->cols, tr->src_bs, tr->dst_bs, tr->addend, tr->add_mod, tr->add_skip);
+    }
+    bwd_tail_launch(A, J, (hipStream_t)stream);
+    CHECK_LAUNCH("bwd_tail");
+    return 0;
 }
 
 int cffm_bias_assemble(const float* own, const float* ring, const float* const pool[4], float* bias, void* biasH, void* stream) {
@@ -2630,16 +2707,18 @@ static int layer_backward_impl(const cffm_geom* g, int depth, const cffm_block_p
     // walks the layer block by block (data-parallel training, BlockwiseReducer) gets a pass per block, accumulating into dx_ref, so
     // that every block's gradient slice is complete when its range returns.
     RedJobs* tail_jobs = nullptr;
-    if (last_block == 0 && g_tail.has) {     // the last block's record reductions ride in the CFFA's final reduction launch
+    if (last_block == 0 && g_tail.has) {     // the last block's record reductions ride in the end-of-range launch (k_bwd_tail)
         g_tail.has = false;
         tail_jobs = &g_tail.jobs;
     }
-    TRY(cffa_finish(g, depth, params, grads, first_block, last_block, blk0, L.total, xs, 4 * img, dxs, 4 * img, first_block != depth - 1, stream, tail_jobs));
-    // (dy_full: the upstream gradient of the whole [B,4,C,H,W] output -- its pass-through frames 0..2 join dx in the same pass)
-    // (so the last block's parameter-gradient tail stays on the caller's stream, in front of the output transpose: no fork behind the last
-    // ln_pool_bwd at all -- the transpose on a side stream of its own was queued AHEAD of the blocks' side work by the graph executor and
-    // held it up until the chain had finished: 0.95 ms per step)
-    if (last_block == 0) TRY(transpose_add(dxs, dx_nchw, g->B * 4, (int)HW, CFFM_C, img, img, dy_full, 4, 3, stream));
+    // The output transpose of a range that ends at block 0 (dy_full: the upstream gradient of the whole [B,4,C,H,W] output -- its
+    // pass-through frames 0..2 join dx in the same pass) shares the launch of the range's record reductions (k_bwd_tail): neither reads
+    // what the other writes, and no fork follows the last ln_pool_bwd -- the transpose on a side stream of its
+    // own was queued AHEAD of the blocks' side work by the graph executor and held it up until the chain had finished (0.95 ms per step).
+    TailArgs tr;
+    if (last_block == 0) tail_transpose(tr, dxs, dx_nchw, g->B * 4, (int)HW, CFFM_C, img, img, dy_full, 4, 3);
+    TRY(cffa_finish(g, depth, params, grads, first_block, last_block, blk0, L.total, xs, 4 * img, dxs, 4 * img, first_block != depth - 1, stream, tail_jobs,
+                    last_block == 0 ? &tr : nullptr));
     TRY(tail_flush((hipStream_t)stream));
     side_join_all((hipStream_t)stream);   // every parameter gradient of the range is complete behind this point of the stream
     return 0;

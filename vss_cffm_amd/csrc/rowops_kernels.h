@@ -129,11 +129,12 @@ __global__ void __launch_bounds__(256) k_param_prep(PrepArgs a) { param_prep_bod
 // although the prep had long finished.  1-D grid: the transpose's workgroups first, then pnx x (blocks) of the prep.
 struct TrArgs { const float* src; float* dst; int rows, cols; long src_bs, dst_bs; int add_mod, add_skip; float* copy_dst; int gx, gy, gz; };
 __global__ void __launch_bounds__(256) k_transpose_prep(TrArgs T, PrepArgs a, int pnx) {
+    __shared__ float tile[64][65];
     const int nt = T.gx * T.gy * T.gz;
     int b = blockIdx.x;
     if (b < nt) {
         transpose_body(T.src, T.dst, T.rows, T.cols, T.src_bs, T.dst_bs, nullptr, T.add_mod, T.add_skip, T.copy_dst, b % T.gx, (b / T.gx) % T.gy,
-                       b / (T.gx * T.gy));
+                       b / (T.gx * T.gy), tile);
         return;
     }
     b -= nt;
@@ -317,6 +318,79 @@ __global__ void __launch_bounds__(1024) k_reduce_records_multi(RedJobs J) {
         if (q + 1 < J.njob && blk >= J.blk_end[q]) j = q + 1;
     if (j > 0) blk -= J.blk_end[j - 1];
     reduce_records_body(J.part[j], J.nblk[j], J.stride[j], J.total[j], J.segs[j], blk, red);
+}
+
+// ---- the end of a range of block backwards: the record reductions and the dx transpose as ONE launch (k_bwd_tail) --------------------
+// Workgroups of 256 threads, by index range: the record reductions of RedJobs in 32-column slabs (about 170 latency-bound workgroups at
+// the workload's size: first, so that they are dispatched first), then the tiles of the dx transpose.  Neither reads what the other
+// writes: a launch has no order among its workgroups.  The whole grid is resident at once (<= 64 VGPRs, 16.6 KB of LDS: 8 workgroups
+// per CU, as k_transpose alone).
+//
+// A 32-column slab of one record set with 256 threads: a thread plays two of reduce_records_body's threads one after the other (8 lanes
+// x 4 columns, 64 slots = 512).  Every (slot, column) sum is built exactly as there -- records slot, slot + 64, ..: four accumulators over
+// whole groups of four, the remaining 1..3 records onto the first, (s0 + s1) + (s2 + s3), then the 64 slots in order -- so the bits are
+// those of k_reduce_records_multi.  red: [64][32].
+__device__ __forceinline__ void reduce_records_slab32(const float* __restrict__ part, int nblk, int stride, int total, const RedSegs& segs, int blk,
+                                                      float (*red)[32]) {
+#pragma unroll 1
+    for (int r = 0; r < 2; ++r) {
+        const int vt = threadIdx.x + 256 * r, slot = vt >> 3, c4 = blk * 32 + 4 * (vt & 7);
+        f32x4 s0 = (f32x4){0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
+        if (c4 < total && slot < nblk) {
+            const float* p = part + c4;
+            const int n = (nblk - slot + 63) >> 6;      // records of this slot
+            int b = slot;
+            for (int k = n >> 2; k > 0; --k, b += 256) {
+                const f32x4 v0 = *(const f32x4*)(p + (long)b * stride), v1 = *(const f32x4*)(p + (long)(b + 64) * stride);
+                const f32x4 v2 = *(const f32x4*)(p + (long)(b + 128) * stride), v3 = *(const f32x4*)(p + (long)(b + 192) * stride);
+                s0 += v0; s1 += v1; s2 += v2; s3 += v3;
+            }
+            const int rem = n & 3;                        // (requested together, added in order)
+            if (rem) {
+                const f32x4 v0 = *(const f32x4*)(p + (long)b * stride);
+                const f32x4 v1 = *(const f32x4*)(p + (long)(rem > 1 ? b + 64 : b) * stride);
+                const f32x4 v2 = *(const f32x4*)(p + (long)(rem > 2 ? b + 128 : b) * stride);
+                s0 += v0;
+                if (rem > 1) s0 += v1;
+                if (rem > 2) s0 += v2;
+            }
+        }
+        *(f32x4*)(&red[slot][4 * (vt & 7)]) = (s0 + s1) + (s2 + s3);
+    }
+    __syncthreads();
+    const int c = blk * 32 + threadIdx.x;
+    if (threadIdx.x < 32 && c < total) {
+        float v = 0.f;
+#pragma unroll 8
+        for (int k = 0; k < 64; ++k) v += red[k][threadIdx.x];
+        for (int k = 0; k < segs.nseg; ++k)
+            if (c >= segs.off[k] && c < segs.off[k] + segs.width[k]) {
+                float* o = segs.out[k] + (c - segs.off[k]);
+                *o = segs.accumulate[k] ? *o + v : v;
+            }
+    }
+}
+struct TailArgs {
+    TrArgs T;                 // T.gx == 0: no transpose (copy_dst unused)
+    const float* addend;
+    int red_end[RED_MAXJOB];  // exclusive prefix of the jobs' 32-column workgroups
+};
+__global__ void __launch_bounds__(256, 8) k_bwd_tail(TailArgs A, RedJobs J) {
+    __shared__ float lds[64 * 65];      // a transpose tile [64][65] or a reduction's [64][32]
+    int b = blockIdx.x;
+    const int nr = J.njob ? A.red_end[J.njob - 1] : 0;
+    if (b < nr) {
+        int j = 0;
+#pragma unroll
+        for (int q = 0; q < RED_MAXJOB - 1; ++q)
+            if (q + 1 < J.njob && b >= A.red_end[q]) j = q + 1;
+        if (j > 0) b -= A.red_end[j - 1];
+        reduce_records_slab32(J.part[j], J.nblk[j], J.stride[j], J.total[j], J.segs[j], b, (float (*)[32])lds);
+        return;
+    }
+    b -= nr;
+    transpose_body(A.T.src, A.T.dst, A.T.rows, A.T.cols, A.T.src_bs, A.T.dst_bs, A.addend, A.T.add_mod, A.T.add_skip, nullptr, b % A.T.gx,
+                   (b / A.T.gx) % A.T.gy, b / (A.T.gx * A.T.gy), (float (*)[65])lds);
 }
 
 // --------------------------------------------------------------------------- column sums (Linear bias grads)
