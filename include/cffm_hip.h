@@ -146,6 +146,12 @@ int cffm_attn_bwd(const cffm_geom* g, const void* qkv16, const int* key_src, con
                   const int* inv_ptr, const int* inv_idx, const void* biasH, const float* ao,
                   const float* dao, const float* lse, float* dqkv /*[B*RC,768] fp32: d(zall w^T), overwritten*/,
                   float* dbiasT /*[8,304,64], overwritten*/, float* dkv_part, void* stream);
+/* the last pass of cffm_attn_bwd as a stage (additive under ABI 13): dqkv[b][row][256..767] = the sum, over the (window, slot) pairs
+ * inv_idx lists for `row`, of the f16 partial rows of dkv_part times their (window, head) scale.  Per element: the readers in inv_idx
+ * order, whole batches of four as ((x0 s0 + x1 s1) + (x2 s2 + x3 s3)) added one batch after the other, then the remaining one to three
+ * singly.  Rows >= 49 nW (pooled) also get their q third [0..255] zeroed; the q third of the target rows is left as it is.  Partial
+ * rows no reader names are never read. */
+int cffm_dkv_gather(const cffm_geom* g, const int* inv_ptr, const int* inv_idx, const float* dkv_part, float* dqkv, void* stream);
 /* y[M,N] = x[M,K] w[N,K]^T ;  dx[M,K] = dy[M,N] w[N,K] ;  dw[N,K] = dy[M,N]^T x[M,K]   (row-major, no bias) */
 int cffm_linear_fwd(const float* x, const float* w, float* y, long M, int N, int K, void* stream);
 /* y[M,N] = x[M,K] w[N,K]^T + b[N]   (a 1x1 convolution on channels-last token rows: the head's classifiers, cffm_head.py:121,147) */
@@ -525,6 +531,7 @@ typedef struct {
 /* active_rows (device, [nrows] ints, or NULL = every row): only rows that own a chunk of this call advance their step count.
  * ticket (device int[CFFM_ADAMW_TICKETS], zero before the first call, or NULL): with tickets the step count is advanced INSIDE the update
  * launch (one kernel; the workgroup that finishes last stores the new state) -- same results as the two-launch form used without.
+ * The one-launch kernel keeps every row's factors in LDS: with more than 64 rows the call takes the two launches, tickets or not.
  * sched is read by the device when the launch runs: it may be device memory or pinned, device-visible host memory. */
 int cffm_adamw_step_rows(const cffm_adamw_chunk2* chunks /* device */, int nchunks, const float* grad_base, float* state,
                          const float* sched, double* consts, int nrows, const int* active_rows, int* ticket, void* stream);

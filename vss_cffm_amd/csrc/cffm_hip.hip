@@ -973,9 +973,15 @@ static int attn_bwd_bias_sum(const float* dbp, int ng, float* dbiasT, void* stre
 }
 static int attn_bwd_gather(const cffm_geom* g, const int* inv_ptr, const int* inv_idx, const float* dkv_part, float* dqkv, void* stream) {
     PROF2(ST_DKV_GATHER);
-    CFFM_LAUNCH(k_dkv_gather, ((g->RC + 3) / 4, g->B), (256), 0, (hipStream_t)stream, to_geo(g), inv_ptr, inv_idx, dkv_part, dqkv);
+    REQUIRE((long)g->nW * CFFM_NKEY_PAD * 1024 < (1L << 32), "attn_bwd gather: a clip's partial rows must stay under 4 GB");
+    CFFM_LAUNCH(k_dkv_gather, ((unsigned)(((long)g->B * g->RC + 3) / 4)), (256), 0, (hipStream_t)stream, to_geo(g), inv_ptr, inv_idx, dkv_part, dqkv);
     CHECK_LAUNCH("attn_bwd gather");
     return 0;
+}
+int cffm_dkv_gather(const cffm_geom* g, const int* inv_ptr, const int* inv_idx, const float* dkv_part, float* dqkv, void* stream) {
+    REQUIRE(g && inv_ptr && inv_idx && dkv_part && dqkv, "dkv_gather: null");
+    REQUIRE(g->B >= 1 && g->nW >= 1 && g->RC == 64 * g->nW && (long)g->B * g->RC < (1L << 31), "dkv_gather: bad geometry");
+    return attn_bwd_gather(g, inv_ptr, inv_idx, dkv_part, dqkv, stream);
 }
 int cffm_attn_bwd(const cffm_geom* g, const void* qkv16, const int* key_src, const int* q_dst,
                   const int* inv_ptr, const int* inv_idx, const void* biasH, const float* ao,
@@ -1125,9 +1131,9 @@ int cffm_adamw_step_rows(const cffm_adamw_chunk2* chunks, int nchunks, const flo
     if (nchunks <= 0) return 0;
     REQUIRE(chunks && state && sched && consts && nrows >= 1, "adamw_step_rows: null table or no rows");
     PROF(ST_ADAMW);
-    if (ticket) {
-        CFFM_LAUNCH(k_adamw_rows_tick, ((unsigned)nchunks), (256), 0, (hipStream_t)stream, (const AdamwChunk2*)chunks, grad_base, state, sched, consts,
-                    nrows, active_rows, ticket);
+    if (ticket && nrows <= ADAMW_FUSED_ROWS) {      // (more rows than the one-launch kernel keeps in LDS: the two launches, same results)
+        CFFM_LAUNCH(k_adamw_rows_tick, ((unsigned)((nchunks + ADAMW_WG_CHUNKS - 1) / ADAMW_WG_CHUNKS)), (256), 0, (hipStream_t)stream,
+                    (const AdamwChunk2*)chunks, nchunks, grad_base, state, sched, consts, nrows, active_rows, ticket);
     } else {
         CFFM_LAUNCH(k_adamw_tick_rows, ((unsigned)((nrows + 63) / 64)), (64), 0, (hipStream_t)stream, state, sched, consts, nrows, active_rows);
         CFFM_LAUNCH(k_adamw_rows, ((unsigned)nchunks), (256), 0, (hipStream_t)stream, (const AdamwChunk2*)chunks, grad_base, (const float*)state, consts);

@@ -644,37 +644,76 @@ __global__ void __launch_bounds__(ATT_BK_THREADS) k_cfm_attn_bwd(Geo G, const h1
 // dqkv[b][row][256..767] = sum over the (window, key slot) pairs that read `row` of the partial rows dkv_part[b*nW + window][slot]
 // (512 halfs each: 8 heads x (K 32 | V 32), in units of part_scale[window][head]); inv_ptr [RC+1], inv_idx [nnz] = CSR inverse of key_src (per clip).
 // One wave per token row, a lane owns 8 channels of one head; pooled rows also get their (unused) q third zeroed so the qkv
-// weight/bias gradient GEMMs see zeros there.  grid (ceil(RC/4), B).
+// weight/bias gradient GEMMs see zeros there.  grid ceil(B RC / 4), one dimension: the pooled rows of EVERY clip are dispatched
+// before any target row (a pooled row has up to 49 readers, a target row at most 4: the long rows start first).
+// Summation order of an element (what keeps dqkv the same bits whatever the number of loads in flight): the readers in inv_idx
+// order, whole batches of four as ((x0 s0 + x1 s1) + (x2 s2 + x3 s3)) added to the sum one batch after the other, then the
+// remaining one to three singly.  DKV_DEPTH readers (four batches) are requested before the first is consumed: a 49-reader row
+// is 4 dependent round trips instead of 13.  Measured in the step: depth 4 16.4 us, 8 14.9 us, 16 13.8 us per launch --
+// the depth pays although 16 costs 114 VGPRs (4 waves per SIMD instead of 8); the dispatch order alone does not (16.8 -> 16.4).
+#ifndef DKV_DEPTH
+#define DKV_DEPTH 16
+#endif
+__device__ __forceinline__ void dkv_add4(f32x4& a0, f32x4& a1, const h16x8* x, const float* s) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        a0[c] += ((float)x[0][c] * s[0] + (float)x[1][c] * s[1]) + ((float)x[2][c] * s[2] + (float)x[3][c] * s[3]);
+        a1[c] += ((float)x[0][4 + c] * s[0] + (float)x[1][4 + c] * s[1]) + ((float)x[2][4 + c] * s[2] + (float)x[3][4 + c] * s[3]);
+    }
+}
+__device__ __forceinline__ void dkv_add1(f32x4& a0, f32x4& a1, const h16x8 x, const float s) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { a0[c] += (float)x[c] * s; a1[c] += (float)x[4 + c] * s; }
+}
+// lane `src`'s value of v (src the same in every lane) as a scalar: the partial-row addresses derived from it stay in SGPRs
+__device__ __forceinline__ int dkv_reader(int v, int src) {
+#ifdef CFFM_EMU
+    return __shfl(v, src, 64);
+#else
+    return __builtin_amdgcn_readlane(v, src);
+#endif
+}
 __global__ void __launch_bounds__(256) k_dkv_gather(Geo G, const int* __restrict__ inv_ptr, const int* __restrict__ inv_idx,
                                                      const float* __restrict__ dkv_part, float* __restrict__ dqkv) {
-    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
-    if (row >= G.RC) return;
+    const int lane = threadIdx.x & 63, item = blockIdx.x * 4 + wave_uniform(threadIdx.x >> 6);
+    const int ntok = CFFM_WA * G.nW, npool = G.RC - ntok;
+    if (item >= G.B * G.RC) return;
+    int b, row;
+    if (item < G.B * npool) { b = item / npool; row = ntok + (item - b * npool); }
+    else { const int t = item - G.B * npool; b = t / ntok; row = t - b * ntok; }
     const int e0 = inv_ptr[row], e1 = inv_ptr[row + 1];
-    const h16* part = (const h16*)dkv_part + (long)b * G.nW * CFFM_NKEY_PAD * 512 + 8 * lane;     // partial row: 8 heads x (K 32 | V 32)
-    const float* scl = dkv_part + (long)G.B * G.nW * CFFM_NKEY_PAD * 256 + (long)b * G.nW * CFFM_HEADS + (lane >> 3);
+    // the clip's partial rows (8 heads x (K 32 | V 32) halfs each) and scales as buffer resources: a load is the lane's 32-bit
+    // offset + a scalar offset per reader, no 64-bit address per load in flight (the host checks that a clip's rows stay under 4 GB)
+    const buf_t part = buf_make((const h16*)dkv_part + (long)b * G.nW * CFFM_NKEY_PAD * 512, (uint32_t)G.nW * CFFM_NKEY_PAD * 1024u);
+    const buf_t scl = buf_make(dkv_part + (long)G.B * G.nW * CFFM_NKEY_PAD * 256 + (long)b * G.nW * CFFM_HEADS, (uint32_t)G.nW * CFFM_HEADS * 4u);
+    const uint32_t xoff = 16u * lane, soff = 4u * (lane >> 3);
     f32x4 a0 = (f32x4){0.f, 0.f, 0.f, 0.f}, a1 = a0;
     for (int eb = e0; eb < e1; eb += 64) {          // a row has at most 49 readers; the loop is for generality
         const int n = (e1 - eb < 64) ? e1 - eb : 64;
         const int mine = (lane < n) ? inv_idx[eb + lane] : 0;   // the whole reader list in one load
-        int e = 0;
-        for (; e + 3 < n; e += 4) {                 // 4 independent 16-B loads (+ their scales) in flight per lane
-            const int i0 = __shfl(mine, e, 64), i1 = __shfl(mine, e + 1, 64), i2 = __shfl(mine, e + 2, 64), i3 = __shfl(mine, e + 3, 64);
-            const h16x8 x0 = *(const h16x8*)(part + (long)i0 * 512), x1 = *(const h16x8*)(part + (long)i1 * 512);
-            const h16x8 x2 = *(const h16x8*)(part + (long)i2 * 512), x3 = *(const h16x8*)(part + (long)i3 * 512);
-            const float s0 = scl[(i0 / CFFM_NKEY_PAD) * CFFM_HEADS], s1 = scl[(i1 / CFFM_NKEY_PAD) * CFFM_HEADS];
-            const float s2 = scl[(i2 / CFFM_NKEY_PAD) * CFFM_HEADS], s3 = scl[(i3 / CFFM_NKEY_PAD) * CFFM_HEADS];
+        for (int e = 0; e < n; e += DKV_DEPTH) {
+            const int cnt = n - e < DKV_DEPTH ? n - e : DKV_DEPTH;   // wave-uniform
+            h16x8 x[DKV_DEPTH];
+            float s[DKV_DEPTH];
+            int rd[DKV_DEPTH];                      // every reader's index before the first load is issued: one wait for `mine`
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                a0[c] += ((float)x0[c] * s0 + (float)x1[c] * s1) + ((float)x2[c] * s2 + (float)x3[c] * s3);
-                a1[c] += ((float)x0[4 + c] * s0 + (float)x1[4 + c] * s1) + ((float)x2[4 + c] * s2 + (float)x3[4 + c] * s3);
+            for (int j = 0; j < DKV_DEPTH; ++j) rd[j] = dkv_reader(mine, e + (j < cnt ? j : 0));
+#pragma unroll
+            for (int j = 0; j < DKV_DEPTH; ++j)     // up to DKV_DEPTH independent 16-B loads (+ their scales) in flight per lane
+                if (j < cnt) {
+                    const f32x4 raw = buf_ld16(part, xoff, (uint32_t)rd[j] * 1024u);
+                    __builtin_memcpy(&x[j], &raw, 16);
+                    s[j] = buf_ld4(scl, soff, (uint32_t)(rd[j] / CFFM_NKEY_PAD) * (CFFM_HEADS * 4u));
+                }
+#pragma unroll
+            for (int q = 0; q < DKV_DEPTH; q += 4) {
+                if (q + 4 <= cnt) dkv_add4(a0, a1, x + q, s + q);
+                else {
+#pragma unroll
+                    for (int j = q; j < q + 3; ++j)
+                        if (j < cnt) dkv_add1(a0, a1, x[j], s[j]);
+                }
             }
-        }
-        for (; e < n; ++e) {
-            const int i0 = __shfl(mine, e, 64);
-            const h16x8 x0 = *(const h16x8*)(part + (long)i0 * 512);
-            const float s0 = scl[(i0 / CFFM_NKEY_PAD) * CFFM_HEADS];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) { a0[c] += (float)x0[c] * s0; a1[c] += (float)x0[4 + c] * s0; }
         }
     }
     float* drow = dqkv + ((long)b * G.RC + row) * 768;

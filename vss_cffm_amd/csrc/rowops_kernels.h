@@ -502,12 +502,26 @@ __device__ __forceinline__ double adamw_ipow(double b, double t) {
     }
     return r;
 }
-// the four state values of row r after its next step (t, lr_t / (1 - b1^t), 1 / sqrt(1 - b2^t), 1 - lr_t wd)
-__device__ __forceinline__ void adamw_next_state(const float* __restrict__ state, const float* __restrict__ sched, const double* __restrict__ consts,
-                                                 int r, float out[4]) {
-    const double* c = consts + (long)ADAMW_NCONST * r;
-    const double t = (double)state[4 * r] + 1.0, wd = (double)sched[2 * r + 1];
-    double lr = (double)sched[2 * r];
+// what the factors of row r are derived from, fetched in one go (every load independent of the others): the row's constants, its step
+// count and (lr, weight decay) -- ONE 8-byte read where the table allows it: in a captured step `sched` is pinned host memory, every
+// read of it an uncached round trip over the host link
+struct AdamwRowIn { double c[11]; float t, lr, wd; };
+__device__ __forceinline__ AdamwRowIn adamw_row_load(const float* __restrict__ state, const float* __restrict__ sched, const double* __restrict__ consts,
+                                                     int r) {
+    AdamwRowIn in;
+#pragma unroll
+    for (int k = 0; k < 11; ++k) in.c[k] = consts[(long)ADAMW_NCONST * r + k];
+    typedef float sched_pair __attribute__((ext_vector_type(2)));
+    if (((uintptr_t)sched & 7) == 0) { const sched_pair lw = ((const sched_pair*)sched)[r]; in.lr = lw[0]; in.wd = lw[1]; }
+    else { in.lr = sched[2 * r]; in.wd = sched[2 * r + 1]; }
+    in.t = state[4 * r];
+    return in;
+}
+// the four state values of the row after its next step (t, lr_t / (1 - b1^t), 1 / sqrt(1 - b2^t), 1 - lr_t wd)
+__device__ __forceinline__ void adamw_row_eval(const AdamwRowIn& in, float out[4]) {
+    const double* c = in.c;
+    const double t = (double)in.t + 1.0, wd = (double)in.wd;
+    double lr = (double)in.lr;
     if (c[3] == 1.0) {                      // poly decay with linear warm-up.  The iteration is the OPTIMIZER's (c[10]: steps taken so far,
                                             // advanced for every row on every step), not the row's own count t: mmcv derives every group's rate
                                             // from the runner's iteration, so a parameter that sits steps out, or first gets a gradient late
@@ -522,6 +536,11 @@ __device__ __forceinline__ void adamw_next_state(const float* __restrict__ state
     out[1] = (float)(lr / (1.0 - adamw_ipow(c[0], t)));
     out[2] = (float)(1.0 / sqrt(1.0 - adamw_ipow(c[1], t)));
     out[3] = (float)(1.0 - lr * wd);
+}
+__device__ __forceinline__ void adamw_next_state(const float* __restrict__ state, const float* __restrict__ sched, const double* __restrict__ consts,
+                                                 int r, float out[4]) {
+    const AdamwRowIn in = adamw_row_load(state, sched, consts, r);
+    adamw_row_eval(in, out);
 }
 __global__ void k_adamw_tick_rows(float* __restrict__ state, const float* __restrict__ sched, double* __restrict__ consts, int nrows,
                                   const int* __restrict__ active) {
@@ -545,11 +564,9 @@ __device__ __forceinline__ void adamw_elem(float& p, float& m, float& v, float g
     v = beta2 * v + omb2 * g * g;
     p = p * decay - step_size * (m / (sqrtf(v) * inv_sqrt_bc2 + eps));
 }
-__device__ __forceinline__ void adamw_update_chunk(AdamwChunk2 c, const float* __restrict__ grad_base, float step_size, float inv_sqrt_bc2,
-                                                   float decay, const double* __restrict__ consts) {
-    if (grad_base) c.g = (const float*)((const char*)grad_base + (uintptr_t)c.g);
-    const double b1 = consts[ADAMW_NCONST * c.row], b2 = consts[ADAMW_NCONST * c.row + 1];
-    const float beta1 = (float)b1, beta2 = (float)b2, omb1 = (float)(1.0 - b1), omb2 = (float)(1.0 - b2), eps = (float)consts[ADAMW_NCONST * c.row + 2];
+// (g of the entry is an address here)
+__device__ __forceinline__ void adamw_update_chunk_with(const AdamwChunk2& c, float step_size, float inv_sqrt_bc2, float decay, float beta1, float omb1,
+                                                        float beta2, float omb2, float eps) {
     const bool vec = (((uintptr_t)c.p | (uintptr_t)c.g | (uintptr_t)c.m | (uintptr_t)c.v) & 15) == 0;
     const int n4 = vec ? c.n / 4 : 0;
     for (int e = threadIdx.x; e < n4; e += 256) {
@@ -569,51 +586,93 @@ __device__ __forceinline__ void adamw_update_chunk(AdamwChunk2 c, const float* _
         c.m[e] = mk; c.v[e] = vk; c.p[e] = pk;
     }
 }
+__device__ __forceinline__ void adamw_update_chunk(AdamwChunk2 c, const float* __restrict__ grad_base, float step_size, float inv_sqrt_bc2,
+                                                   float decay, const double* __restrict__ consts) {
+    if (grad_base) c.g = (const float*)((const char*)grad_base + (uintptr_t)c.g);
+    const double b1 = consts[ADAMW_NCONST * c.row], b2 = consts[ADAMW_NCONST * c.row + 1];
+    const float beta1 = (float)b1, beta2 = (float)b2, omb1 = (float)(1.0 - b1), omb2 = (float)(1.0 - b2), eps = (float)consts[ADAMW_NCONST * c.row + 2];
+    adamw_update_chunk_with(c, step_size, inv_sqrt_bc2, decay, beta1, omb1, beta2, omb2, eps);
+}
 __global__ void __launch_bounds__(256) k_adamw_rows(const AdamwChunk2* __restrict__ chunks, const float* __restrict__ grad_base,
                                                      const float* __restrict__ state, const double* __restrict__ consts) {
     const AdamwChunk2 c = chunks[blockIdx.x];
     adamw_update_chunk(c, grad_base, state[4 * c.row + 1], state[4 * c.row + 2], state[4 * c.row + 3], consts);
 }
 // The same update with the step-count tick folded in (one launch instead of two on the tail of a training step): every workgroup
-// derives its row's factors from the state BEFORE the step (adamw_next_state: the arithmetic of k_adamw_tick_rows, so the results are
+// derives the rows' factors from the state BEFORE the step (adamw_row_eval: the arithmetic of k_adamw_tick_rows, so the results are
 // bit-identical); the workgroup that draws the last ticket -- all others have read the state by then -- stores the advanced state of
 // the active rows; the tickets are back at zero for the next launch.
-__global__ void __launch_bounds__(256) k_adamw_rows_tick(const AdamwChunk2* __restrict__ chunks, const float* __restrict__ grad_base,
+// No load of the launch waits for more than one other: the workgroup's last wave fetches what the factors of EVERY row (at most
+// ADAMW_FUSED_ROWS; the host takes the two-launch form above that) are derived from -- state, constants and the possibly host-resident
+// sched, lane r for row r -- beside the table entries, not behind them, evaluates them while the chunks' operands are in flight and
+// leaves them in LDS together with the float constants of the update (beta1, 1 - beta1, beta2, 1 - beta2, eps: these used to be three
+// more loads behind the barrier).  The last workgroup stores its LDS copy: no second evaluation, no second read of sched.
+// A workgroup takes ADAMW_WG_CHUNKS consecutive entries of the table, all their operands requested up front: half the evaluations,
+// host reads and tickets per launch.
+#ifndef ADAMW_WG_CHUNKS
+#define ADAMW_WG_CHUNKS 2
+#endif
+#define ADAMW_FUSED_ROWS 64
+__global__ void __launch_bounds__(256) k_adamw_rows_tick(const AdamwChunk2* __restrict__ chunks, int nchunks, const float* __restrict__ grad_base,
                                                           float* __restrict__ state, const float* __restrict__ sched,
                                                           double* __restrict__ consts, int nrows, const int* __restrict__ active,
                                                           int* __restrict__ ticket) {
-    __shared__ float sc[4];
+    __shared__ float sc[ADAMW_FUSED_ROWS][9];     // per row: t, step size, 1 / sqrt(1 - b2^t), decay | beta1, 1 - beta1, beta2, 1 - beta2, eps
     __shared__ int last;
-    AdamwChunk2 c = chunks[blockIdx.x];
-    const bool full = c.n == 2048 && (((uintptr_t)c.p | (uintptr_t)(grad_base ? (const float*)((const char*)grad_base + (uintptr_t)c.g) : c.g) | (uintptr_t)c.m | (uintptr_t)c.v) & 15) == 0;
-    if (full) {
-        // a whole aligned chunk (all but the last of a tensor): its 8 KB per operand are requested BEFORE lane 0 works out the row's
-        // factors (double-precision divisions and a square root on one lane: ~2 us that every thread of the workgroup would wait out)
-        if (grad_base) c.g = (const float*)((const char*)grad_base + (uintptr_t)c.g);
-        const int e0 = threadIdx.x, e1 = threadIdx.x + 256;
-        f32x4 p0 = ((const f32x4*)c.p)[e0], m0 = ((const f32x4*)c.m)[e0], v0 = ((const f32x4*)c.v)[e0], p1 = ((const f32x4*)c.p)[e1],
-              m1 = ((const f32x4*)c.m)[e1], v1 = ((const f32x4*)c.v)[e1];
-        const f32x4 g0 = ((const f32x4*)c.g)[e0], g1 = ((const f32x4*)c.g)[e1];
-        if (threadIdx.x == 0) adamw_next_state(state, sched, consts, c.row, sc);
-        __syncthreads();
-        const float step_size = sc[1], inv_sqrt_bc2 = sc[2], decay = sc[3];
-        const double b1 = consts[ADAMW_NCONST * c.row], b2 = consts[ADAMW_NCONST * c.row + 1];
-        const float beta1 = (float)b1, beta2 = (float)b2, omb1 = (float)(1.0 - b1), omb2 = (float)(1.0 - b2), eps = (float)consts[ADAMW_NCONST * c.row + 2];
+    const int first = blockIdx.x * ADAMW_WG_CHUNKS;
+    const int myrow = (int)threadIdx.x - 192;     // the last wave: lane r works out row r
+    const bool rowlane = myrow >= 0 && myrow < nrows;
+    AdamwChunk2 c[ADAMW_WG_CHUNKS];
+    bool full[ADAMW_WG_CHUNKS];
+    f32x4 p0[ADAMW_WG_CHUNKS], m0[ADAMW_WG_CHUNKS], v0[ADAMW_WG_CHUNKS], g0[ADAMW_WG_CHUNKS], p1[ADAMW_WG_CHUNKS], m1[ADAMW_WG_CHUNKS],
+          v1[ADAMW_WG_CHUNKS], g1[ADAMW_WG_CHUNKS];
+    const int e0 = threadIdx.x, e1 = threadIdx.x + 256;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float pk = p0[k], mk = m0[k], vk = v0[k];
-            adamw_elem(pk, mk, vk, g0[k], beta1, omb1, beta2, omb2, decay, step_size, inv_sqrt_bc2, eps);
-            p0[k] = pk; m0[k] = mk; v0[k] = vk;
-            pk = p1[k]; mk = m1[k]; vk = v1[k];
-            adamw_elem(pk, mk, vk, g1[k], beta1, omb1, beta2, omb2, decay, step_size, inv_sqrt_bc2, eps);
-            p1[k] = pk; m1[k] = mk; v1[k] = vk;
+    for (int j = 0; j < ADAMW_WG_CHUNKS; ++j) c[j] = chunks[first + j < nchunks ? first + j : first];
+    AdamwRowIn in;
+    if (rowlane) in = adamw_row_load(state, sched, consts, myrow);
+#pragma unroll
+    for (int j = 0; j < ADAMW_WG_CHUNKS; ++j) {
+        if (first + j >= nchunks) c[j].n = 0;
+        if (grad_base) c[j].g = (const float*)((const char*)grad_base + (uintptr_t)c[j].g);
+        full[j] = c[j].n == 2048 && (((uintptr_t)c[j].p | (uintptr_t)c[j].g | (uintptr_t)c[j].m | (uintptr_t)c[j].v) & 15) == 0;
+    }
+    // a whole aligned chunk (all but the last of a tensor): its 8 KB per operand are requested BEFORE the rows' factors are worked out
+    // (double-precision divisions and a square root: ~2 us that every thread of the workgroup would wait out)
+#pragma unroll
+    for (int j = 0; j < ADAMW_WG_CHUNKS; ++j)
+        if (full[j]) {
+            p0[j] = ((const f32x4*)c[j].p)[e0]; m0[j] = ((const f32x4*)c[j].m)[e0]; v0[j] = ((const f32x4*)c[j].v)[e0];
+            p1[j] = ((const f32x4*)c[j].p)[e1]; m1[j] = ((const f32x4*)c[j].m)[e1]; v1[j] = ((const f32x4*)c[j].v)[e1];
+            g0[j] = ((const f32x4*)c[j].g)[e0]; g1[j] = ((const f32x4*)c[j].g)[e1];
         }
-        ((f32x4*)c.p)[e0] = p0; ((f32x4*)c.m)[e0] = m0; ((f32x4*)c.v)[e0] = v0;
-        ((f32x4*)c.p)[e1] = p1; ((f32x4*)c.m)[e1] = m1; ((f32x4*)c.v)[e1] = v1;
-    } else {
-        if (threadIdx.x == 0) adamw_next_state(state, sched, consts, c.row, sc);
-        __syncthreads();
-        adamw_update_chunk(c, grad_base, sc[1], sc[2], sc[3], consts);
+    if (rowlane) {
+        float o[4];
+        adamw_row_eval(in, o);
+        float* d = sc[myrow];
+        d[0] = o[0]; d[1] = o[1]; d[2] = o[2]; d[3] = o[3];
+        d[4] = (float)in.c[0]; d[5] = (float)(1.0 - in.c[0]); d[6] = (float)in.c[1]; d[7] = (float)(1.0 - in.c[1]); d[8] = (float)in.c[2];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < ADAMW_WG_CHUNKS; ++j) {
+        const float* f = sc[c[j].row];
+        const float step_size = f[1], inv_sqrt_bc2 = f[2], decay = f[3], beta1 = f[4], omb1 = f[5], beta2 = f[6], omb2 = f[7], eps = f[8];
+        if (full[j]) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float pk = p0[j][k], mk = m0[j][k], vk = v0[j][k];
+                adamw_elem(pk, mk, vk, g0[j][k], beta1, omb1, beta2, omb2, decay, step_size, inv_sqrt_bc2, eps);
+                p0[j][k] = pk; m0[j][k] = mk; v0[j][k] = vk;
+                pk = p1[j][k]; mk = m1[j][k]; vk = v1[j][k];
+                adamw_elem(pk, mk, vk, g1[j][k], beta1, omb1, beta2, omb2, decay, step_size, inv_sqrt_bc2, eps);
+                p1[j][k] = pk; m1[j][k] = mk; v1[j][k] = vk;
+            }
+            ((f32x4*)c[j].p)[e0] = p0[j]; ((f32x4*)c[j].m)[e0] = m0[j]; ((f32x4*)c[j].v)[e0] = v0[j];
+            ((f32x4*)c[j].p)[e1] = p1[j]; ((f32x4*)c[j].m)[e1] = m1[j]; ((f32x4*)c[j].v)[e1] = v1[j];
+        } else if (c[j].n > 0) {
+            adamw_update_chunk_with(c[j], step_size, inv_sqrt_bc2, decay, beta1, omb1, beta2, omb2, eps);
+        }
     }
     // (no fence: the state values were consumed above, so those loads are complete before the ticket is drawn, and nothing this
     //  workgroup wrote is read by another one -- a device-scope fence here would write back the XCD's whole L2 per workgroup: 80 us)
@@ -630,13 +689,12 @@ __global__ void __launch_bounds__(256) k_adamw_rows_tick(const AdamwChunk2* __re
     }
     __syncthreads();
     if (!last) return;
-    for (int r = threadIdx.x; r < nrows; r += 256) {
-        if (!active || active[r]) {
-            float o[4];
-            adamw_next_state(state, sched, consts, r, o);
-            state[4 * r] = o[0]; state[4 * r + 1] = o[1]; state[4 * r + 2] = o[2]; state[4 * r + 3] = o[3];
+    if (rowlane) {                                // what this workgroup worked out from the state before the step: nobody has written it since
+        if (!active || active[myrow]) {
+            const float* f = sc[myrow];
+            state[4 * myrow] = f[0]; state[4 * myrow + 1] = f[1]; state[4 * myrow + 2] = f[2]; state[4 * myrow + 3] = f[3];
         }
-        consts[ADAMW_NCONST * r + 10] += 1.0;    // the global iteration: every row, active or not
+        consts[ADAMW_NCONST * myrow + 10] = in.c[10] + 1.0;    // the global iteration: every row, active or not
     }
     if (threadIdx.x == 0) *ticket = 0;
 }
