@@ -728,6 +728,38 @@ int cffm_patch_embed_bwd(const float* x_nchw, const float* w, const float* gamma
                          float* dx_nchw /* may be NULL */, float* dw, float* db, float* dgamma, float* dbeta, void* workspace, int B, int Cin,
                          int H, int W, int Cout, int k, int stride, float eps, void* stream);
 
+/* ---- added under ABI 13, additive: one Linear layer on token rows, forward and backward, with a residual and a per-sample factor ----
+ * What a MiT block's q / kv / fc1 (no residual, no factor) and proj / fc2 (residual = the block input, factor = the DropPath mask / keep)
+ * compute in a training pass (csrc/gemm_kernels.h, host side csrc/gemm.h).  x [M][K], w [N][K] (nn.Linear's own layout), b [N] or NULL,
+ * residual [M][N] or NULL, scale [B] or NULL with M = B * rows_per_sample; row m belongs to sample m / rows_per_sample.
+ *   cffm_linear_rows_fwd   y[m] = residual[m] + scale[m / rps] * (x[m] w^T + b); a NULL b, residual or scale drops its term.  A sample
+ *                          whose scale is 0 gets the bits of residual (zeros without one), for finite operands.  Nothing is saved.
+ *   cffm_linear_rows_bwd   with g[m] = scale[m / rps] * dy[m], which is never written to memory:  dx [M][K] = g w (the factor applied to
+ *                          the finished rows; dx == NULL skips it; rows of a sample whose scale is 0 are exact zeros);  dw [N][K] = g^T x
+ *                          (the factor applied to the dy tile while it is staged);  db [N] = the column sum of g in fp32 (NULL skips it).
+ *                          The gradient of residual is dy itself: the caller passes it on, nothing is copied.
+ * Products: the three-pass bf16 split of the other Linear GEMMs (fp32 operands split into bf16 hi + lo, hi.lo + lo.hi + hi.hi, fp32
+ * accumulation).  No atomics: dw's contraction over the M rows is split into slabs and db into records whose count and order follow from
+ * (M, N, K) alone, a second kernel adds them in that order: the same bits on every call.  workspace:
+ * cffm_linear_rows_bwd_workspace_bytes(...) bytes, 16-byte aligned, need not be initialised; it holds the dw slabs [ksplit][N][K] and the db
+ * records only (never an [M][N] temporary) and may be 0 bytes, in which case NULL is accepted; with_dx is taken for symmetry and changes
+ * nothing (dx needs no workspace), with_db = whether db will be non-null.
+ * Limits: M >= 1; N and K multiples of 4 (not 16 as in cffm_mit_stage_infer: the tile loads read 16-byte pieces and nothing else here asks
+ * for more; hidden sizes such as 20 C stay inside); M a multiple of rows_per_sample >= 1; M*max(N, K) and N*K below 2^30 (an operand is
+ * addressed with 32-bit byte offsets).  Errors (nothing is enqueued, every output stays as it is, cffm_last_error is set; the workspace
+ * query returns < 0): these limits; a NULL x / w / y / dy / dw, or a NULL workspace of non-zero size; a pointer that is not 16-byte
+ * aligned (scale: 4-byte); y equal to any input pointer -- x, w, b, residual, scale: there is no in-place form, y == residual included;
+ * dx / dw / db equal to dy, x, w or scale, to each other or to the workspace (only equal pointers are looked for, not overlapping ranges).
+ * All of these, and the grant of the kernels' LDS, are settled before the first launch.  The one error that can follow a launch is the
+ * runtime refusing it (code -2): what was enqueued before it then stays enqueued.  Everything is enqueued on `stream` alone: no allocation,
+ * no host round trip, so the calls can be captured into a graph.  dw cannot be skipped (dx and db can): a layer with a frozen weight still
+ * has it formed. */
+int cffm_linear_rows_fwd(const float* x, const float* w, const float* b /* NULL ok */, const float* residual /* NULL ok */,
+                         const float* scale /* NULL ok */, float* y, long M, int N, int K, int rows_per_sample, void* stream);
+long cffm_linear_rows_bwd_workspace_bytes(long M, int N, int K, int rows_per_sample, int with_dx, int with_db);   /* < 0: refused */
+int cffm_linear_rows_bwd(const float* dy, const float* x, const float* w, const float* scale /* NULL ok */, float* dx /* NULL ok */,
+                         float* dw, float* db /* NULL ok */, void* workspace, long M, int N, int K, int rows_per_sample, void* stream);
+
 /* n = 1..4 consecutive MiT stages, each WITH its patch embedding, as one call: per stage cffm_patch_embed_fwd's kernel writes the
  * normalised rows straight into the stage's residual buffer (cffm_nchw_ln_rows does not run), then the blocks and cffm_ln_rows_nchw exactly as
  * cffm_mit_stage_infer enqueues them.  x_nchw [B, stages[0].Cin, Hin, Win] is stage 0's input, outs[i] (host array of n device pointers)

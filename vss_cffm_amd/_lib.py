@@ -209,6 +209,9 @@ SIGNATURES = {
     'cffm_patch_embed_fwd_train': (ci, [vp] * 7 + [ci] * 7 + [cf, vp]),
     'cffm_patch_embed_bwd_workspace_bytes': (cl, [ci] * 8),
     'cffm_patch_embed_bwd': (ci, [vp] * 11 + [ci] * 7 + [cf, vp]),
+    'cffm_linear_rows_fwd': (ci, [vp] * 6 + [cl, ci, ci, ci, vp]),
+    'cffm_linear_rows_bwd_workspace_bytes': (cl, [cl, ci, ci, ci, ci, ci]),
+    'cffm_linear_rows_bwd': (ci, [vp] * 8 + [cl, ci, ci, ci, vp]),
     'cffm_mit_infer_ws_floats': (cl, [MSP, ci]),
     'cffm_mit_infer': (ci, [MSP, ci, vp, C.POINTER(vp), vp, vp]),
 }

@@ -20,7 +20,7 @@ In front of kv, stages with sr_ratio > 1 reduce the map with the `sr` convolutio
 no NCHW view, no transposes, the Conv2d weight read in its own layout.  ``'torch'`` is the reference's permute / reshape, Conv2d,
 reshape / permute, LayerNorm: the default (the fused pass is exact fp32 but, as measured, not faster at model level),
 the A/B partner in the tests and what CPU tensors, other dtypes and shapes outside the kernel's limits get.  `sr_impl` is independent
-of `attn_impl`.  The three Linear layers are stock PyTorch either way.
+of `attn_impl`.  The three Linear layers are stock PyTorch either way (unless `linear_impl`, below, says otherwise).
 
 For inference, ``MixVisionTransformer.stage_impl = 'hip'`` runs everything of a stage behind ``patch_embed.proj`` -- the embedding's
 LayerNorm, every block, the stage's LayerNorm and the change to an NCHW map -- as ONE library call (``ops.mit_stage_infer`` ->
@@ -43,6 +43,13 @@ On the same path ``conv_impl = 'hip'`` (``MixVisionTransformer.set_conv_impl``) 
 convolution, flatten / transpose and its LayerNorm -- to the library as one call per direction (``ops.overlap_patch_embed`` ->
 cffm_patch_embed_fwd_train / cffm_patch_embed_bwd): bf16-split products, every gradient summed in a fixed order.  ``'torch'`` (the default)
 is stock Conv2d, which is also what a convolution outside the kernel's limits and a 7 x 7 embedding whose input requires grad get.
+
+And ``linear_impl = 'hip'`` (``MixVisionTransformer.set_linear_impl``) hands the five Linear layers of every block to the library in both
+directions (``ops.linear_rows`` -> cffm_linear_rows_fwd / cffm_linear_rows_bwd): q, kv and fc1 as they are; proj and fc2 with the block input
+as the residual and the DropPath factor of each sample as a scale in the GEMM's epilogue, so that each residual line of ``Block.forward`` is one
+call.  The factor is drawn as ``DropPath.forward`` draws it, so both settings consume the generator alike and drop the same samples.  ``'torch'``
+(the default) is stock nn.Linear and the reference's residual lines, which is also what tensors outside the limits, other dtypes, CPU tensors
+and modules with ``proj_drop`` / ``drop`` > 0 get.
 """
 import math
 from functools import partial
@@ -52,9 +59,9 @@ import torch.nn as nn
 
 from . import _lib
 from .checkpoint import load_reference_checkpoint
-from .ops import (dwconv_gelu, layer_norm_rows, layer_norm_rows_nchw, ln_supported, mit_infer, mit_stage_cfg, mit_stage_infer, mit_stage_supported,
-                  mit_stage_tensors, mit_stages, nchw_layer_norm_rows, overlap_patch_embed, patch_embed_out_hw, patch_embed_supported, sr_reduce,
-                  sr_reduce_supported, sra_attention)
+from .ops import (dwconv_gelu, layer_norm_rows, layer_norm_rows_nchw, linear_rows, linear_rows_supported, ln_supported, mit_infer, mit_stage_cfg,
+                  mit_stage_infer, mit_stage_supported, mit_stage_tensors, mit_stages, nchw_layer_norm_rows, overlap_patch_embed,
+                  patch_embed_out_hw, patch_embed_supported, sr_reduce, sr_reduce_supported, sra_attention)
 from .registry import BACKBONES
 
 
@@ -75,6 +82,45 @@ def _norm_rows(impl, norm, x):
     if _norm_fused(impl, norm, x, x.shape[-1]):
         return layer_norm_rows(x, norm.weight, norm.bias, norm.eps)
     return norm(x)
+
+
+def _linear_fused(impl, lin, x, drop=None):
+    """whether `lin` of the token rows x takes the library's Linear (linear_impl = 'hip'): a plain nn.Linear on fp32 rows [B, N, C] or [M, C] on
+    the GPU (or under the emulator override), parameters where x is, inside the kernels' limits, and no dropout (`drop`: the nn.Dropout of the
+    owning module that sits behind its last Linear).  Anything else: the stock line."""
+    if impl != 'hip' or type(lin) is not nn.Linear or not (x.is_cuda or _lib._override is not None) or x.dtype != torch.float32:
+        return False
+    if x.dim() not in (2, 3) or x.numel() == 0 or x.shape[-1] != lin.in_features or (drop is not None and drop.p != 0):
+        return False
+    if any(t is not None and (t.dtype != torch.float32 or t.device != x.device) for t in (lin.weight, lin.bias)):
+        return False
+    return linear_rows_supported(lin.in_features, lin.out_features, x.numel() // x.shape[-1])
+
+
+def _linear_rows(impl, lin, x, drop=None):
+    """lin(x) of token rows: one library call per direction with linear_impl = 'hip', the module's own forward otherwise"""
+    if _linear_fused(impl, lin, x, drop):
+        return linear_rows(x, lin.weight, lin.bias)
+    return lin(x)
+
+
+def _drop_scale(drop_path, x):
+    """the factor DropPath.forward multiplies each sample of x with, as a [B] tensor, drawn with DropPath's own torch.rand call (the same
+    shape, dtype and device: the generator moves as it does there); None where DropPath is the identity"""
+    if type(drop_path) is not DropPath or drop_path.drop_prob == 0. or not drop_path.training:
+        return None
+    keep = 1 - drop_path.drop_prob
+    mask = keep + torch.rand((x.shape[0],) + (1,) * (x.dim() - 1), dtype=x.dtype, device=x.device)
+    return mask.floor_().div_(keep).reshape(-1)
+
+
+def _residual_linear(impl, lin, x, drop, residual, drop_path):
+    """residual + drop_path(drop(lin(x))): with linear_impl = 'hip' one library call, DropPath's factor and the residual in the GEMM's
+    epilogue; the reference's line otherwise"""
+    if (_linear_fused(impl, lin, x, drop) and type(drop_path) in (DropPath, nn.Identity) and residual.dtype == torch.float32
+            and residual.device == x.device and tuple(residual.shape) == tuple(x.shape[:-1]) + (lin.out_features,)):
+        return linear_rows(x, lin.weight, lin.bias, residual, _drop_scale(drop_path, x))
+    return residual + drop_path(drop(lin(x)))
 
 
 def _init_weights(m):
@@ -129,6 +175,7 @@ class Mlp(nn.Module):
     # 'hip': dwconv + bias + GELU in one kernel of libcffm_hip.so for fp32 GPU tensors (it raises when the library is missing);
     # 'torch': the reference's op sequence (what everything else gets, and the A/B partner in the tests)
     dwconv_impl = 'hip'
+    linear_impl = 'torch'      # 'hip': fc1 / fc2 are the library's Linear, forward and backward (see MixVisionTransformer.linear_impl)
 
     def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.):
         super().__init__()
@@ -146,13 +193,17 @@ class Mlp(nn.Module):
                 and type(self.act) is nn.GELU and getattr(self.act, 'approximate', 'none') == 'none' and self.drop.p == 0
                 and x.shape[-1] % 4 == 0)
 
-    def forward(self, x, H, W):
-        x = self.fc1(x)
+    def forward(self, x, H, W, residual=None, drop_path=None):
+        """residual / drop_path: handed in by a Block with linear_impl = 'hip'; the result is then the whole residual line
+        residual + drop_path(mlp(x))"""
+        x = _linear_rows(self.linear_impl, self.fc1, x, self.drop)
         if self._fused(x):
             x = dwconv_gelu(x, self.dwconv.dwconv.weight, self.dwconv.dwconv.bias, H, W)
         else:
             x = self.drop(self.act(self.dwconv(x, H, W)))
-        return self.drop(self.fc2(x))
+        if residual is not None:
+            return _residual_linear(self.linear_impl, self.fc2, x, self.drop, residual, drop_path)
+        return self.drop(_linear_rows(self.linear_impl, self.fc2, x, self.drop))
 
 
 class Attention(nn.Module):
@@ -166,6 +217,8 @@ class Attention(nn.Module):
     sr_impl = 'torch'
     # 'hip': the LayerNorm behind the stock `sr` convolution is the library's, forward and backward (see MixVisionTransformer.norm_impl)
     norm_impl = 'torch'
+    # 'hip': q / kv / proj are the library's Linear, forward and backward (see MixVisionTransformer.linear_impl)
+    linear_impl = 'torch'
 
     def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, attn_drop=0., proj_drop=0., sr_ratio=1):
         super().__init__()
@@ -199,22 +252,34 @@ class Attention(nn.Module):
             return sr_reduce(x, self.sr.weight, self.sr.bias, self.norm.weight, self.norm.bias, H, W, self.sr_ratio, self.norm.eps)
         return _norm_rows(self.norm_impl, self.norm, self.sr(x.permute(0, 2, 1).reshape(B, C, H, W)).reshape(B, C, -1).permute(0, 2, 1))
 
-    def forward(self, x, H, W):
+    def _lin(self, lin, x):
+        return _linear_rows(self.linear_impl, lin, x, self.proj_drop)
+
+    def _tail(self, x, residual, drop_path):
+        if residual is not None:
+            return _residual_linear(self.linear_impl, self.proj, x, self.proj_drop, residual, drop_path)
+        return self.proj_drop(self._lin(self.proj, x))
+
+    def forward(self, x, H, W, residual=None, drop_path=None):
+        """residual / drop_path: handed in by a Block with linear_impl = 'hip'; the result is then the whole residual line
+        residual + drop_path(attn(x))"""
         B, N, C = x.shape
         if self._fused(x):
-            kv = self.kv(self._reduced(x, H, W) if self.sr_ratio > 1 else x)
-            return self.proj_drop(self.proj(sra_attention(self.q(x), kv, self.num_heads, self.scale)))
+            kv = self._lin(self.kv, self._reduced(x, H, W) if self.sr_ratio > 1 else x)
+            return self._tail(sra_attention(self._lin(self.q, x), kv, self.num_heads, self.scale), residual, drop_path)
         hd = C // self.num_heads
-        q = self.q(x).reshape(B, N, self.num_heads, hd).permute(0, 2, 1, 3)
+        q = self._lin(self.q, x).reshape(B, N, self.num_heads, hd).permute(0, 2, 1, 3)
         if self.sr_ratio > 1:
             x = self._reduced(x, H, W)
-        k, v = self.kv(x).reshape(B, -1, 2, self.num_heads, hd).permute(2, 0, 3, 1, 4)
+        k, v = self._lin(self.kv, x).reshape(B, -1, 2, self.num_heads, hd).permute(2, 0, 3, 1, 4)
         attn = self.attn_drop(((q @ k.transpose(-2, -1)) * self.scale).softmax(dim=-1))
-        return self.proj_drop(self.proj((attn @ v).transpose(1, 2).reshape(B, N, C)))
+        return self._tail((attn @ v).transpose(1, 2).reshape(B, N, C), residual, drop_path)
 
 
 class Block(nn.Module):
     norm_impl = 'torch'        # 'hip': norm1 / norm2 are the library's LayerNorm, forward and backward (see MixVisionTransformer.norm_impl)
+    # 'hip': each residual line is closed inside attn / mlp, by the library's Linear where proj / fc2 are eligible (MixVisionTransformer.linear_impl)
+    linear_impl = 'torch'
 
     def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, qk_scale=None, drop=0., attn_drop=0., drop_path=0.,
                  act_layer=nn.GELU, norm_layer=nn.LayerNorm, sr_ratio=1):
@@ -228,6 +293,9 @@ class Block(nn.Module):
         self.apply(_init_weights)
 
     def forward(self, x, H, W):
+        if self.linear_impl == 'hip':
+            x = self.attn(_norm_rows(self.norm_impl, self.norm1, x), H, W, residual=x, drop_path=self.drop_path)
+            return self.mlp(_norm_rows(self.norm_impl, self.norm2, x), H, W, residual=x, drop_path=self.drop_path)
         x = x + self.drop_path(self.attn(_norm_rows(self.norm_impl, self.norm1, x), H, W))
         return x + self.drop_path(self.mlp(_norm_rows(self.norm_impl, self.norm2, x), H, W))
 
@@ -296,6 +364,12 @@ class MixVisionTransformer(nn.Module):
     # embedding whose input requires grad, takes the stock line, silently.  'torch': stock Conv2d -- the default (DESIGN section 3w has
     # the measurements).  The inference paths (stage_impl, embed_impl) are not touched and win where they apply.
     conv_impl = 'torch'
+    # 'hip': on the modules' own path the five Linear layers of every block -- q, kv, proj, fc1, fc2 -- are the library's bf16-split GEMMs,
+    # forward and backward (ops.linear_rows), proj and fc2 with the residual and the DropPath factor in the epilogue: fp32 GPU tensors
+    # inside the kernels' limits, proj_drop.p == 0 and mlp.drop.p == 0; anything else takes the stock line, silently.  'torch': stock
+    # nn.Linear -- the default (DESIGN section 3z has the measurements).  Attention, Mlp and Block carry an attribute of the same name;
+    # set_linear_impl sets them all.
+    linear_impl = 'torch'
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dims=[64, 128, 256, 512], num_heads=[1, 2, 4, 8],
                  mlp_ratios=[4, 4, 4, 4], qkv_bias=False, qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.,
@@ -358,6 +432,14 @@ class MixVisionTransformer(nn.Module):
         for m in self.modules():
             if hasattr(type(m), 'conv_impl'):
                 m.conv_impl = impl
+
+    def set_linear_impl(self, impl):
+        """linear_impl of the model and of every Attention, Mlp and Block"""
+        if impl not in ('torch', 'hip'):
+            raise ValueError("linear_impl must be 'torch' or 'hip', got %r" % (impl,))
+        for m in self.modules():
+            if hasattr(type(m), 'linear_impl'):
+                m.linear_impl = impl
 
     def freeze_patch_emb(self):
         self.patch_embed1.requires_grad = False      # (as in the reference: an attribute on the module, the parameters keep theirs)

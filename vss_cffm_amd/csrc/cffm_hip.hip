@@ -3507,6 +3507,69 @@ int cffm_patch_embed_bwd(const float* x_nchw, const float* w, const float* gamma
     return 0;
 }
 
+// ---- one Linear layer on token rows, forward and backward (gemm.h: gemm_rows_*) ----
+// the limits of the three calls: what the tile loads can read (16-byte pieces along N and K, 32-bit byte offsets into an operand)
+static int lrows_check(const char* who, long M, int N, int K, int rps) {
+    REQUIRE(M >= 1 && N >= 4 && K >= 4 && N % 4 == 0 && K % 4 == 0, "%s: M=%ld N=%d K=%d: M must be at least 1, N and K multiples of 4", who, M, N, K);
+    REQUIRE(rps >= 1 && M % rps == 0, "%s: M=%ld is no multiple of rows_per_sample=%d", who, M, rps);
+    REQUIRE(M < (1L << 31) && M * std::max(N, K) < (1L << 30) && (long)N * K < (1L << 30),
+            "%s: M*max(N, K) = %ld and N*K = %ld must be below 2^30", who, M * std::max(N, K), (long)N * K);
+    return 0;
+}
+// workspace of cffm_linear_rows_bwd (floats, every carve 256-byte aligned): the dw slabs [ksplit][N][K] (ksplit > 1) | the db records [nrec][N]
+struct LrowsWs { RowsBwdPlan P; long slab, rec, total; };
+static LrowsWs lrows_layout(long M, int N, int K, int with_db) {
+    LrowsWs W;
+    W.P = gemm_rows_bwd_plan(M, N, K);
+    long p = 0;
+    W.slab = p; p += W.P.ksplit > 1 ? up((long)W.P.ksplit * N * K) : 0;
+    W.rec = p; p += with_db ? up((long)W.P.nrec * N) : 0;
+    W.total = p;
+    return W;
+}
+int cffm_linear_rows_fwd(const float* x, const float* w, const float* b, const float* residual, const float* scale, float* y, long M, int N,
+                         int K, int rows_per_sample, void* stream) {
+    TRY(lrows_check("linear_rows_fwd", M, N, K, rows_per_sample));
+    REQUIRE(aligned16(x) && aligned16(w) && aligned16(y) && (uintptr_t)b % 16 == 0 && (uintptr_t)residual % 16 == 0 && (uintptr_t)scale % 4 == 0,
+            "linear_rows_fwd: x / w / y must be non-null and 16-byte aligned, b / residual 16-byte aligned or null, scale 4-byte aligned or null");
+    REQUIRE((const float*)y != x && (const float*)y != w && (const float*)y != b && (const float*)y != residual && (const float*)y != scale,
+            "linear_rows_fwd: y must not alias an input (x, w, b, residual, scale)");
+    REQUIRE(gemm_rows_fwd(x, w, b, residual, scale, y, M, N, K, rows_per_sample, (hipStream_t)stream) == 0, "linear_rows_fwd: launch refused");
+    CHECK_LAUNCH("linear_rows_fwd");
+    return 0;
+}
+long cffm_linear_rows_bwd_workspace_bytes(long M, int N, int K, int rows_per_sample, int with_dx, int with_db) {
+    (void)with_dx;      // the input gradient needs no workspace
+    if (lrows_check("linear_rows_bwd_workspace_bytes", M, N, K, rows_per_sample)) return -1;
+    return lrows_layout(M, N, K, with_db != 0).total * (long)sizeof(float);
+}
+int cffm_linear_rows_bwd(const float* dy, const float* x, const float* w, const float* scale, float* dx, float* dw, float* db, void* workspace,
+                         long M, int N, int K, int rows_per_sample, void* stream) {
+    TRY(lrows_check("linear_rows_bwd", M, N, K, rows_per_sample));
+    const LrowsWs W = lrows_layout(M, N, K, db != nullptr);
+    REQUIRE(aligned16(dy) && aligned16(x) && aligned16(w) && aligned16(dw) && (uintptr_t)dx % 16 == 0 && (uintptr_t)db % 16 == 0 &&
+            (uintptr_t)scale % 4 == 0 && (uintptr_t)workspace % 16 == 0 && (workspace || !W.total),
+            "linear_rows_bwd: dy / x / w / dw (and the workspace, unless its size is 0) must be non-null and 16-byte aligned, dx / db 16-byte "
+            "aligned or null, scale 4-byte aligned or null");
+    const float* const ins[4] = {dy, x, w, scale};
+    float* const outs[3] = {dx, dw, db};
+    for (int o = 0; o < 3; ++o) {
+        for (int i = 0; i < 4; ++i) REQUIRE(!outs[o] || (const float*)outs[o] != ins[i], "linear_rows_bwd: an output aliases an input");
+        for (int q = 0; q < o; ++q) REQUIRE(!outs[o] || outs[o] != outs[q], "linear_rows_bwd: two outputs alias");
+        REQUIRE(!outs[o] || !workspace || (void*)outs[o] != workspace, "linear_rows_bwd: an output aliases the workspace");
+    }
+    // (every refusal before the first launch: with dx enqueued, a refused dw would break "nothing is enqueued")
+    REQUIRE(gemm_rows_bwd_grant(M, N, K, scale != nullptr, dx != nullptr, W.P), "linear_rows_bwd: LDS grant refused");
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = (float*)workspace;
+    if (dx) REQUIRE(gemm_rows_dx(dy, w, scale, dx, M, N, K, rows_per_sample, st) == 0, "linear_rows_bwd: launch refused (dx)");
+    REQUIRE(gemm_rows_dw(dy, x, scale, dw, M, N, K, rows_per_sample, W.P, W.P.ksplit > 1 ? ws + W.slab : nullptr, st) == 0,
+            "linear_rows_bwd: launch refused (dw)");
+    if (db) gemm_rows_db(dy, scale, db, M, N, rows_per_sample, W.P, ws + W.rec, st);
+    CHECK_LAUNCH("linear_rows_bwd");
+    return 0;
+}
+
 long cffm_mit_infer_ws_floats(const cffm_mit_stage* stages, int n) {
     long need = 0;
     return mit_infer_check("mit_infer_ws_floats", stages, n, nullptr, nullptr, &need) ? -1 : need;

@@ -26,16 +26,18 @@ static bool lds_grant(int& have, std::initializer_list<LdsAsk> asks) {
 float* lib_scratch(size_t nfloats);   // cffm_hip.hip: library-owned device scratch (grows on demand)
 __global__ void k_sum_splits(const float* __restrict__ part, int nsplit, long n, float* __restrict__ out);
 
-template <bool A_T, bool B_T, int EPI = 0, bool A_PRE = false, bool B_PRE = false>
+// rscale / rps: the per-sample factors of EPI 8 and of A_PRE == 3 (gemm_kernels.h); slabs: where the split-K partial outputs go
+// ([ksplit][M][ldc] floats, the caller's) instead of the library scratch, which allocates on demand
+template <bool A_T, bool B_T, int EPI = 0, int A_PRE = 0, int B_PRE = 0>
 static int gemm_split_launch(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, int ksplit,
                              hipStream_t st, const float* bias = nullptr, float* aux = nullptr, int prefer_big = 0,
-                             float* aux2 = nullptr) {
+                             float* aux2 = nullptr, const float* rscale = nullptr, int rps = 1, float* slabs = nullptr) {
     int klen = ((K + ksplit - 1) / ksplit + 63) / 64 * 64;
     ksplit = (K + klen - 1) / klen;
     float* out = C;
     const long split_stride = (long)M * ldc;
     if (ksplit > 1) {
-        out = lib_scratch((size_t)ksplit * split_stride);
+        out = slabs ? slabs : lib_scratch((size_t)ksplit * split_stride);
         if (!out) return -1;
     }
     const long b128 = (long)((N + 127) / 128) * ((M + 127) / 128) * ksplit;
@@ -45,7 +47,7 @@ static int gemm_split_launch(const float* A, const float* B, float* C, int M, in
         !lds_grant(lds_have, {{(const void*)k_gemm_split<BM_, BN_, BK_, A_T, B_T, EPI, PF_, A_PRE, B_PRE>, GEMM_LDS(BM_, BN_, BK_)}})) return -1; \
     CFFM_LAUNCH((k_gemm_split<BM_, BN_, BK_, A_T, B_T, EPI, PF_, A_PRE, B_PRE>), ((unsigned)(((N + BN_ - 1) / BN_) * ((M + BM_ - 1) / BM_) * ksplit)), (256), \
                 GEMM_LDS(BM_, BN_, BK_), st, A, \
-                B, out, M, N, K, lda, ldb, ldc, klen, split_stride, bias, aux, aux2); } while (0)
+                B, out, M, N, K, lda, ldb, ldc, klen, split_stride, bias, aux, aux2, rscale, rps); } while (0)
     // measured on MI355X (scripts/gemm_bench.py, CFFM-B1 shapes): 128x128 wins when it already gives >= 384 workgroups
     // (qkv / fc1 forward, the 1024-wide input gradient), 64x64 otherwise; prefetch depth beyond the listed one is neutral.
     if (b128 >= 384 || prefer_big) {
@@ -57,6 +59,17 @@ static int gemm_split_launch(const float* A, const float* B, float* C, int M, in
         CFFM_LAUNCH(k_sum_splits, ((unsigned)((n4 + 63) / 64)), (256), 0, st, (const float*)out, ksplit, split_stride, C);
     }
     return 0;
+}
+// What gemm_split_launch<...> of the same sizes would have to be granted, asked for without launching: a call with several launches
+// settles every refusal before its first one.  (The launch asks again; a grant that was given once is given again.)
+template <bool A_T, bool B_T, int EPI, int A_PRE, int B_PRE>
+static bool gemm_split_grant(int M, int N, int K, int ksplit, int prefer_big) {
+    const int klen = ((K + ksplit - 1) / ksplit + 63) / 64 * 64;
+    ksplit = (K + klen - 1) / klen;
+    const long b128 = (long)((N + 127) / 128) * ((M + 127) / 128) * ksplit;
+    if (!(b128 >= 384 || prefer_big) || GEMM_LDS(128, 128, 32) <= 65536) return true;      // (the 64 x 64 body stays under 64 KiB)
+    static int lds_have = 0;
+    return lds_grant(lds_have, {{(const void*)k_gemm_split<128, 128, 32, A_T, B_T, EPI, 1, A_PRE, B_PRE>, GEMM_LDS(128, 128, 32)}});
 }
 // y[M,N] = x[M,K] w[N,K]^T
 static int gemm_nt_split(const float* x, const float* w, float* y, long M, int N, int K, hipStream_t st) {
@@ -82,6 +95,57 @@ static int gemm_tn_split(const float* dy, const float* x, float* dw, long M, int
     if (ksplit > maxsplit) ksplit = maxsplit;
     if (ksplit < 1) ksplit = 1;
     return gemm_split_launch<true, true, 0, DY_PRE, X_PRE>(dy, x, dw, N, K, (int)M, N, K, K, ksplit, st, nullptr, nullptr, big);
+}
+
+// ---- one Linear layer on token rows with a per-sample factor (cffm_linear_rows_*): row m belongs to sample m / rps -------------------
+// y[m] = r[m] + s[m / rps] (x[m] w^T + b); b, r, s may each be null
+static int gemm_rows_fwd(const float* x, const float* w, const float* b, const float* r, const float* s, float* y, long M, int N, int K, int rps,
+                         hipStream_t st) {
+    return gemm_split_launch<false, false, 8>(x, w, y, (int)M, N, K, K, K, N, 1, st, b, const_cast<float*>(r), 0, nullptr, s, rps);
+}
+// dx[m] = s[m / rps] (dy[m] w): the factor is per output row, so it is the same epilogue
+static int gemm_rows_dx(const float* dy, const float* w, const float* s, float* dx, long M, int N, int K, int rps, hipStream_t st) {
+    return gemm_split_launch<false, true, 8>(dy, w, dx, (int)M, K, N, N, K, K, 1, st, nullptr, nullptr, 0, nullptr, s, rps);
+}
+// The plan of the weight gradient and of the bias gradient's records: gemm_tn_split's tile choice and split count (it follows from
+// (M, N, K) alone), RS rows per db record such that the column-sum grid has about 1024 workgroups, at most 64 records of at least 64 rows.
+struct RowsBwdPlan { int big, ksplit, nrec, RS; };
+static RowsBwdPlan gemm_rows_bwd_plan(long M, int N, int K) {
+    RowsBwdPlan P;
+    P.big = (N > 96 && K >= 128);
+    const int tiles = P.big ? ((N + 127) / 128) * ((K + 127) / 128) : ((N + 63) / 64) * ((K + 63) / 64);
+    int ksplit = (320 + tiles - 1) / tiles;
+    const int maxsplit = (int)((M + 127) / 128);
+    if (ksplit > maxsplit) ksplit = maxsplit;
+    if (ksplit < 1) ksplit = 1;
+    const int klen = (int)(((M + ksplit - 1) / ksplit + 63) / 64 * 64);      // (gemm_split_launch's rounding)
+    P.ksplit = (int)((M + klen - 1) / klen);
+    const int ncb = (N + 63) / 64;
+    long n = (1024 + ncb - 1) / ncb;
+    if (n > 64) n = 64;
+    if (n > (M + 63) / 64) n = (M + 63) / 64;
+    if (n < 1) n = 1;
+    P.RS = (int)(((M + n - 1) / n + 15) / 16 * 16);
+    P.nrec = (int)((M + P.RS - 1) / P.RS);
+    return P;
+}
+// everything the launches of one backward call can be refused for, before the first of them
+static bool gemm_rows_bwd_grant(long M, int N, int K, bool scaled, bool with_dx, const RowsBwdPlan& P) {
+    if (with_dx && !gemm_split_grant<false, true, 8, 0, 0>((int)M, K, N, 1, 0)) return false;
+    return scaled ? gemm_split_grant<true, true, 0, 3, 0>(N, K, (int)M, P.ksplit, P.big) : gemm_split_grant<true, true, 0, 0, 0>(N, K, (int)M, P.ksplit, P.big);
+}
+// dw[N,K] = (s dy)^T x with s applied while the dy tile is staged (s == null: the plain form); slabs: P.ksplit * N * K floats when
+// P.ksplit > 1
+static int gemm_rows_dw(const float* dy, const float* x, const float* s, float* dw, long M, int N, int K, int rps, const RowsBwdPlan& P,
+                        float* slabs, hipStream_t st) {
+    if (P.ksplit > 1 && !slabs) return -1;
+    if (s) return gemm_split_launch<true, true, 0, 3, 0>(dy, x, dw, N, K, (int)M, N, K, K, P.ksplit, st, nullptr, nullptr, P.big, nullptr, s, rps, slabs);
+    return gemm_split_launch<true, true, 0, 0, 0>(dy, x, dw, N, K, (int)M, N, K, K, P.ksplit, st, nullptr, nullptr, P.big, nullptr, nullptr, 1, slabs);
+}
+// db[N] = the column sum of s dy: P.nrec records [N] in `rec`, added in record order
+static void gemm_rows_db(const float* dy, const float* s, float* db, long M, int N, int rps, const RowsBwdPlan& P, float* rec, hipStream_t st) {
+    CFFM_LAUNCH(k_rowscale_colsum, ((unsigned)((N + 63) / 64), (unsigned)P.nrec), (256), 0, st, dy, s, rec, (int)M, N, rps, P.RS);
+    CFFM_LAUNCH(k_sum_splits, ((unsigned)((N / 4 + 63) / 64)), (256), 0, st, (const float*)rec, P.nrec, (long)N, db);
 }
 
 // ---- grouped weight gradients: dw_p[N_p,K_p] = dy_p[M_p,N_p]^T x_p[M_p,K_p], p < n <= 4, one launch (k_gemm_group_tt) --------

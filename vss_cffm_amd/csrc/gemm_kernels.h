@@ -145,9 +145,12 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // `pre`: 0 plain fp32 (split here) | 1 the registers hold split-4 data: no arithmetic | 2 (row-contiguous operands only) the operand
 // is gelu(stored + bias): the weight gradient of fc2 reads the saved fc1 product `hraw` and re-applies bias + GELU while it stages the
 // tile, so the forward never writes the activation (29.5 MB per block at CFFM-B1 size) -- bit-identical to what it would have stored
-template <int ROWS, bool TR, int BK>
+// | 3 (row-contiguous operands only, compile-time only: SCL) the operand is s[k-row's sample] * stored: the weight gradient of linear_rows
+// scales dy along the contraction while it stages the tile, so g = s dy never exists in memory; `sc` = the factor of each register's k-row
+// (ScaleRegs below).  SCL is a template argument of its own so that a body whose `pre` is a run-time value gains no branch.
+template <int ROWS, bool TR, int BK, bool SCL = false>
 __device__ __forceinline__ void tile_store(const TileRegs<ROWS, BK>& r, bf16* __restrict__ hi, bf16* __restrict__ lo, int tid,
-                                           int pre = 0, f32x4 bias4 = (f32x4){0.f, 0.f, 0.f, 0.f}) {
+                                           int pre = 0, f32x4 bias4 = (f32x4){0.f, 0.f, 0.f, 0.f}, const float* sc = nullptr) {
     if (!TR) {
 #pragma unroll
         for (int it = 0; it < ROWS * BK / 1024; ++it) {
@@ -168,7 +171,8 @@ __device__ __forceinline__ void tile_store(const TileRegs<ROWS, BK>& r, bf16* __
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 bf16x4 hh, ll;
-                if (pre == 1) unsplit4(r.v[2 * it + h], hh, ll);
+                if (SCL) split4(r.v[2 * it + h] * sc[2 * it + h], hh, ll);
+                else if (pre == 1) unsplit4(r.v[2 * it + h], hh, ll);
                 else if (pre == 2) {
                     f32x4 a;
                     for (int e = 0; e < 4; ++e) a[e] = gelu_erf(r.v[2 * it + h][e] + bias4[e]);
@@ -181,6 +185,39 @@ __device__ __forceinline__ void tile_store(const TileRegs<ROWS, BK>& r, bf16* __
         }
     }
 }
+
+// The per-sample factors of a row-contiguous operand tile (pre == 3): register v[2 it + h] of TileRegs holds k-row k0 + 2 kp + h, whose
+// sample is k / rps.  A thread's k-rows advance by BK from one tile load to the next, in tile order, so each slot keeps (sample, remainder)
+// and steps them by (BK / rps, BK % rps) with one carry: two divisions per slot when the kernel starts, none in the K-loop.  The factor is
+// loaded when the tile is (its latency hides with the tile's) and used when the tile is stored; a k-row past the matrix reads the last
+// sample's factor and multiplies zeros.
+template <int ROWS, int BK>
+struct ScaleRegs { float s[ROWS * BK / 1024]; };
+template <int ROWS, int BK>
+struct ScaleWalk {
+    int smp[ROWS * BK / 1024], rem[ROWS * BK / 1024], qs, rs, rps, last;
+    __device__ __forceinline__ void init(int kbeg, int tid, int rps_, int nrows) {
+        rps = rps_; qs = BK / rps_; rs = BK - qs * rps_; last = nrows / rps_ - 1;
+#pragma unroll
+        for (int it = 0; it < ROWS * BK / 2048; ++it)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int k = kbeg + 2 * ((tid + 256 * it) / (ROWS / 4)) + h;
+                smp[2 * it + h] = k / rps_;
+                rem[2 * it + h] = k - smp[2 * it + h] * rps_;
+            }
+    }
+    // the factors of the tile the walk stands at, then one tile further
+    __device__ __forceinline__ void load(ScaleRegs<ROWS, BK>& r, const float* __restrict__ scale) {
+#pragma unroll
+        for (int i = 0; i < ROWS * BK / 1024; ++i) {
+            r.s[i] = scale[smp[i] < last ? smp[i] : last];
+            smp[i] += qs;
+            rem[i] += rs;
+            if (rem[i] >= rps) { rem[i] -= rps; ++smp[i]; }
+        }
+    }
+};
 
 // one MFMA operand fragment (8 k-slots of row `row`) out of an LDS image
 template <int ROWS, bool TR, int BK>
@@ -221,6 +258,8 @@ __device__ __forceinline__ bf16x8 frag_read(const bf16* __restrict__ img, int ro
 //        values the attention kernels used to form from the fp32 product, stored once at half the bytes
 //      5 as 1 with aux written in split-4 storage | 6 GELU backward: C = product * gelu'(aux + bias), aux2 = column-sum records
 //        of C (one per 32-row slab of a wave) | 7 as 6 with C in split-4 storage
+//      8 token rows (linear_rows): C[m] = aux[m] + s[m / rps] * (raw + bias), s = rscale; a null aux, rscale or bias drops its term.  A
+//        row whose s is 0 gets aux's bits (or zeros).  The input gradient of the same layer is this epilogue on the <F,T> form, no aux.
 // XCD-aware placement (speed only): workgroup b runs on XCD b % 8, each XCD with its own 4 MiB L2.  The 1-D grid is
 // re-numbered so that every XCD owns a CONTIGUOUS run of (k-slice, row panel, column tile) triples, column tile
 // fastest: the tiles that share an A row panel / a k-slice then hit the same L2 instead of eight different ones.
@@ -234,12 +273,17 @@ __device__ __forceinline__ int xcd_linear_id() {
 // a_pre_rt / b_pre_rt at run time.  A run-time form puts a branch into every tile_store, which cuts the fast K-loop into basic blocks
 // (34 per K-step in the 128 x 128 <T,T> body, 2-3 times the instructions of a body with constant forms) and keeps the scheduling hints
 // from reaching across them.  With PF = 1 the split is a phase behind the MFMAs either way: it has to wait for the one tile in flight.
+// A_PRE == 3: A = rscale[k-row / rps] * stored (tile_store's scaled form; <T,.> only, compile time only).
 template <int BM, int BN, int BK, bool A_T, bool B_T, int EPI, int PF, int A_PRE = -1, int B_PRE = -1>
 __device__ __forceinline__ void gemm_tile(char* smem, const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ C,
                                           int M, int N, int K, int lda, int ldb, int ldc, int klen, long split_stride,
                                           const float* __restrict__ bias, float* __restrict__ aux, int bx, int by, int bz,
                                           bool a_pre_rt = false, int b_pre_rt = 0, float* __restrict__ aux2 = nullptr,
-                                          const float* __restrict__ b_bias = nullptr /* b_pre == 2: bias of the on-load GELU */) {
+                                          const float* __restrict__ b_bias = nullptr /* b_pre == 2: bias of the on-load GELU */,
+                                          const float* __restrict__ rscale = nullptr /* EPI 8 / A_PRE 3: one factor per sample */,
+                                          int rps = 1 /* rows per sample */) {
+    constexpr bool A_SCL = A_PRE == 3;
+    static_assert(!A_SCL || A_T, "the scaled form exists for a row-contiguous A only");
     const int a_pre = A_PRE >= 0 ? A_PRE : (int)a_pre_rt, b_pre = B_PRE >= 0 ? B_PRE : b_pre_rt;
     bf16* Ah = (bf16*)smem;
     bf16* Al = Ah + GEMM_IMG(BM, BK);
@@ -267,12 +311,16 @@ __device__ __forceinline__ void gemm_tile(char* smem, const float* __restrict__ 
     TileRegs<BM, BK> ra[PF];
     TileRegs<BN, BK> rb[PF];
     const int NKT = (kend - kbeg + BK - 1) / BK;
+    ScaleRegs<BM, BK> sa[PF];      // A_SCL only: the factors that go with ra[u]
+    ScaleWalk<BM, BK> wa;
+    if (A_SCL) { wa.init(kbeg, tid, rps, K); wa.load(sa[0], rscale); }
     tile_load<BM, A_T, BK>(ra[0], A, lda, m0, M, kbeg, kend, tid);
     tile_load<BN, B_T, BK>(rb[0], B, ldb, n0, N, kbeg, kend, tid);
-    tile_store<BM, A_T, BK>(ra[0], Ah, Al, tid, a_pre);
+    tile_store<BM, A_T, BK, A_SCL>(ra[0], Ah, Al, tid, a_pre, (f32x4){0.f, 0.f, 0.f, 0.f}, sa[0].s);
     tile_store<BN, B_T, BK>(rb[0], Bh, Bl, tid, b_pre, bb4);
 #pragma unroll
     for (int u = 0; u < PF; ++u) {   // tile 1+u -> register set u (past kend -> zeros, never used)
+        if (A_SCL) wa.load(sa[u], rscale);
         tile_load<BM, A_T, BK>(ra[u], A, lda, m0, M, kbeg + (1 + u) * BK, kend, tid);
         tile_load<BN, B_T, BK>(rb[u], B, ldb, n0, N, kbeg + (1 + u) * BK, kend, tid);
     }
@@ -310,8 +358,9 @@ __device__ __forceinline__ void gemm_tile(char* smem, const float* __restrict__ 
                         acc[i][j] = mfma16x16x32_bf16(ah, bh[j], acc[i][j]);
                     }
                 }
-                tile_store<BM, A_T, BK>(ra[u], Ah + nxt, Al + nxt, tid, a_pre);
+                tile_store<BM, A_T, BK, A_SCL>(ra[u], Ah + nxt, Al + nxt, tid, a_pre, (f32x4){0.f, 0.f, 0.f, 0.f}, sa[u].s);
                 tile_store<BN, B_T, BK>(rb[u], Bh + nxt, Bl + nxt, tid, b_pre, bb4);
+                if (A_SCL) wa.load(sa[u], rscale);
                 tile_load_fast<BM, A_T, BK>(ra[u], rsa, va, sa0 + (t + 1 + PF) * dsa, lda4);
                 tile_load_fast<BN, B_T, BK>(rb[u], rsb, vb, sb0 + (t + 1 + PF) * dsb, ldb4);
                 GEMM_INTERLEAVE(3 * MT * NT);
@@ -347,10 +396,11 @@ __device__ __forceinline__ void gemm_tile(char* smem, const float* __restrict__ 
                     }
                 }
                 if (t + 1 < NKT) {
-                    tile_store<BM, A_T, BK>(ra[u], Ah + nxt, Al + nxt, tid, a_pre);
+                    tile_store<BM, A_T, BK, A_SCL>(ra[u], Ah + nxt, Al + nxt, tid, a_pre, (f32x4){0.f, 0.f, 0.f, 0.f}, sa[u].s);
                     tile_store<BN, B_T, BK>(rb[u], Bh + nxt, Bl + nxt, tid, b_pre, bb4);
                 }
                 if (t + 1 + PF < NKT) {
+                    if (A_SCL) wa.load(sa[u], rscale);
                     tile_load<BM, A_T, BK>(ra[u], A, lda, m0, M, kbeg + (t + 1 + PF) * BK, kend, tid);
                     tile_load<BN, B_T, BK>(rb[u], B, ldb, n0, N, kbeg + (t + 1 + PF) * BK, kend, tid);
                 }
@@ -411,6 +461,16 @@ __device__ __forceinline__ void gemm_tile(char* smem, const float* __restrict__ 
                 *(f32x4*)dst = *(const f32x4*)(aux + (long)row * ldc + col) + v + bv;
                 continue;
             }
+            if (EPI == 8 && col + 3 < N) {          // N % 4 == 0 (checked by the callers)
+                const float s = rscale ? rscale[row / rps] : 1.f;
+                f32x4 o = s * (v + bv);
+                if (aux) {
+                    const f32x4 r4 = *(const f32x4*)(aux + (long)row * ldc + col);
+                    for (int e = 0; e < 4; ++e) o[e] = s == 0.f ? r4[e] : r4[e] + o[e];
+                } else if (s == 0.f) o = (f32x4){0.f, 0.f, 0.f, 0.f};
+                *(f32x4*)dst = o;
+                continue;
+            }
             v += bv;
             if (col + 3 < N) {
                 *(f32x4*)dst = v;
@@ -431,15 +491,52 @@ __device__ __forceinline__ void gemm_tile(char* smem, const float* __restrict__ 
     }
 }
 
-template <int BM, int BN, int BK, bool A_T, bool B_T, int EPI, int PF, bool A_PRE = false, bool B_PRE = false>
+template <int BM, int BN, int BK, bool A_T, bool B_T, int EPI, int PF, int A_PRE = 0, int B_PRE = 0>
 __global__ void __launch_bounds__(256) k_gemm_split(const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ C,
                                                      int M, int N, int K, int lda, int ldb, int ldc, int klen, long split_stride,
-                                                     const float* __restrict__ bias, float* __restrict__ aux, float* __restrict__ aux2) {
+                                                     const float* __restrict__ bias, float* __restrict__ aux, float* __restrict__ aux2,
+                                                     const float* __restrict__ rscale, int rps) {
     CFFM_DYN_SMEM(smem);
     const int lin = xcd_linear_id();
     const int ntn = (N + BN - 1) / BN, ntm = (M + BM - 1) / BM;
     gemm_tile<BM, BN, BK, A_T, B_T, EPI, PF, A_PRE, B_PRE>(smem, A, B, C, M, N, K, lda, ldb, ldc, klen, split_stride, bias, aux, lin % ntn,
-                                                           (lin / ntn) % ntm, lin / (ntn * ntm), A_PRE, B_PRE, aux2);
+                                                           (lin / ntn) % ntm, lin / (ntn * ntm), A_PRE != 0, B_PRE, aux2, nullptr, rscale, rps);
+}
+
+// The bias gradient of linear_rows as records: rec[slab][N] = the sum over the slab's RS rows (RS a multiple of 16) of
+// s[row / rps] * dy[row][:], fp32, in a fixed order; k_sum_splits adds the records in slab order.  A pass of its own over dy, not a part of
+// the weight-gradient kernel: that kernel stages every dy tile once per 64- or 128-wide column tile of dw, so a sum taken there is either
+// repeated K / BN times or sits behind a workgroup-uniform branch inside the K-loop body, which the comment at gemm_tile rules out; and its
+// 128 x 128 body has no registers to spare.  Reading dy once more costs M N 4 bytes (29 MB, under 4 us at 8 TB/s, for a stage-1 layer of
+// mit_b1 at 480 x 480).  grid (ceil(N / 64), nslab), 256 threads = 16 column chunks of 16 bytes x 16 rows; the sample of a thread's row
+// is stepped like ScaleWalk's.  scale may be null.
+__global__ void __launch_bounds__(256) k_rowscale_colsum(const float* __restrict__ dy, const float* __restrict__ scale, float* __restrict__ rec,
+                                                          int M, int N, int rps, int RS) {
+    __shared__ f32x4 red[16][16];
+    const int cx = threadIdx.x & 15, ry = threadIdx.x >> 4;
+    const int col = blockIdx.x * 64 + 4 * cx;
+    const int r0 = blockIdx.y * RS, r1 = (M - r0 < RS) ? M : r0 + RS;
+    f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (col < N) {          // N % 4 == 0
+        int row = r0 + ry;
+        int smp = row / rps, rem = row - smp * rps;
+        const int qs = 16 / rps, rs = 16 - qs * rps;
+#pragma unroll 4
+        for (; row < r1; row += 16) {
+            const float s = scale ? scale[smp] : 1.f;
+            acc += s * *(const f32x4*)(dy + (long)row * N + col);
+            smp += qs;
+            rem += rs;
+            if (rem >= rps) { rem -= rps; ++smp; }
+        }
+    }
+    red[ry][cx] = acc;
+    __syncthreads();
+    if (ry == 0 && col < N) {
+        f32x4 t = red[0][cx];
+        for (int i = 1; i < 16; ++i) t += red[i][cx];
+        *(f32x4*)(rec + (long)blockIdx.y * N + col) = t;
+    }
 }
 
 // Up to GEMM_GROUP_MAX independent weight-gradient GEMMs (dw = dy^T x, <T,T>, 128x128 tiles) in ONE launch.  The four of a

@@ -1683,6 +1683,91 @@ def layer_norm_rows_nchw(x, weight, bias, H, W, eps=1e-5):
     return _LayerNormFn.apply(x, weight, bias, _LN_TO_NCHW, (x.shape[0], x.shape[2], int(H), int(W)), float(eps))
 
 
+# ---------------------------------------------------------------------------------------------- one Linear layer on token rows, differentiable
+def linear_rows_supported(in_features, out_features, rows):
+    """whether a Linear layer in_features -> out_features on `rows` token rows is inside the limits of cffm_linear_rows_fwd / _bwd"""
+    k, n, m = int(in_features), int(out_features), int(rows)
+    return k >= 4 and n >= 4 and k % 4 == 0 and n % 4 == 0 and m >= 1 and m * max(n, k) < 2 ** 30 and n * k < 2 ** 30
+
+
+class _LinearRowsFn(torch.autograd.Function):
+    """y = residual + scale[sample] * (x w^T + bias) on token rows and its backward (csrc/gemm_kernels.h: the bf16-split GEMMs with the
+    token-row epilogue and the scaled staging of dy).  Saved: x, the weight and the scale -- nothing else; the backward's workspace (the dw
+    slabs and the db records) lives only inside it.  The residual's gradient is the incoming gradient itself, not a copy."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, scale, rps):
+        lib = _lib.get()
+        # every input contiguous BEFORE the stream is looked up or anything is enqueued (as _LayerNormFn.forward)
+        x, weight = _sra_operand(x), _sra_operand(weight)
+        bias, residual, scale = (None if t is None else _sra_operand(t) for t in (bias, residual, scale))
+        n, k = weight.shape
+        m = x.numel() // k
+        y = torch.empty(tuple(x.shape[:-1]) + (n,), dtype=torch.float32, device=x.device)
+        _lib.check(lib.cffm_linear_rows_fwd(_ptr(x), _ptr(weight), _ptr(bias), _ptr(residual), _ptr(scale), _ptr(y), m, n, k, rps, _stream(x)), lib)
+        ctx.save_for_backward(x, weight, scale)
+        ctx.dims = (m, n, k, rps)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        lib = _lib.get()
+        x, weight, scale = ctx.saved_tensors
+        m, n, k, rps = ctx.dims
+        want_dx, want_dw, want_db, want_dr = (bool(v) for v in ctx.needs_input_grad[:4])
+        dx = dw = db = None
+        if want_dx or want_dw or want_db:
+            dy = _sra_operand(dout)
+            dx = torch.empty_like(x) if want_dx else None
+            dw = torch.empty_like(weight)                   # (the call always forms dw: a layer with a frozen weight is not the hot path)
+            db = torch.empty(n, dtype=torch.float32, device=x.device) if want_db else None
+            nbytes = lib.cffm_linear_rows_bwd_workspace_bytes(m, n, k, rps, int(want_dx), int(want_db))
+            if nbytes < 0:
+                raise _lib.CffmError('libcffm_hip: %s' % lib.cffm_last_error().decode())
+            ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device) if nbytes else None
+            _lib.check(lib.cffm_linear_rows_bwd(_ptr(dy), _ptr(x), _ptr(weight), _ptr(scale), _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), m, n, k, rps,
+                                                _stream(x)), lib)
+        return dx, (dw if want_dw else None), db, (dout if want_dr else None), None, None
+
+
+def linear_rows(x, weight, bias=None, residual=None, scale=None):
+    """``residual + scale[sample] * F.linear(x, weight, bias)`` of fp32 token rows x [B, N, Cin] or [M, Cin] -> [..., Cout], one library call
+    per direction (``cffm_linear_rows_fwd`` / ``cffm_linear_rows_bwd``): the three-pass bf16-split GEMM of the inference stage call with the
+    residual and the per-sample factor in its epilogue.  bias [Cout], residual [..., Cout] and scale [B] (fp32; what DropPath multiplies a
+    sample's branch with: 0 or 1 / keep) may each be None.  A sample whose scale is 0 leaves with the bits of its residual.  Differentiable
+    in x, weight, bias and residual (not in scale); x gets no gradient formed when it needs none; every gradient is bit-reproducible and the
+    residual's gradient is the incoming one, uncopied.  Cin and Cout multiples of 4, rows * max(Cin, Cout) below 2^30.  Launches on the
+    current stream."""
+    what = 'linear_rows'
+    for t, name in ((x, 'x'), (weight, 'weight'), (bias, 'bias'), (residual, 'residual'), (scale, 'scale')):
+        if t is None and name not in ('x', 'weight'):
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise _lib.CffmError('%s: %s must be a tensor' % (what, name))
+        _require_device(t, '%s %s' % (what, name))
+        if t.device != x.device:
+            raise _lib.CffmError('%s: %s is on %s, x on %s' % (what, name, t.device, x.device))
+    if x.dim() not in (2, 3) or weight.dim() != 2 or x.shape[-1] != weight.shape[1] or x.numel() == 0:
+        raise _lib.CffmError('%s: x must be a non-empty [B, N, Cin] or [M, Cin] tensor and weight [Cout, Cin]' % what)
+    n, k = weight.shape
+    m = x.numel() // k
+    if not linear_rows_supported(k, n, m):
+        raise _lib.CffmError('%s: Cin=%d and Cout=%d must be multiples of 4 and rows * max(Cin, Cout) = %d below 2^30' % (what, k, n, m * max(n, k)))
+    if bias is not None and tuple(bias.shape) != (n,):
+        raise _lib.CffmError('%s: bias must be a [%d] tensor' % (what, n))
+    if residual is not None and tuple(residual.shape) != tuple(x.shape[:-1]) + (n,):
+        raise _lib.CffmError('%s: residual must be a %s tensor' % (what, tuple(x.shape[:-1]) + (n,)))
+    rps = m
+    if scale is not None:
+        samples = scale.numel()
+        if scale.dim() != 1 or samples == 0 or (x.dim() == 3 and samples != x.shape[0]) or m % samples:
+            raise _lib.CffmError('%s: scale must be a [B] tensor, B = x.shape[0] for a [B, N, Cin] x and a divisor of M for an [M, Cin] x' % what)
+        rps = m // samples
+        scale = scale.detach()
+    return _LinearRowsFn.apply(x, weight, bias, residual, scale, rps)
+
+
 MIT_HEAD_SIZES = (32, 64)
 MIT_SR_RATIOS = (1, 2, 4, 8)
 
