@@ -780,6 +780,63 @@ long cffm_mit_infer_ws_floats(const cffm_mit_stage* stages /* host [n] */, int n
 int cffm_mit_infer(const cffm_mit_stage* stages /* host [n] */, int n, const float* x_nchw, float* const* outs /* host [n] */, float* ws,
                    void* stream);
 
+/* ---- added under ABI 13, additive: LayerNorm backward of token rows with the neighbouring adds fused in (csrc/mitln_kernels.h) ----
+ *   d  = dout_a + dout_b            one rounded fp32 add per element; dout_b == NULL: d = dout_a
+ *   v  = LN-backward(x, gamma, d)   cffm_ln_rows_bwd's arithmetic, to the bit
+ *   dx = dres + v                   one fp32 add rounded on its own, never fused with the multiply that makes v; dres == NULL: dx = v
+ * dgamma / dbeta are those of d.  The result has the bits of cffm_ln_rows_bwd(x, gamma, dout_a + dout_b) followed by dres + dx with the two
+ * adds done as separate fp32 passes, and with dout_b == dres == NULL the bits of cffm_ln_rows_bwd itself.  These are the two passes
+ * autograd adds around a MiT block's LayerNorms: d(norm1 out) = dx_q + dx_sr and dx1 = dy + LN2-backward.  dx == dres (in place) is allowed: a
+ * lane reads its own elements before it writes them; dx equal to x, dout_a or dout_b is refused.  ws: cffm_ln_bwd_workspace_bytes(M, C, 1).
+ * Limits and errors as cffm_ln_rows_bwd (nothing is enqueued, every output stays as it is); dout_b / dres 16-byte aligned or NULL. */
+int cffm_ln_rows_bwd_add(const float* x, const float* gamma, const float* dout_a, const float* dout_b /* NULL ok */,
+                         const float* dres /* NULL ok */, float* dx, float* dgamma, float* dbeta, void* ws, long M, int C, float eps,
+                         void* stream);
+
+/* ---- added under ABI 13, additive: the blocks of one MiT stage in a training pass, one call per direction ----
+ * x_rows [B][H*W][C] (what the patch embedding hands to the first block) -> y_rows (what the last block hands to the stage's norm), and
+ * back.  The patch embedding and the stage's norm are not part of the calls.  cffm_mit_stage_cfg is reused: B, H, W, C, heads, hidden,
+ * sr_ratio, depth, scale, eps_block and eps_sr are read, eps_embed / eps_out are not.  scales: host [depth] or NULL (no factor anywhere);
+ * each factor [B] or NULL: what DropPath multiplies a sample's attention / Mix-FFN branch with (0 or 1 / keep).
+ *   forward, per block    LN (norm1) | q | sr conv + LN (sr_ratio > 1, rows before the LN and their stats kept) | kv | attention (lse kept) |
+ *                         proj + bias + residual, scale_attn | LN (norm2) | fc1 | depthwise 3x3 + GELU | fc2 + bias + residual, scale_mlp.
+ *                         The kernels, launch plans and bits of cffm_ln_rows, cffm_linear_rows_fwd, cffm_sr_ln_fwd, cffm_sra_attn_fwd and
+ *                         cffm_dwconv_gelu_fwd chained in that order.
+ *   saved, per block      z1 | q | (sr_ratio > 1: sr rows before the LN | their stats | r) | kv | attention output | lse | x1 | z2 | h | a |
+ *                         the block's output (every block but the last), each carve 256-byte aligned.  Nothing is recomputed in the backward
+ *                         beyond what the single kernels already recompute.
+ *   backward, g = the gradient of a block's output, blocks in reverse
+ *                         fc2 (dw, db from scale_mlp g and a; da) | dwconv + GELU backward (dh, ddw, ddb) | fc1 (dw, db; dz2) |
+ *                         g1 = g + LN2-backward(x1, dz2) (cffm_ln_rows_bwd_add's kernel) | proj (dw, db from scale_attn g1 and ao; dao) |
+ *                         attention backward (dq, dkv) | kv (dw, db; dr) | sr backward (sr_ratio > 1: dz1b and the four sr gradients; else
+ *                         dz1b = dr) | q (dw, db; dz1a) | g' = g1 + LN1-backward(x, dz1a + dz1b): the previous block's g, dx_rows for block 0.
+ *                         Every gradient has the bits the single calls give when autograd chains them.
+ * grads: host [depth], the fields of cffm_mit_block_params as writable pointers, non-null exactly where the parameter is non-null; every
+ * gradient is formed (written, not accumulated).  ws: cffm_mit_blocks_train_bwd_ws_floats(cfg) floats for the backward -- the running
+ * gradients, the temporaries of one block, and ONE set of dw slabs / db records / LayerNorm records / attention, sr and dwconv workspaces,
+ * each the maximum over the call's uses; the forward keeps every intermediate in `saved` and needs no workspace
+ * (cffm_mit_blocks_train_fwd_ws_floats returns 0 and ws may be NULL).  Every byte of saved and ws that is read is written by the same
+ * forward + backward pair; neither needs initialising.  Everything is enqueued on `stream` alone: no allocation, no host round trip, no
+ * atomics, so both calls can be captured into a HIP graph.
+ * Limits: those of cffm_mit_stage_infer.  Errors (every check is settled before the first launch: nothing is enqueued, every output stays
+ * as it is; the three size queries return < 0): those limits, a null pointer where one is required, sr pointers at sr_ratio 1, a pointer
+ * that is not 16-byte aligned (a factor: 4-byte), a gradient pointer that is null where the parameter is not or the reverse, and any two of
+ * x_rows / y_rows / saved / ws (forward) or x_rows / saved / dy_rows / dx_rows / ws (backward) being equal. */
+typedef struct {
+    float *n1_g, *n1_b, *q_w, *q_b, *kv_w, *kv_b, *sr_w, *sr_b, *srn_g, *srn_b, *proj_w, *proj_b,
+          *n2_g, *n2_b, *fc1_w, *fc1_b, *dw_w, *dw_b, *fc2_w, *fc2_b;
+} cffm_mit_block_grad_ptrs;
+typedef struct { const float *scale_attn, *scale_mlp; } cffm_mit_block_scales;      /* [B] each, NULL = no DropPath factor */
+long cffm_mit_blocks_train_saved_floats(const cffm_mit_stage_cfg* c);      /* the whole call: depth blocks; < 0: refused */
+long cffm_mit_blocks_train_fwd_ws_floats(const cffm_mit_stage_cfg* c);
+long cffm_mit_blocks_train_bwd_ws_floats(const cffm_mit_stage_cfg* c);
+int cffm_mit_blocks_train_fwd(const cffm_mit_stage_cfg* c, const cffm_mit_block_params* blocks /* host [depth] */,
+                              const cffm_mit_block_scales* scales /* host [depth], NULL = none anywhere */,
+                              const float* x_rows /* [B][H*W][C] */, float* y_rows, float* saved, float* ws, void* stream);
+int cffm_mit_blocks_train_bwd(const cffm_mit_stage_cfg* c, const cffm_mit_block_params* blocks, const cffm_mit_block_scales* scales,
+                              const cffm_mit_block_grad_ptrs* grads /* host [depth] */, const float* x_rows, const float* saved,
+                              const float* dy_rows, float* dx_rows, float* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

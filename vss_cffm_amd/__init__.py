@@ -7,6 +7,7 @@ from .cluster import kmeans, kmeans_workspace  # noqa: F401,E402
 from .ops import dwconv_gelu, ln_rows, ln_rows_nchw, mit_infer, mit_stage_infer, nchw_ln_rows, patch_embed, predict, sr_reduce, sra_attention  # noqa: F401,E402
 from .ops import layer_norm_rows, layer_norm_rows_nchw, nchw_layer_norm_rows, overlap_patch_embed  # noqa: F401,E402
 from .ops import linear_rows, linear_rows_supported  # noqa: F401,E402
+from .ops import mit_blocks_train, mit_blocks_train_supported  # noqa: F401,E402
 from . import head  # noqa: F401,E402  (registers the three CFFM heads and CrossEntropyLoss)
 from .config import Config  # noqa: F401,E402
 from . import optim  # noqa: F401,E402

@@ -61,9 +61,14 @@ class GtcPtrs(C.Structure):
 
 
 class MitBlockPtrs(C.Structure):
-    """cffm_mit_block_params"""
+    """cffm_mit_block_params / cffm_mit_block_grad_ptrs (same field order)"""
     _fields_ = [(n, vp) for n in ('n1_g', 'n1_b', 'q_w', 'q_b', 'kv_w', 'kv_b', 'sr_w', 'sr_b', 'srn_g', 'srn_b', 'proj_w', 'proj_b',
                                   'n2_g', 'n2_b', 'fc1_w', 'fc1_b', 'dw_w', 'dw_b', 'fc2_w', 'fc2_b')]
+
+
+class MitBlockScales(C.Structure):
+    """cffm_mit_block_scales"""
+    _fields_ = [('scale_attn', vp), ('scale_mlp', vp)]
 
 
 class MitStageCfg(C.Structure):
@@ -81,6 +86,7 @@ class MitStage(C.Structure):
 GP, BP = C.POINTER(Geom), C.POINTER(BlockPtrs)
 MBP, MCP = C.POINTER(MitBlockPtrs), C.POINTER(MitStageCfg)
 MSP = C.POINTER(MitStage)
+MSC = C.POINTER(MitBlockScales)
 GTP = C.POINTER(GtcPtrs)
 CBP = C.POINTER(CffaBwdBlock)
 P4 = vp * 4
@@ -214,6 +220,12 @@ SIGNATURES = {
     'cffm_linear_rows_bwd': (ci, [vp] * 8 + [cl, ci, ci, ci, vp]),
     'cffm_mit_infer_ws_floats': (cl, [MSP, ci]),
     'cffm_mit_infer': (ci, [MSP, ci, vp, C.POINTER(vp), vp, vp]),
+    'cffm_ln_rows_bwd_add': (ci, [vp] * 9 + [cl, ci, cf, vp]),
+    'cffm_mit_blocks_train_saved_floats': (cl, [MCP]),
+    'cffm_mit_blocks_train_fwd_ws_floats': (cl, [MCP]),
+    'cffm_mit_blocks_train_bwd_ws_floats': (cl, [MCP]),
+    'cffm_mit_blocks_train_fwd': (ci, [MCP, MBP, MSC, vp, vp, vp, vp, vp]),
+    'cffm_mit_blocks_train_bwd': (ci, [MCP, MBP, MSC, MBP, vp, vp, vp, vp, vp, vp]),
 }
 
 

@@ -50,6 +50,14 @@ as the residual and the DropPath factor of each sample as a scale in the GEMM's 
 call.  The factor is drawn as ``DropPath.forward`` draws it, so both settings consume the generator alike and drop the same samples.  ``'torch'``
 (the default) is stock nn.Linear and the reference's residual lines, which is also what tensors outside the limits, other dtypes, CPU tensors
 and modules with ``proj_drop`` / ``drop`` > 0 get.
+
+On top of these, ``block_impl = 'hip'`` (``MixVisionTransformer.set_block_impl``) hands ALL blocks of a stage to the library as one call per
+direction in a training pass (``ops.mit_blocks_train`` -> cffm_mit_blocks_train_fwd / _bwd): the same kernels in the same order as the five
+per-op switches on 'hip', with one `saved` buffer, one workspace and no eager call between them, and the two adds autograd puts around a
+block's LayerNorms inside the LayerNorm backward.  The result and every gradient have the bits of the per-op path, the DropPath factors are
+drawn before the call in the modules' order, so the same samples drop.  ``'torch'`` (the default) is the path described above, which is also
+what a stage gets under no_grad, with nothing to differentiate, outside the library's limits or with a block that is not plain
+(`_blocks_fused`).  The patch embedding and the stage's norm stay on the modules' own path either way.
 """
 import math
 from functools import partial
@@ -59,8 +67,8 @@ import torch.nn as nn
 
 from . import _lib
 from .checkpoint import load_reference_checkpoint
-from .ops import (dwconv_gelu, layer_norm_rows, layer_norm_rows_nchw, linear_rows, linear_rows_supported, ln_supported, mit_infer, mit_stage_cfg,
-                  mit_stage_infer, mit_stage_supported, mit_stage_tensors, mit_stages, nchw_layer_norm_rows, overlap_patch_embed,
+from .ops import (dwconv_gelu, layer_norm_rows, layer_norm_rows_nchw, linear_rows, linear_rows_supported, ln_supported, mit_blocks_cfg,
+                  mit_blocks_train, mit_blocks_train_supported, mit_infer, mit_stage_cfg, mit_stage_infer, mit_stage_supported, mit_stage_tensors, mit_stages, nchw_layer_norm_rows, overlap_patch_embed,
                   patch_embed_out_hw, patch_embed_supported, sr_reduce, sr_reduce_supported, sra_attention)
 from .registry import BACKBONES
 
@@ -370,6 +378,11 @@ class MixVisionTransformer(nn.Module):
     # nn.Linear -- the default (DESIGN section 3z has the measurements).  Attention, Mlp and Block carry an attribute of the same name;
     # set_linear_impl sets them all.
     linear_impl = 'torch'
+    # 'hip': in a training pass (grad mode on, something to differentiate) all blocks of a stage are ONE library call per direction
+    # (ops.mit_blocks_train): fp32 GPU tensors, a stage inside the limits of cffm_mit_stage_infer, plain blocks (nn.Linear, affine
+    # nn.LayerNorm, no dropout, DropPath or Identity); any other stage takes the loop over its blocks, silently, and under no_grad the
+    # switch has no say.  'torch': the loop over the blocks -- the default (DESIGN section 3aa has the measurements).
+    block_impl = 'torch'
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dims=[64, 128, 256, 512], num_heads=[1, 2, 4, 8],
                  mlp_ratios=[4, 4, 4, 4], qkv_bias=False, qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.,
@@ -440,6 +453,55 @@ class MixVisionTransformer(nn.Module):
         for m in self.modules():
             if hasattr(type(m), 'linear_impl'):
                 m.linear_impl = impl
+
+    def set_block_impl(self, impl):
+        """block_impl of the model: 'hip' = every eligible stage's blocks as one library call per direction in a training pass"""
+        if impl not in ('torch', 'hip'):
+            raise ValueError("block_impl must be 'torch' or 'hip', got %r" % (impl,))
+        self.block_impl = impl
+
+    def _blocks_fused(self, blocks, x, H, W):
+        """whether the blocks of a stage take the one-call training path for these token rows: block_impl = 'hip', grad mode on and something
+        to differentiate, fp32 tensors on the GPU (or under the emulator override), plain blocks of one configuration, parameters where
+        the kernels can read them, sizes inside the library's limits"""
+        if self.block_impl != 'hip' or len(blocks) == 0 or not torch.is_grad_enabled():
+            return False
+        if not (x.is_cuda or _lib._override is not None) or x.dtype != torch.float32 or x.dim() != 3 or x.numel() == 0:
+            return False
+        c, b0 = x.shape[-1], blocks[0]
+        ts = []
+        for blk in blocks:
+            a, m = blk.attn, blk.mlp
+            norms = [blk.norm1, blk.norm2] + ([a.norm] if a.sr_ratio > 1 else [])
+            if any(type(n) is not nn.LayerNorm or not n.elementwise_affine or n.bias is None or tuple(n.normalized_shape) != (c,) for n in norms):
+                return False
+            if blk.norm1.eps != b0.norm1.eps or blk.norm2.eps != b0.norm1.eps or (a.sr_ratio > 1 and a.norm.eps != b0.attn.norm.eps):
+                return False
+            if any(type(lin) is not nn.Linear for lin in (a.q, a.kv, a.proj, m.fc1, m.fc2)):
+                return False
+            if any(lin.bias is None for lin in (a.proj, m.fc1, m.fc2)) or a.attn_drop.p or a.proj_drop.p or m.drop.p:
+                return False
+            if type(blk.drop_path) not in (DropPath, nn.Identity):
+                return False
+            if type(m.act) is not nn.GELU or getattr(m.act, 'approximate', 'none') != 'none':
+                return False
+            if (a.num_heads, a.scale, a.sr_ratio, m.fc1.out_features) != (b0.attn.num_heads, b0.attn.scale, b0.attn.sr_ratio, b0.mlp.fc1.out_features):
+                return False
+            if (a.q.in_features, a.q.out_features, a.kv.out_features, a.proj.out_features, m.fc1.in_features, m.fc2.out_features) != (c, c, 2 * c, c, c, c):
+                return False
+            dw = m.dwconv.dwconv
+            if type(dw) is not nn.Conv2d or tuple(dw.weight.shape) != (m.fc1.out_features, 1, 3, 3) or dw.bias is None or dw.padding != (1, 1) or dw.stride != (1, 1):
+                return False
+            if a.sr_ratio > 1:
+                s = a.sr_ratio
+                if type(a.sr) is not nn.Conv2d or tuple(a.sr.weight.shape) != (c, c, s, s) or a.sr.bias is None or a.sr.stride != (s, s) or a.sr.padding != (0, 0):
+                    return False
+            ts += [p for p in blk.parameters()]
+        if any(t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous() or t.data_ptr() % 16 for t in ts):
+            return False
+        if not (x.requires_grad or any(t.requires_grad for t in ts)):
+            return False
+        return mit_blocks_train_supported(mit_blocks_cfg(x.shape, H, W, blocks))
 
     def freeze_patch_emb(self):
         self.patch_embed1.requires_grad = False      # (as in the reference: an attribute on the module, the parameters keep theirs)
@@ -561,8 +623,14 @@ class MixVisionTransformer(nn.Module):
                 outs.append(x)
                 continue
             x, H, W = getattr(self, 'patch_embed%d' % i)(x)
-            for blk in getattr(self, 'block%d' % i):
-                x = blk(x, H, W)
+            blocks = getattr(self, 'block%d' % i)
+            if self._blocks_fused(blocks, x, H, W):
+                # the DropPath factors in the order the modules draw them: block 0 attention line, block 0 Mix-FFN line, block 1 ...
+                scales = [(_drop_scale(blk.drop_path, x), _drop_scale(blk.drop_path, x)) for blk in blocks]
+                x = mit_blocks_train(x, blocks, H, W, scales)
+            else:
+                for blk in blocks:
+                    x = blk(x, H, W)
             norm = getattr(self, 'norm%d' % i)
             if _norm_fused(self.norm_impl, norm, x, x.shape[-1]):
                 x = layer_norm_rows_nchw(x, norm.weight, norm.bias, H, W, norm.eps)

@@ -2902,6 +2902,23 @@ static void dwg_fwd_launch(const float* h, const float* w, const float* b, float
     const DwgGeom G = dwg_plan(M, H, W, C, DWG_XR, DWG_FWD_LANES, 1);
     CFFM_LAUNCH(k_dwg_fwd, ((unsigned)((G.S * G.C4 + 255) / 256)), (256), 0, st, h, w, b, out, G);
 }
+// workspace of the backward (floats): the GELU-scaled gradient [M][H][W][C] | the partial weight-gradient slabs [S][10][C4] f32x4
+static long dwg_bwd_ws_floats(int M, int H, int W, int C) {
+    const DwgGeom G1 = dwg_plan(M, H, W, C, DWG_XR_BWD, DWG_BWD1_LANES, 4);
+    return (long)M * H * W * C + G1.S * DWG_NACC * G1.C4 * 4;
+}
+// (checked arguments -> the two launches: shared with the MiT stage-blocks training call)
+static void dwg_bwd_launch(const float* h, const float* w, const float* b, const float* dout, float* dh, float* dw, float* db, float* workspace,
+                           int M, int H, int W, int C, hipStream_t st) {
+    const DwgGeom G1 = dwg_plan(M, H, W, C, DWG_XR_BWD, DWG_BWD1_LANES, 4);
+    const DwgGeom G2 = dwg_plan(M, H, W, C, DWG_XR, DWG_FWD_LANES, 1);
+    float* g = workspace;                                      // [M][H][W][C]
+    f32x4* part = (f32x4*)(g + (long)M * H * W * C);           // [S][10][C4] f32x4 (M*H*W*C is a multiple of 4: 16-byte aligned)
+    const int nred = DWG_NACC * ((G1.C4 + 15) / 16);
+    CFFM_LAUNCH(k_dwg_bwd1, ((unsigned)((G1.S * G1.C4 + 63) / 64)), (256), 0, st, h, w, b, dout, g, part, G1);
+    CFFM_LAUNCH(k_dwg_bwd2, ((unsigned)(nred + (G2.S * G2.C4 + 255) / 256)), (256), 0, st, (const float*)g, w, dh, (const f32x4*)part, dw, db, G2,
+                G1.S, nred);
+}
 extern "C" {
 int cffm_dwconv_gelu_fwd(const float* h, const float* w, const float* b, float* out, int M, int H, int W, int C, void* stream) {
     TRY(dwg_check("dwconv_gelu_fwd", M, H, W, C));
@@ -2912,23 +2929,14 @@ int cffm_dwconv_gelu_fwd(const float* h, const float* w, const float* b, float* 
 }
 long cffm_dwconv_gelu_bwd_workspace_bytes(int M, int H, int W, int C) {
     if (dwg_check("dwconv_gelu_bwd_workspace_bytes", M, H, W, C)) return -1;
-    const DwgGeom G1 = dwg_plan(M, H, W, C, DWG_XR_BWD, DWG_BWD1_LANES, 4);
-    return (long)M * H * W * C * 4 + G1.S * DWG_NACC * G1.C4 * 16;
+    return dwg_bwd_ws_floats(M, H, W, C) * 4;
 }
 int cffm_dwconv_gelu_bwd(const float* h, const float* w, const float* b, const float* dout, float* dh, float* dw, float* db,
                          void* workspace, int M, int H, int W, int C, void* stream) {
     TRY(dwg_check("dwconv_gelu_bwd", M, H, W, C));
     REQUIRE(aligned16(h) && aligned16(w) && aligned16(b) && aligned16(dout) && aligned16(dh) && aligned16(dw) && aligned16(db) &&
             aligned16(workspace), "dwconv_gelu_bwd: h / w / b / dout / dh / dw / db / workspace must be non-null and 16-byte aligned");
-    const DwgGeom G1 = dwg_plan(M, H, W, C, DWG_XR_BWD, DWG_BWD1_LANES, 4);
-    const DwgGeom G2 = dwg_plan(M, H, W, C, DWG_XR, DWG_FWD_LANES, 1);
-    float* g = (float*)workspace;                              // [M][H][W][C]
-    f32x4* part = (f32x4*)(g + (long)M * H * W * C);           // [S][10][C4] f32x4 (M*H*W*C is a multiple of 4: 16-byte aligned)
-    const int nred = DWG_NACC * ((G1.C4 + 15) / 16);
-    hipStream_t st = (hipStream_t)stream;
-    CFFM_LAUNCH(k_dwg_bwd1, ((unsigned)((G1.S * G1.C4 + 63) / 64)), (256), 0, st, h, w, b, dout, g, part, G1);
-    CFFM_LAUNCH(k_dwg_bwd2, ((unsigned)(nred + (G2.S * G2.C4 + 255) / 256)), (256), 0, st, (const float*)g, w, dh, (const f32x4*)part, dw, db, G2,
-                G1.S, nred);
+    dwg_bwd_launch(h, w, b, dout, dh, dw, db, (float*)workspace, M, H, W, C, (hipStream_t)stream);
     CHECK_LAUNCH("dwconv_gelu_bwd");
     return 0;
 }
@@ -2963,33 +2971,21 @@ static void sra_fwd_launch(const float* q, const float* kv, float* out, float* l
     else { if (hd == 64) SRA_FWD(64, 1); else SRA_FWD(32, 1); }
 #undef SRA_FWD
 }
-extern "C" {
-int cffm_sra_attn_fwd(const float* q, const float* kv, float* out, float* lse, int B, int N, int Nk, int heads, int hd, float scale, void* stream) {
-    TRY(sra_check("sra_attn_fwd", B, N, Nk, heads, hd, scale));
-    REQUIRE(aligned16(q) && aligned16(kv) && aligned16(out) && (uintptr_t)lse % 16 == 0,
-            "sra_attn_fwd: q / kv / out must be non-null and q / kv / out / lse 16-byte aligned");
-    sra_fwd_launch(q, kv, out, lse, B, N, Nk, heads, hd, scale, (hipStream_t)stream);
-    CHECK_LAUNCH("sra_attn_fwd");
-    return 0;
-}
-long cffm_sra_attn_bwd_workspace_bytes(int B, int N, int Nk, int heads, int hd) {
-    if (sra_check("sra_attn_bwd_workspace_bytes", B, N, Nk, heads, hd, 1.f)) return -1;
+// workspace of the backward (floats): delta [B][heads][N] | with more than one query chunk, the dk / dv slabs [chunks][B][Nk][2C]
+static long sra_bwd_ws_floats(int B, int N, int Nk, int heads, int hd) {
     int tpc;
     const int chunks = sra_chunks(B, N, Nk, heads, &tpc);
-    return 4 * (sra_delta_floats(B, N, heads) + (chunks > 1 ? 2L * chunks * B * Nk * heads * hd : 0L));
+    return sra_delta_floats(B, N, heads) + (chunks > 1 ? 2L * chunks * B * Nk * heads * hd : 0L);
 }
-int cffm_sra_attn_bwd(const float* q, const float* kv, const float* out, const float* lse, const float* dout, float* dq, float* dkv,
-                      void* workspace, int B, int N, int Nk, int heads, int hd, float scale, void* stream) {
-    TRY(sra_check("sra_attn_bwd", B, N, Nk, heads, hd, scale));
-    REQUIRE(aligned16(q) && aligned16(kv) && aligned16(out) && aligned16(lse) && aligned16(dout) && aligned16(dq) && aligned16(dkv) &&
-            aligned16(workspace), "sra_attn_bwd: q / kv / out / lse / dout / dq / dkv / workspace must be non-null and 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
+// (checked arguments -> the launches: shared with the MiT stage-blocks training call)
+static void sra_bwd_launch(const float* q, const float* kv, const float* out, const float* lse, const float* dout, float* dq, float* dkv,
+                           float* workspace, int B, int N, int Nk, int heads, int hd, float scale, hipStream_t st) {
     const unsigned gz = (unsigned)(B * heads);
     const double c = (double)scale * 1.4426950408889634;
     const float chi = (float)c, clo = (float)(c - (double)chi);
     int tpc;
     const int chunks = sra_chunks(B, N, Nk, heads, &tpc);
-    float* delta = (float*)workspace;                            // [B][heads][N]
+    float* delta = workspace;                                    // [B][heads][N]
     const long stride = 2L * B * Nk * heads * hd;                // floats of one slab [B][Nk][2C]
     float* slab = chunks > 1 ? delta + sra_delta_floats(B, N, heads) : dkv;
 #define SRA_DQ(HD_, QW_) CFFM_LAUNCH((k_sra_bwd_dq<HD_, QW_>), ((unsigned)((N + 64 * QW_ - 1) / (64 * QW_)), 1, gz), (256), 0, st, q, kv, out, lse, dout, dq, delta, N, Nk, heads, scale, chi, clo)
@@ -3003,6 +2999,26 @@ int cffm_sra_attn_bwd(const float* q, const float* kv, const float* out, const f
         const long n4 = stride / 4;
         CFFM_LAUNCH(k_sra_dkv_sum, ((unsigned)std::min(2048L, (n4 + 255) / 256)), (256), 0, st, (const f32x4*)slab, (f32x4*)dkv, n4, n4, chunks);
     }
+}
+extern "C" {
+int cffm_sra_attn_fwd(const float* q, const float* kv, float* out, float* lse, int B, int N, int Nk, int heads, int hd, float scale, void* stream) {
+    TRY(sra_check("sra_attn_fwd", B, N, Nk, heads, hd, scale));
+    REQUIRE(aligned16(q) && aligned16(kv) && aligned16(out) && (uintptr_t)lse % 16 == 0,
+            "sra_attn_fwd: q / kv / out must be non-null and q / kv / out / lse 16-byte aligned");
+    sra_fwd_launch(q, kv, out, lse, B, N, Nk, heads, hd, scale, (hipStream_t)stream);
+    CHECK_LAUNCH("sra_attn_fwd");
+    return 0;
+}
+long cffm_sra_attn_bwd_workspace_bytes(int B, int N, int Nk, int heads, int hd) {
+    if (sra_check("sra_attn_bwd_workspace_bytes", B, N, Nk, heads, hd, 1.f)) return -1;
+    return 4 * sra_bwd_ws_floats(B, N, Nk, heads, hd);
+}
+int cffm_sra_attn_bwd(const float* q, const float* kv, const float* out, const float* lse, const float* dout, float* dq, float* dkv,
+                      void* workspace, int B, int N, int Nk, int heads, int hd, float scale, void* stream) {
+    TRY(sra_check("sra_attn_bwd", B, N, Nk, heads, hd, scale));
+    REQUIRE(aligned16(q) && aligned16(kv) && aligned16(out) && aligned16(lse) && aligned16(dout) && aligned16(dq) && aligned16(dkv) &&
+            aligned16(workspace), "sra_attn_bwd: q / kv / out / lse / dout / dq / dkv / workspace must be non-null and 16-byte aligned");
+    sra_bwd_launch(q, kv, out, lse, dout, dq, dkv, (float*)workspace, B, N, Nk, heads, hd, scale, (hipStream_t)stream);
     CHECK_LAUNCH("sra_attn_bwd");
     return 0;
 }
@@ -3049,6 +3065,17 @@ static void srln_fwd_launch(int s, hipStream_t st, const float* x, const float* 
     else if (s == 4) srln_launch_fwd<4>(ncw, grid, st, x, w, b, gamma, beta, out, z, stats, G, eps);
     else srln_launch_fwd<8>(ncw, grid, st, x, w, b, gamma, beta, out, z, stats, G, eps);
 }
+// workspace of the backward (floats): dz [M][C] | the partial column sums [row blocks][3][C]
+static long srln_bwd_ws_floats(const SrGeom& G) { return srln_dz_floats(G) + 3L * srln_row_blocks(G) * G.C; }
+// (checked arguments -> the launches: shared with the MiT stage-blocks training call)
+static void srln_bwd_launch(int s, hipStream_t st, const float* x, const float* w, const float* gamma, const float* z, const float* stats,
+                            const float* dout, float* dx, float* dw, float* db, float* dgamma, float* dbeta, float* workspace, const SrGeom& G) {
+    float* dz = workspace;                                       // [M][C]
+    float* part = dz + srln_dz_floats(G);                        // [row blocks][3][C]
+    if (s == 2) srln_launch_bwd<2>(st, x, w, gamma, z, stats, dout, dx, dw, db, dgamma, dbeta, dz, part, G);
+    else if (s == 4) srln_launch_bwd<4>(st, x, w, gamma, z, stats, dout, dx, dw, db, dgamma, dbeta, dz, part, G);
+    else srln_launch_bwd<8>(st, x, w, gamma, z, stats, dout, dx, dw, db, dgamma, dbeta, dz, part, G);
+}
 extern "C" {
 int cffm_sr_ln_fwd(const float* x, const float* w, const float* b, const float* gamma, const float* beta, float* out, float* z, float* stats,
                    int B, int H, int W, int C, int s, float eps, void* stream) {
@@ -3065,7 +3092,7 @@ int cffm_sr_ln_fwd(const float* x, const float* w, const float* b, const float* 
 long cffm_sr_ln_bwd_workspace_bytes(int B, int H, int W, int C, int s) {
     SrGeom G;
     if (srln_check("sr_ln_bwd_workspace_bytes", B, H, W, C, s, 0.f, &G)) return -1;
-    return 4 * (srln_dz_floats(G) + 3L * srln_row_blocks(G) * C);
+    return 4 * srln_bwd_ws_floats(G);
 }
 int cffm_sr_ln_bwd(const float* x, const float* w, const float* gamma, const float* z, const float* stats, const float* dout, float* dx,
                    float* dw, float* db, float* dgamma, float* dbeta, void* workspace, int B, int H, int W, int C, int s, float eps,
@@ -3075,12 +3102,7 @@ int cffm_sr_ln_bwd(const float* x, const float* w, const float* gamma, const flo
     REQUIRE(aligned16(x) && aligned16(w) && aligned16(gamma) && aligned16(z) && aligned16(stats) && aligned16(dout) &&
             aligned16(dx) && aligned16(dw) && aligned16(db) && aligned16(dgamma) && aligned16(dbeta) && aligned16(workspace),
             "sr_ln_bwd: x / w / gamma / z / stats / dout / dx / dw / db / dgamma / dbeta / workspace must be non-null and 16-byte aligned");
-    float* dz = (float*)workspace;                               // [M][C]
-    float* part = dz + srln_dz_floats(G);                        // [row blocks][3][C]
-    hipStream_t st = (hipStream_t)stream;
-    if (s == 2) srln_launch_bwd<2>(st, x, w, gamma, z, stats, dout, dx, dw, db, dgamma, dbeta, dz, part, G);
-    else if (s == 4) srln_launch_bwd<4>(st, x, w, gamma, z, stats, dout, dx, dw, db, dgamma, dbeta, dz, part, G);
-    else srln_launch_bwd<8>(st, x, w, gamma, z, stats, dout, dx, dw, db, dgamma, dbeta, dz, part, G);
+    srln_bwd_launch(s, (hipStream_t)stream, x, w, gamma, z, stats, dout, dx, dw, db, dgamma, dbeta, (float*)workspace, G);
     CHECK_LAUNCH("sr_ln_bwd");
     return 0;
 }
@@ -3159,6 +3181,29 @@ static void mln_bwd_launch(int which, hipStream_t st, const float* x, const floa
         default: mln_bwd_go<64, 1>(which, st, x, g, dy, dx, rec, M, nimg, G, eps);
     }
     CFFM_LAUNCH((k_ln_bwd_final), ((unsigned)(C / 2)), (MLN_FIN_SLICES), 0, st, rec, dgamma, dbeta, (int)mln_bwd_records(M, C, HW), C);
+}
+// the rows form with the neighbouring adds fused in (k_ln_rows_bwd_add): dout = dya (+ dyb), dx = (dres +) LN-backward.  Grid, records and
+// the final sum are those of mln_bwd_launch(0, ...)
+template <int PW, int V>
+static void mln_bwd_add_go(hipStream_t st, const float* x, const float* g, const float* dya, const float* dyb, const float* dres, float* dx,
+                           float* rec, long M, const MlnGeom& G, float eps) {
+#define MLN_ADD(B_, R_) CFFM_LAUNCH((k_ln_rows_bwd_add<PW, V, B_, R_>), ((unsigned)mln_bwd_records(M, G.C, 1)), (256), 0, st, x, g, dya, dyb, dres, dx, rec, M, G, eps)
+    if (dyb) { if (dres) MLN_ADD(true, true); else MLN_ADD(true, false); }
+    else { if (dres) MLN_ADD(false, true); else MLN_ADD(false, false); }
+#undef MLN_ADD
+}
+static void mln_bwd_add_launch(hipStream_t st, const float* x, const float* g, const float* dya, const float* dyb, const float* dres, float* dx,
+                               float* dgamma, float* dbeta, float* rec, long M, int C, float eps) {
+    const MlnGeom G = mln_geom(C, 1);
+    if (G.C4 > 64) mln_bwd_add_go<64, 2>(st, x, g, dya, dyb, dres, dx, rec, M, G, eps);
+    else switch (mln_pw(C)) {
+        case 4: mln_bwd_add_go<4, 1>(st, x, g, dya, dyb, dres, dx, rec, M, G, eps); break;
+        case 8: mln_bwd_add_go<8, 1>(st, x, g, dya, dyb, dres, dx, rec, M, G, eps); break;
+        case 16: mln_bwd_add_go<16, 1>(st, x, g, dya, dyb, dres, dx, rec, M, G, eps); break;
+        case 32: mln_bwd_add_go<32, 1>(st, x, g, dya, dyb, dres, dx, rec, M, G, eps); break;
+        default: mln_bwd_add_go<64, 1>(st, x, g, dya, dyb, dres, dx, rec, M, G, eps);
+    }
+    CFFM_LAUNCH((k_ln_bwd_final), ((unsigned)(C / 2)), (MLN_FIN_SLICES), 0, st, rec, dgamma, dbeta, (int)mln_bwd_records(M, C, 1), C);
 }
 
 // workspace of one stage call (floats).  The residual stream alternates between xa and xb inside a block (xa -> proj + residual -> xb ->
@@ -3423,6 +3468,19 @@ int cffm_ln_rows_bwd(const float* x, const float* gamma, const float* dout, floa
     CHECK_LAUNCH("ln_rows_bwd");
     return 0;
 }
+int cffm_ln_rows_bwd_add(const float* x, const float* gamma, const float* dout_a, const float* dout_b, const float* dres, float* dx, float* dgamma,
+                         float* dbeta, void* ws, long M, int C, float eps, void* stream) {
+    TRY(mln_check("ln_rows_bwd_add", C, eps));
+    REQUIRE(M >= 1 && M * C < (1L << 31), "ln_rows_bwd_add: M=%ld rows of C=%d: M must be at least 1 and M*C below 2^31", M, C);
+    REQUIRE(aligned16(x) && aligned16(gamma) && aligned16(dout_a) && aligned16(dx) && aligned16(dgamma) && aligned16(dbeta) && aligned16(ws) &&
+            (uintptr_t)dout_b % 16 == 0 && (uintptr_t)dres % 16 == 0,
+            "ln_rows_bwd_add: x / gamma / dout_a / dx / dgamma / dbeta / ws must be non-null and 16-byte aligned, dout_b / dres 16-byte aligned or null");
+    REQUIRE((const float*)dx != x && (const float*)dx != dout_a && (const float*)dx != dout_b,
+            "ln_rows_bwd_add: dx must not alias x, dout_a or dout_b (dx == dres is the one in-place form)");
+    mln_bwd_add_launch((hipStream_t)stream, x, gamma, dout_a, dout_b, dres, dx, dgamma, dbeta, (float*)ws, M, C, eps);
+    CHECK_LAUNCH("ln_rows_bwd_add");
+    return 0;
+}
 int cffm_nchw_ln_rows_bwd(const float* x_nchw, const float* gamma, const float* dout_rows, float* dx_nchw, float* dgamma, float* dbeta, void* ws,
                           int B, int C, int H, int W, float eps, void* stream) {
     TRY(mln_check_map("nchw_ln_rows_bwd", B, C, H, W, eps));
@@ -3567,6 +3625,232 @@ int cffm_linear_rows_bwd(const float* dy, const float* x, const float* w, const 
             "linear_rows_bwd: launch refused (dw)");
     if (db) gemm_rows_db(dy, scale, db, M, N, rows_per_sample, W.P, ws + W.rec, st);
     CHECK_LAUNCH("linear_rows_bwd");
+    return 0;
+}
+
+// ---- the blocks of one MiT stage in a training pass: one call per direction (cffm_mit_blocks_train_*) ----
+}  // extern "C"
+// Float offsets.  `saved`: depth slices of `per` floats, one per block, in the order below (xout = the block's output, the next block's
+// input: the last block has none, its output is y_rows).  The backward's workspace: g / g1, the running gradient and the gradient behind
+// norm2's residual add, live across a block; `phase`, which the Mix-FFN half of a block's backward (da | dh | dwconv workspace | dz2) and
+// then its attention half (dao | dq | dkv | attention workspace | dr | sr workspace | dz1a | dz1b) lay out anew; and the three carves every
+// Linear / LayerNorm backward of the call shares, each the maximum over its users: the dw slabs, the db records, the LayerNorm records.
+// The forward needs no workspace: every intermediate it makes is kept.
+struct MitTrainLay {
+    MitWs W;
+    SrGeom SG;
+    long z1, q, sz, sstats, r, kv, ao, lse, x1, z2, h, a, xout, per, saved_total;
+    long g, g1, phase, da, dh, dwgws, dz2, dao, dq, dkv, sraws, dr, srws, dz1a, dz1b, slab, rec, lnrec, bwd_total;
+};
+struct MitLin { long M; int N, K; };
+static void mit_train_linears(const cffm_mit_stage_cfg* c, const MitWs& W, MitLin (&L)[5]) {     // q | kv | proj | fc1 | fc2
+    const long Mk = (long)c->B * W.Nk;
+    L[0] = {W.M, c->C, c->C}; L[1] = {Mk, 2 * c->C, c->C}; L[2] = {W.M, c->C, c->C}; L[3] = {W.M, c->hidden, c->C}; L[4] = {W.M, c->C, c->hidden};
+}
+static int mit_train_check(const char* who, const cffm_mit_stage_cfg* c0, cffm_mit_stage_cfg* co, MitTrainLay* Lo) {
+    REQUIRE(c0, "%s: null cfg", who);
+    cffm_mit_stage_cfg c = *c0;
+    c.eps_embed = c.eps_out = 0.f;                               // (not read by these calls)
+    MitTrainLay L = {};
+    TRY(mit_cfg_check(who, &c, &L.W));
+    const int s = c.sr_ratio, C = c.C, hid = c.hidden;
+    if (s > 1) TRY(srln_check(who, c.B, c.H, c.W, C, s, c.eps_sr, &L.SG));
+    TRY(mln_check(who, C, c.eps_block));
+    MitLin lin[5];
+    mit_train_linears(&c, L.W, lin);
+    for (const MitLin& l : lin) TRY(lrows_check(who, l.M, l.N, l.K, 1));
+    const long MC = L.W.M * C, KC = (long)c.B * L.W.Nk * C, MH = L.W.M * hid;
+    long p = 0;
+    L.z1 = p; p += up(MC);
+    L.q = p; p += up(MC);
+    L.sz = p; p += s > 1 ? up(KC) : 0;
+    L.sstats = p; p += s > 1 ? up(2L * c.B * L.W.Nk) : 0;
+    L.r = p; p += s > 1 ? up(KC) : 0;
+    L.kv = p; p += up(2 * KC);
+    L.ao = p; p += up(MC);
+    L.lse = p; p += up((long)c.B * c.heads * L.W.N);
+    L.x1 = p; p += up(MC);
+    L.z2 = p; p += up(MC);
+    L.h = p; p += up(MH);
+    L.a = p; p += up(MH);
+    L.xout = p; p += up(MC);
+    L.per = p;
+    L.saved_total = (long)c.depth * L.per - up(MC);
+    p = 0;
+    L.g = p; p += up(MC);
+    L.g1 = p; p += up(MC);
+    L.phase = p;
+    long m = p;                                                  // the Mix-FFN half
+    L.da = m; m += up(MH);
+    L.dh = m; m += up(MH);
+    L.dwgws = m; m += up(dwg_bwd_ws_floats(c.B, c.H, c.W, hid));
+    L.dz2 = m; m += up(MC);
+    long a = p;                                                  // the attention half
+    L.dao = a; a += up(MC);
+    L.dq = a; a += up(MC);
+    L.dkv = a; a += up(2 * KC);
+    L.sraws = a; a += up(sra_bwd_ws_floats(c.B, L.W.N, L.W.Nk, c.heads, C / c.heads));
+    L.dz1a = a; a += up(MC);
+    L.dz1b = a; a += up(MC);
+    L.dr = s > 1 ? a : L.dz1b; a += s > 1 ? up(KC) : 0;          // (sr_ratio 1: kv's input gradient IS dz1b)
+    L.srws = a; a += s > 1 ? up(srln_bwd_ws_floats(L.SG)) : 0;
+    p = std::max(m, a);
+    long slab = 0, rec = 0;
+    for (int i = 0; i < 5; ++i) {
+        const RowsBwdPlan P = gemm_rows_bwd_plan(lin[i].M, lin[i].N, lin[i].K);
+        slab = std::max(slab, P.ksplit > 1 ? (long)P.ksplit * lin[i].N * lin[i].K : 0L);
+        rec = std::max(rec, (long)P.nrec * lin[i].N);
+    }
+    L.slab = p; p += up(slab);
+    L.rec = p; p += up(rec);
+    L.lnrec = p; p += up(mln_bwd_records(L.W.M, C, 1) * 2 * C);
+    L.bwd_total = p;
+    if (co) *co = c;
+    if (Lo) *Lo = L;
+    return 0;
+}
+// the pointers of both directions: the parameters as cffm_mit_stage_infer asks for them, the factors, and (backward) a gradient pointer
+// exactly where there is a parameter
+static int mit_train_ptr_check(const char* who, const cffm_mit_stage_cfg* c, const cffm_mit_block_params* blocks, const cffm_mit_block_scales* scales,
+                               const cffm_mit_block_grad_ptrs* grads, bool bwd) {
+    alignas(16) static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};      // (the stage's own norms are not part of these calls)
+    TRY(mit_ptr_check(who, c, blocks, dummy, dummy, dummy, dummy));
+    for (int i = 0; scales && i < c->depth; ++i)
+        REQUIRE((uintptr_t)scales[i].scale_attn % 4 == 0 && (uintptr_t)scales[i].scale_mlp % 4 == 0, "%s: block %d: a scale is not 4-byte aligned", who, i);
+    if (!bwd) return 0;
+    REQUIRE(grads, "%s: null gradient pointers", who);
+    constexpr int NF = sizeof(cffm_mit_block_params) / sizeof(const float*);
+    static_assert(sizeof(cffm_mit_block_grad_ptrs) == sizeof(cffm_mit_block_params), "the two structs have the same fields");
+    for (int i = 0; i < c->depth; ++i) {
+        const float* const* pp = (const float* const*)&blocks[i];
+        float* const* gp = (float* const*)&grads[i];
+        for (int f = 0; f < NF; ++f) {
+            REQUIRE(!pp[f] == !gp[f] && (uintptr_t)gp[f] % 16 == 0,
+                    "%s: block %d: gradient %d must be non-null exactly where the parameter is, and 16-byte aligned", who, i, f);
+            REQUIRE((const float*)gp[f] != pp[f] || !gp[f], "%s: block %d: gradient %d aliases its parameter", who, i, f);
+        }
+    }
+    return 0;
+}
+static int mit_train_alias_check(const char* who, const void* const* ptrs, const char* const* names, int n) {
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < i; ++j)
+            REQUIRE(!ptrs[i] || ptrs[i] != ptrs[j], "%s: %s and %s must not alias", who, names[j], names[i]);
+    return 0;
+}
+// one Linear layer's backward on the call's shared carves (cffm_linear_rows_bwd's three launches, in its order)
+static int mit_train_linear_bwd(const float* dy, const float* x, const float* w, const float* s, float* dx, float* dw, float* db, const MitLin& l,
+                                int rps, float* slab, float* rec, hipStream_t st) {
+    const RowsBwdPlan P = gemm_rows_bwd_plan(l.M, l.N, l.K);
+    if (gemm_rows_dx(dy, w, s, dx, l.M, l.N, l.K, rps, st)) return -1;
+    if (gemm_rows_dw(dy, x, s, dw, l.M, l.N, l.K, rps, P, P.ksplit > 1 ? slab : nullptr, st)) return -1;
+    if (db) gemm_rows_db(dy, s, db, l.M, l.N, rps, P, rec, st);
+    return 0;
+}
+extern "C" {
+long cffm_mit_blocks_train_saved_floats(const cffm_mit_stage_cfg* c) {
+    MitTrainLay L;
+    return mit_train_check("mit_blocks_train_saved_floats", c, nullptr, &L) ? -1 : L.saved_total;
+}
+long cffm_mit_blocks_train_fwd_ws_floats(const cffm_mit_stage_cfg* c) {
+    return mit_train_check("mit_blocks_train_fwd_ws_floats", c, nullptr, nullptr) ? -1 : 0;
+}
+long cffm_mit_blocks_train_bwd_ws_floats(const cffm_mit_stage_cfg* c) {
+    MitTrainLay L;
+    return mit_train_check("mit_blocks_train_bwd_ws_floats", c, nullptr, &L) ? -1 : L.bwd_total;
+}
+int cffm_mit_blocks_train_fwd(const cffm_mit_stage_cfg* c0, const cffm_mit_block_params* blocks, const cffm_mit_block_scales* scales,
+                              const float* x_rows, float* y_rows, float* saved, float* ws, void* stream) {
+    const char* who = "mit_blocks_train_fwd";
+    cffm_mit_stage_cfg c;
+    MitTrainLay L;
+    TRY(mit_train_check(who, c0, &c, &L));
+    TRY(mit_train_ptr_check(who, &c, blocks, scales, nullptr, false));
+    REQUIRE(aligned16(x_rows) && aligned16(y_rows) && aligned16(saved) && (uintptr_t)ws % 16 == 0,
+            "%s: x_rows / y_rows / saved must be non-null and 16-byte aligned, ws 16-byte aligned (the forward needs none: NULL is accepted)", who);
+    const void* const ptrs[] = {x_rows, y_rows, saved, ws};
+    const char* const names[] = {"x_rows", "y_rows", "saved", "ws"};
+    TRY(mit_train_alias_check(who, ptrs, names, 4));
+    MitLin lin[5];
+    mit_train_linears(&c, L.W, lin);
+    for (const MitLin& l : lin)
+        REQUIRE((gemm_split_grant<false, false, 8, 0, 0>((int)l.M, l.N, l.K, 1, 0)), "%s: LDS grant refused", who);
+    hipStream_t st = (hipStream_t)stream;
+    const int s = c.sr_ratio, B = c.B, C = c.C, hid = c.hidden, N = L.W.N, Nk = L.W.Nk;
+    const long M = L.W.M;
+    for (int i = 0; i < c.depth; ++i) {
+        const cffm_mit_block_params& p = blocks[i];
+        const float* sa = scales ? scales[i].scale_attn : nullptr;
+        const float* sm = scales ? scales[i].scale_mlp : nullptr;
+        float* S = saved + (long)i * L.per;
+        const float* xin = i ? S - L.per + L.xout : x_rows;
+        float* xout = i + 1 < c.depth ? S + L.xout : y_rows;
+        mln_launch(0, st, xin, p.n1_g, p.n1_b, S + L.z1, M, 0, C, 1, c.eps_block);
+        bool bad = gemm_rows_fwd(S + L.z1, p.q_w, p.q_b, nullptr, nullptr, S + L.q, M, C, C, (int)M, st) != 0;
+        if (s > 1) srln_fwd_launch(s, st, S + L.z1, p.sr_w, p.sr_b, p.srn_g, p.srn_b, S + L.r, S + L.sz, S + L.sstats, L.SG, c.eps_sr);
+        bad = bad || gemm_rows_fwd(s > 1 ? S + L.r : S + L.z1, p.kv_w, p.kv_b, nullptr, nullptr, S + L.kv, lin[1].M, 2 * C, C, (int)lin[1].M, st);
+        sra_fwd_launch(S + L.q, S + L.kv, S + L.ao, S + L.lse, B, N, Nk, c.heads, C / c.heads, c.scale, st);
+        bad = bad || gemm_rows_fwd(S + L.ao, p.proj_w, p.proj_b, xin, sa, S + L.x1, M, C, C, sa ? N : (int)M, st);
+        mln_launch(0, st, S + L.x1, p.n2_g, p.n2_b, S + L.z2, M, 0, C, 1, c.eps_block);
+        bad = bad || gemm_rows_fwd(S + L.z2, p.fc1_w, p.fc1_b, nullptr, nullptr, S + L.h, M, hid, C, (int)M, st);
+        dwg_fwd_launch(S + L.h, p.dw_w, p.dw_b, S + L.a, B, c.H, c.W, hid, st);
+        bad = bad || gemm_rows_fwd(S + L.a, p.fc2_w, p.fc2_b, S + L.x1, sm, xout, M, C, hid, sm ? N : (int)M, st);
+        REQUIRE(!bad, "%s: launch refused", who);
+    }
+    CHECK_LAUNCH("mit_blocks_train_fwd");
+    return 0;
+}
+int cffm_mit_blocks_train_bwd(const cffm_mit_stage_cfg* c0, const cffm_mit_block_params* blocks, const cffm_mit_block_scales* scales,
+                              const cffm_mit_block_grad_ptrs* grads, const float* x_rows, const float* saved, const float* dy_rows, float* dx_rows,
+                              float* ws, void* stream) {
+    const char* who = "mit_blocks_train_bwd";
+    cffm_mit_stage_cfg c;
+    MitTrainLay L;
+    TRY(mit_train_check(who, c0, &c, &L));
+    TRY(mit_train_ptr_check(who, &c, blocks, scales, grads, true));
+    REQUIRE(aligned16(x_rows) && aligned16(saved) && aligned16(dy_rows) && aligned16(dx_rows) && aligned16(ws),
+            "%s: x_rows / saved / dy_rows / dx_rows / ws must be non-null and 16-byte aligned", who);
+    const void* const ptrs[] = {x_rows, saved, dy_rows, dx_rows, ws};
+    const char* const names[] = {"x_rows", "saved", "dy_rows", "dx_rows", "ws"};
+    TRY(mit_train_alias_check(who, ptrs, names, 5));
+    MitLin lin[5];
+    mit_train_linears(&c, L.W, lin);
+    for (int i = 0; i < 5; ++i) {
+        // (a block's factor may be null where another's is not: both forms of the scaled layers are asked for when any factor is given)
+        const RowsBwdPlan P = gemm_rows_bwd_plan(lin[i].M, lin[i].N, lin[i].K);
+        REQUIRE(gemm_rows_bwd_grant(lin[i].M, lin[i].N, lin[i].K, false, true, P), "%s: LDS grant refused", who);
+        if (scales && (i == 2 || i == 4)) REQUIRE(gemm_rows_bwd_grant(lin[i].M, lin[i].N, lin[i].K, true, true, P), "%s: LDS grant refused", who);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int s = c.sr_ratio, B = c.B, C = c.C, hid = c.hidden, N = L.W.N, Nk = L.W.Nk;
+    const long M = L.W.M;
+    float *gA = ws + L.g, *g1 = ws + L.g1, *slab = ws + L.slab, *rec = ws + L.rec, *lnrec = ws + L.lnrec;
+    for (int i = c.depth - 1; i >= 0; --i) {
+        const cffm_mit_block_params& p = blocks[i];
+        const cffm_mit_block_grad_ptrs& d = grads[i];
+        const float* sa = scales ? scales[i].scale_attn : nullptr;
+        const float* sm = scales ? scales[i].scale_mlp : nullptr;
+        const float* S = saved + (long)i * L.per;
+        const float* xin = i ? S - L.per + L.xout : x_rows;
+        const float* g = i + 1 < c.depth ? gA : dy_rows;
+        float* gx = i ? gA : dx_rows;
+        bool bad = mit_train_linear_bwd(g, S + L.a, p.fc2_w, sm, ws + L.da, d.fc2_w, d.fc2_b, lin[4], sm ? N : (int)M, slab, rec, st) != 0;
+        dwg_bwd_launch(S + L.h, p.dw_w, p.dw_b, ws + L.da, ws + L.dh, d.dw_w, d.dw_b, ws + L.dwgws, B, c.H, c.W, hid, st);
+        bad = bad || mit_train_linear_bwd(ws + L.dh, S + L.z2, p.fc1_w, nullptr, ws + L.dz2, d.fc1_w, d.fc1_b, lin[3], (int)M, slab, rec, st);
+        mln_bwd_add_launch(st, S + L.x1, p.n2_g, ws + L.dz2, nullptr, g, g1, d.n2_g, d.n2_b, lnrec, M, C, c.eps_block);
+        bad = bad || mit_train_linear_bwd(g1, S + L.ao, p.proj_w, sa, ws + L.dao, d.proj_w, d.proj_b, lin[2], sa ? N : (int)M, slab, rec, st);
+        sra_bwd_launch(S + L.q, S + L.kv, S + L.ao, S + L.lse, ws + L.dao, ws + L.dq, ws + L.dkv, ws + L.sraws, B, N, Nk, c.heads, C / c.heads,
+                       c.scale, st);
+        bad = bad || mit_train_linear_bwd(ws + L.dkv, s > 1 ? S + L.r : S + L.z1, p.kv_w, nullptr, ws + L.dr, d.kv_w, d.kv_b, lin[1], (int)lin[1].M,
+                                          slab, rec, st);
+        if (s > 1)
+            srln_bwd_launch(s, st, S + L.z1, p.sr_w, p.srn_g, S + L.sz, S + L.sstats, ws + L.dr, ws + L.dz1b, d.sr_w, d.sr_b, d.srn_g, d.srn_b,
+                            ws + L.srws, L.SG);
+        bad = bad || mit_train_linear_bwd(ws + L.dq, S + L.z1, p.q_w, nullptr, ws + L.dz1a, d.q_w, d.q_b, lin[0], (int)M, slab, rec, st);
+        mln_bwd_add_launch(st, xin, p.n1_g, ws + L.dz1a, ws + L.dz1b, g1, gx, d.n1_g, d.n1_b, lnrec, M, C, c.eps_block);
+        REQUIRE(!bad, "%s: launch refused", who);
+    }
+    CHECK_LAUNCH("mit_blocks_train_bwd");
     return 0;
 }
 

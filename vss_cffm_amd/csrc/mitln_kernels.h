@@ -369,6 +369,63 @@ __global__ void __launch_bounds__(256) k_ln_rows_bwd(const float* __restrict__ x
     mln_record<PW, V>(R, dg, db, G, rec + (long)blockIdx.x * 2 * G.C);
 }
 
+// a + b rounded on its own: the add carries no contract flag, so it is never fused with the multiply that made an operand.  (__fadd_rn
+// is a plain `+` in the HIP headers and IS fused under the device default -ffp-contract=fast.)
+__device__ __forceinline__ float mln_add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
+// k_ln_rows_bwd with the adds autograd puts around a block's LayerNorms fused in:  d = dya (+ dyb, HAS_B),  v = LN-backward(x, gamma, d),
+// dx = dres + v (HAS_RES) or v.  Each add is one fp32 add rounded on its own, so dx / dgamma / dbeta have the bits of
+// k_ln_rows_bwd(x, gamma, dya + dyb) followed by dres + dx as two separate element-wise passes.  For that mln_row_bwd has to be compiled
+// to the instructions it has in k_ln_rows_bwd: where a product with two users may be folded into an FMA or not (g * dy in g * dy - a),
+// what the compiler does depends on the code around it.  With the two adds as run-time branches the V = 2 form came out with other
+// FMAs than k_ln_rows_bwd's, and so did every form with the result passed through an empty asm before the last add; as template
+// parameters, nothing else added, all forms have k_ln_rows_bwd's multiplies and FMAs (counted in the ISA, and tested bit for bit).
+// dx == dres is allowed: a lane reads its own chunks of dres before it writes them (hence no __restrict__ on the two).  rec, grid,
+// block: as k_ln_rows_bwd.
+template <int PW, int V, bool HAS_B, bool HAS_RES>
+__global__ void __launch_bounds__(256) k_ln_rows_bwd_add(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ dya,
+                                                          const float* __restrict__ dyb, const float* dres, float* dx, float* __restrict__ rec,
+                                                          long M, MlnGeom G, float eps) {
+    constexpr int RPB = 4 * (64 / PW);
+    __shared__ f32x4 R[MLN_RED_FLOATS(V) / 4];
+    const int j = threadIdx.x & (PW - 1), sub = threadIdx.x / PW;
+    const f32x4 z = (f32x4){0.f, 0.f, 0.f, 0.f};
+    bool act[V];
+    f32x4 g[V], dg[V], db[V];
+    mln_gamma<V>(gamma, G, j, act, g);
+#pragma unroll
+    for (int k = 0; k < V; ++k) dg[k] = db[k] = z;
+    for (long row0 = (long)blockIdx.x * RPB; row0 < M; row0 += (long)gridDim.x * RPB) {   // (uniform over the workgroup)
+        const long row = row0 + sub;
+        const bool live = row < M;
+        f32x4 v[V], d[V], r[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            v[k] = (live && act[k]) ? *(const f32x4*)(x + row * G.C + 4 * (j + k * G.L)) : z;
+            d[k] = (live && act[k]) ? *(const f32x4*)(dya + row * G.C + 4 * (j + k * G.L)) : z;
+            if (HAS_B) {
+                const f32x4 e = (live && act[k]) ? *(const f32x4*)(dyb + row * G.C + 4 * (j + k * G.L)) : z;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) d[k][c] = mln_add_rn(d[k][c], e[c]);
+            }
+            if (HAS_RES) r[k] = (live && act[k]) ? *(const f32x4*)(dres + row * G.C + 4 * (j + k * G.L)) : z;
+        }
+        mln_row_bwd<PW, V>(v, d, act, g, live, G.C, eps, dg, db);
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            if (HAS_RES) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) v[k][c] = mln_add_rn(r[k][c], v[k][c]);
+            }
+            if (live && act[k]) *(f32x4*)(dx + row * G.C + 4 * (j + k * G.L)) = v[k];
+        }
+    }
+    mln_record<PW, V>(R, dg, db, G, rec + (long)blockIdx.x * 2 * G.C);
+}
+
 // one image's NCHW pixels p0 .. p0 + np - 1 (src = channel 0, pixel p0) -> T[pixel][LD]: the input side of k_nchw_ln_rows
 __device__ __forceinline__ void mln_tile_in(float* T, const float* __restrict__ src0, const MlnGeom& G, int np) {
     const int q = threadIdx.x & 3, PG = G.TP / 4, items = MLN_ITEMS(G);

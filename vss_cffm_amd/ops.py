@@ -1854,6 +1854,145 @@ def mit_stage_infer(conv_out, embed_norm, blocks, out_norm, ws=None, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- the blocks of one MiT stage per call, differentiable
+def mit_blocks_cfg(shape, H, W, blocks):
+    """cffm_mit_stage_cfg of cffm_mit_blocks_train_*: `shape` = (B, N, C) of the token rows, `blocks` the stage's Block modules (all of one
+    configuration).  eps_embed / eps_out are not read by those calls and stay 0."""
+    b, _, c = (int(v) for v in shape)
+    a, m = blocks[0].attn, blocks[0].mlp
+    return _lib.MitStageCfg(B=b, H=int(H), W=int(W), C=c, heads=int(a.num_heads), hidden=int(m.fc1.out_features), sr_ratio=int(a.sr_ratio),
+                            depth=len(blocks), scale=float(a.scale), eps_embed=0.0, eps_block=float(blocks[0].norm1.eps),
+                            eps_sr=float(a.norm.eps) if a.sr_ratio > 1 else 0.0, eps_out=0.0)
+
+
+def mit_blocks_train_supported(cfg):
+    """whether the blocks of this stage are inside the limits of cffm_mit_blocks_train_fwd / _bwd: those of cffm_mit_stage_infer"""
+    return mit_stage_supported(cfg)
+
+
+def _mit_block_tensors(blocks):
+    """the parameters of the blocks in the order of cffm_mit_block_params, None where a module has none"""
+    return mit_stage_tensors(blocks, blocks[0].norm1, blocks[0].norm1)[:-4]
+
+
+def _mit_block_structs(tensors, depth):
+    n = len(_MIT_FIELDS)
+    structs = (_lib.MitBlockPtrs * depth)()
+    for i in range(depth):
+        for f, t in zip(_MIT_FIELDS, tensors[i * n:(i + 1) * n]):
+            setattr(structs[i], f, t.data_ptr() if t is not None else None)
+    return structs
+
+
+def _mit_scale_structs(scales, depth):
+    """scales: None or depth pairs (attn factor, mlp factor) of [B] tensors or None -> cffm_mit_block_scales[depth] or None"""
+    if scales is None or all(t is None for pair in scales for t in pair):
+        return None
+    structs = (_lib.MitBlockScales * depth)()
+    for i, (sa, sm) in enumerate(scales):
+        structs[i].scale_attn = sa.data_ptr() if sa is not None else None
+        structs[i].scale_mlp = sm.data_ptr() if sm is not None else None
+    return structs
+
+
+def _mit_sized(lib, fn, cfg):
+    need = fn(C.byref(cfg))
+    if need < 0:
+        raise _lib.CffmError('libcffm_hip: %s' % lib.cffm_last_error().decode())
+    return need
+
+
+class _MitBlocksTrainFn(torch.autograd.Function):
+    """Every block of one MiT stage, forward and backward, as one library call each (cffm_mit_blocks_train_fwd / _bwd).  Saved: x, the
+    parameters, the factors and the library's `saved` buffer (every intermediate of the forward); the backward's workspace lives only
+    inside it.  All gradients are formed by the one call, also when only some are asked for; those not asked for are dropped."""
+
+    @staticmethod
+    def forward(ctx, x, cfg, scales, *params):
+        lib = _lib.get()
+        # every input contiguous BEFORE the stream is looked up or anything is enqueued (as _LayerNormFn.forward)
+        x = _sra_operand(x)
+        params = [None if t is None else _sra_operand(t) for t in params]
+        if scales is not None:
+            scales = [tuple(None if t is None else _sra_operand(t) for t in pair) for pair in scales]
+        y = torch.empty_like(x)
+        saved = torch.empty(_mit_sized(lib, lib.cffm_mit_blocks_train_saved_floats, cfg), dtype=torch.float32, device=x.device)
+        need = _mit_sized(lib, lib.cffm_mit_blocks_train_fwd_ws_floats, cfg)
+        ws = torch.empty(need, dtype=torch.float32, device=x.device) if need else None
+        _lib.check(lib.cffm_mit_blocks_train_fwd(C.byref(cfg), _mit_block_structs(params, cfg.depth), _mit_scale_structs(scales, cfg.depth),
+                                                 _ptr(x), _ptr(y), _ptr(saved), _ptr(ws), _stream(x)), lib)
+        ctx.save_for_backward(x, saved, *params)
+        ctx.cfg, ctx.scales = cfg, scales
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        lib = _lib.get()
+        x, saved, *params = ctx.saved_tensors
+        cfg, scales = ctx.cfg, ctx.scales
+        dy = _sra_operand(dout)
+        dx = torch.empty_like(x)
+        grads = [None if t is None else torch.empty_like(t) for t in params]
+        ws = torch.empty(_mit_sized(lib, lib.cffm_mit_blocks_train_bwd_ws_floats, cfg), dtype=torch.float32, device=x.device)
+        _lib.check(lib.cffm_mit_blocks_train_bwd(C.byref(cfg), _mit_block_structs(params, cfg.depth), _mit_scale_structs(scales, cfg.depth),
+                                                 _mit_block_structs(grads, cfg.depth), _ptr(x), _ptr(saved), _ptr(dy), _ptr(dx), _ptr(ws),
+                                                 _stream(x)), lib)
+        need = ctx.needs_input_grad
+        return (dx if need[0] else None, None, None) + tuple(g if n else None for g, n in zip(grads, need[3:]))
+
+
+def mit_blocks_train(x, blocks, H, W, scales=None):
+    """Every block of one MiT stage on token rows, differentiable, as ONE library call per direction (``cffm_mit_blocks_train_fwd`` /
+    ``_bwd``): x [B, H*W, C] fp32 (what the patch embedding hands to the first block), `blocks` the stage's Block modules, all of one
+    configuration -> what the last block hands to the stage's norm.  The result and every gradient have the bits of the same blocks run op
+    by op with ``norm_impl``, ``linear_impl``, ``sr_impl``, ``attn_impl`` and ``dwconv_impl`` = 'hip'.  ``scales``: None, or a [depth, 2, B]
+    fp32 tensor -- [i, 0] / [i, 1] the factor DropPath multiplies each sample's attention / Mix-FFN branch of block i with (0 or 1 / keep)
+    -- or depth pairs of [B] tensors or None; it is detached and not differentiable.  Differentiable in x and every parameter; the modules'
+    dropouts and DropPath modules are NOT applied (the caller draws the factors).  Limits: ``mit_blocks_train_supported``.  Launches on the
+    current stream."""
+    what = 'mit_blocks_train'
+    if not isinstance(x, torch.Tensor) or x.dim() != 3:
+        raise _lib.CffmError('%s: x must be a [B, H*W, C] tensor' % what)
+    _require_device(x, what + ' x')
+    blocks = list(blocks)
+    if not blocks:
+        raise _lib.CffmError('%s: a stage needs at least one block' % what)
+    b, n, c = x.shape
+    if n != int(H) * int(W) or x.numel() == 0:
+        raise _lib.CffmError('%s: x %s is not [B, %d*%d, C]' % (what, tuple(x.shape), int(H), int(W)))
+    tensors = _mit_block_tensors(blocks)
+    nf = len(_MIT_FIELDS)
+    for i, t in enumerate(tensors):
+        name = _MIT_FIELDS[i % nf]
+        if t is None:
+            if name not in _MIT_OPTIONAL:
+                raise _lib.CffmError('%s: parameter %s is missing' % (what, name))
+            continue
+        _require_device(t, what + ' parameter')
+        if t.device != x.device:
+            raise _lib.CffmError('%s: parameter %s must be on %s' % (what, name, x.device))
+    if scales is not None:
+        if isinstance(scales, torch.Tensor):
+            if tuple(scales.shape) != (len(blocks), 2, b):
+                raise _lib.CffmError('%s: scales must be a [%d, 2, %d] tensor' % (what, len(blocks), b))
+            _require_device(scales, what + ' scales')
+            scales = scales.detach().contiguous()
+            scales = [(scales[i, 0], scales[i, 1]) for i in range(len(blocks))]
+        else:
+            scales = [tuple(pair) for pair in scales]
+            if len(scales) != len(blocks) or any(len(pair) != 2 for pair in scales):
+                raise _lib.CffmError('%s: scales must hold one (attention, Mix-FFN) pair per block' % what)
+            for t in (t for pair in scales for t in pair if t is not None):
+                _require_device(t, what + ' scales')
+                if tuple(t.shape) != (b,) or t.device != x.device:
+                    raise _lib.CffmError('%s: a factor must be a [%d] tensor on %s' % (what, b, x.device))
+            scales = [tuple(None if t is None else t.detach() for t in pair) for pair in scales]
+        if any(t is not None and t.device != x.device for pair in scales for t in pair):
+            raise _lib.CffmError('%s: scales must be on %s' % (what, x.device))
+    return _MitBlocksTrainFn.apply(x, mit_blocks_cfg(x.shape, H, W, blocks), scales, *tensors)
+
+
 # ---------------------------------------------------------------------------------------------- the overlapping patch embedding + n stages per call (inference)
 # The limits of cffm_patch_embed_fwd: a copy of pemb_check in csrc/cffm_hip.hip (stated in include/cffm_hip.h); change both together.
 PEMB_KERNELS = ((7, 4), (3, 2))
