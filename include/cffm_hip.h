@@ -324,6 +324,17 @@ int cffm_segfuse_fwd(float* y, const float* d, const float* const z[3], const in
 /* the adjoint of the three resizes: dz_m [N*h_m*w_m,256] = up_m^T g, g [N*H*W,256] (gather form, deterministic) */
 int cffm_segfuse_bwd(const float* g, float* const dz[3], const int h[3], const int w[3], int nmaps, int N, int H, int W,
                      void* stream);
+/* added under ABI 13, additive: the eval tail of a frame in one pass (streaming inference).  With y, d, z, h, w, nmaps as for
+ * cffm_segfuse_fwd (y is only read here), H and W even, and scale / shift = coef[0] / coef[1] of cffm_bn_finalize_fwd(part = NULL):
+ *   out[n, patch, :] = 0.25 * ((r00 + r01) + (r10 + r11)),   r = max((y + d + sum_m bilinear(z_m)) * scale + shift, 0)
+ * over the 2 x 2 patches of the map: rows [N, H/2 * W/2, 256] with the bits of cffm_segfuse_fwd followed by cffm_bn_relu_pool_fwd's `stack`;
+ * the pre-BN map and `fused` are never written.  out = ring + slot * slot_floats, slot = slots[which] read on the device (slots: device
+ * int[4], which in 0..3; NULL: slot 0, which = 0) and clamped there into [0, nslots): a bad table cannot address outside the ring.
+ * slot_floats >= N * H/2 * W/2 * 256, a multiple of 4.  Odd H or W, null or misaligned pointers (16 bytes; the table 4), and a ring that
+ * overlaps y, d, scale, shift or a map are errors, returned before anything is enqueued.  One launch on `stream`, no LDS, no atomics. */
+int cffm_segfuse_pool_fwd(const float* y, const float* d, const float* const z[3], const int h[3], const int w[3], int nmaps,
+                          const float* scale, const float* shift, float* ring, long slot_floats, int nslots, const int* slots, int which,
+                          int N, int H, int W, void* stream);
 
 /* ---- the head's training loss without full-resolution logits ----
  * Replaces decode_head.py:744-835's resize(seg_logit, size=label size, 'bilinear', align_corners=False) followed by
@@ -433,6 +444,15 @@ int cffm_layer_infer_rows(const cffm_geom* g, int depth, const cffm_block_params
                           float* y_rows, const int* key_src, const int* q_dst, float* ws, void* stream);
 int cffm_layer_infer_full(const cffm_geom* g, int depth, const cffm_block_params* params, const float* prepared, const float* x_nchw,
                           float* y_full_nchw, const int* key_src, const int* q_dst, float* ws, void* stream);
+/* added under ABI 13, additive: cffm_layer_infer_rows on four frames that lie in a ring of per-frame row buffers (streaming inference).
+ * Frame t (0..3, the target last) of sample b is ring + clamp(slots[t], 0, nslots - 1) * slot_floats + b * frame_bs, [HW,256] floats;
+ * slots is a DEVICE int[4] read by the kernels, entries may repeat.  No pointer argument depends on the table, so a captured call is
+ * replayed for other frames by rewriting the table.  The target frame is also block 0's residual.  Same prepared data, same workspace
+ * (cffm_layer_infer_ws_floats), every launch on `stream`; the ring is only read.  y_rows or ws inside the ring is an error.  With
+ * ring = x_rows, slot_floats = HW * 256, nslots = 4, slots = {0,1,2,3} and frame_bs = 4 * HW * 256 the call is cffm_layer_infer_rows. */
+int cffm_layer_infer_rows_ring(const cffm_geom* g, int depth, const cffm_block_params* params, const float* prepared, const float* ring,
+                               long slot_floats, int nslots, const int* slots, long frame_bs, float* y_rows, const int* key_src,
+                               const int* q_dst, float* ws, void* stream);
 
 /* ---- `linear_fuse`'s BatchNorm + ReLU and the 1/4 -> 1/8 resize that builds the clip stack (cffm_head.py:119, :131-135), on token
  * rows [pixels,256].  With even H, W the bilinear 1/2 resize (align_corners=False) is exactly a 2x2 average.

@@ -14,6 +14,7 @@ from . import optim  # noqa: F401,E402
 from . import distributed  # noqa: F401,E402
 from . import evaluation  # noqa: F401,E402
 from . import segmentor  # noqa: F401,E402  (registers EncoderDecoder_clips)
+from .stream import ClipStream  # noqa: F401,E402
 from . import backbone  # noqa: F401,E402  (registers mit_b0 ... mit_b5)
 from .registry import (BACKBONES, HEADS, LOSSES, NECKS, SEGMENTORS, Registry, build_backbone,  # noqa: F401,E402
                        build_from_cfg, build_head, build_loss, build_neck, build_segmentor)

@@ -198,13 +198,32 @@ __device__ __forceinline__ int frame_group(int frame) { return frame == 3 ? 0 : 
 // INFER = true: the forward of a call that keeps nothing for a backward (the inference forward of the layer) -- mean_out / rstd_out are
 // not written and the pooling matrix always comes prepared (M != NULL; pw is not read).  Selected at compile time: the training
 // instantiation is the kernel it was, and the arithmetic of the two is the same, instruction for instruction.
-template <bool INFER>
+// RING = true (a new instantiation; the two forms above are the kernels they were): the four frames lie in a ring of per-frame row
+// buffers -- x_ref = the ring, frame t of sample b at x_ref + clamp(rg.slots[t]) * rg.slot_floats + b * ref_bs; the table is device memory,
+// so a captured launch serves any four slots, and every entry is clamped into [0, rg.nslots): no table can address outside the ring.
+// x_tgt == NULL: the target is frame 3 of the table (block 0); otherwise the block before's rows, as in the other forms.  In block 0 the
+// target's rows, each read exactly once by the launch, are also copied to rg.tgt_copy [B,HW,256]: the residual k_mlp_fwd adds sits at an
+// address its arguments can name, so that kernel is not touched and no host pointer depends on the table.
+struct LnpNoRing {};
+struct LnpRing { const int* slots; long slot_floats; int nslots; float* tgt_copy; };
+template <bool RING> struct LnpRingArg { typedef LnpNoRing type; };
+template <> struct LnpRingArg<true> { typedef LnpRing type; };
+__device__ __forceinline__ const float* lnp_ring_frame(const float* ring, const LnpRing& rg, int frame, long b, long frame_bs) {
+    int s = rg.slots[frame];
+    s = s < 0 ? 0 : (s > rg.nslots - 1 ? rg.nslots - 1 : s);
+    return ring + (long)s * rg.slot_floats + b * frame_bs;
+}
+__device__ __forceinline__ const float* lnp_ring_frame(const float*, const LnpNoRing&, int, long, long) { return nullptr; }
+__device__ __forceinline__ void lnp_ring_keep(const LnpRing& rg, long row, int lane, const f32x4& v) { *(f32x4*)(rg.tgt_copy + row * CFFM_C + 4 * lane) = v; }
+__device__ __forceinline__ void lnp_ring_keep(const LnpNoRing&, long, int, const f32x4&) {}
+template <bool INFER, bool RING = false>
 __global__ void __launch_bounds__(LNP_THREADS, 6) k_ln_pool_fwd(Geo G, const float* __restrict__ x_ref, long ref_bs,
                                                       const float* __restrict__ x_tgt, long tgt_bs,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
                                                       const float* __restrict__ M /* or NULL: built here from pw */, PoolW pw, PoolB pb,
                                                       float* __restrict__ zall, float* __restrict__ mean_out,
-                                                      float* __restrict__ rstd_out, int split /* zall rows in split-4 storage */) {
+                                                      float* __restrict__ rstd_out, int split /* zall rows in split-4 storage */,
+                                                      typename LnpRingArg<RING>::type rg) {
     __shared__ float sM[9 * CFFM_WA];
     __shared__ float red[4][9][CFFM_C];              // (eight waves: the upper four add into the lower four's rows)
     const int w = blockIdx.x, frame = blockIdx.y, b = blockIdx.z;
@@ -216,7 +235,9 @@ __global__ void __launch_bounds__(LNP_THREADS, 6) k_ln_pool_fwd(Geo G, const flo
     for (int e = threadIdx.x; e < ncell * CFFM_WA; e += LNP_THREADS)
         sM[e] = (INFER || M) ? M[g0 * CFFM_WA + e] : pool_matrix_entry(pw, g0 + e / CFFM_WA, e % CFFM_WA);
     __syncthreads();
-    const float* xf = (frame == 3) ? x_tgt + (long)b * tgt_bs : x_ref + (long)b * ref_bs + (long)frame * G.HW * CFFM_C;
+    const float* xf;
+    if (RING) xf = (frame == 3 && x_tgt) ? x_tgt + (long)b * tgt_bs : lnp_ring_frame(x_ref, rg, frame, b, ref_bs);
+    else xf = (frame == 3) ? x_tgt + (long)b * tgt_bs : x_ref + (long)b * ref_bs + (long)frame * G.HW * CFFM_C;
     const f32x4 gm = *(const f32x4*)(gamma + 4 * lane), bt = *(const f32x4*)(beta + 4 * lane);
     f32x4 acc[9];
 #pragma unroll
@@ -242,6 +263,7 @@ __global__ void __launch_bounds__(LNP_THREADS, 6) k_ln_pool_fwd(Geo G, const flo
             if (valid) {
                 const long pix = (long)y * G.W0 + x;
                 const f32x4 xv = xr[kk];
+                if (RING && frame == 3 && !x_tgt) lnp_ring_keep(rg, (long)b * G.HW + pix, lane, xv);
                 const float mu = wave_sum(xv[0] + xv[1] + xv[2] + xv[3]) * (1.f / CFFM_C);
                 const f32x4 d = xv - mu;
                 const float var = wave_sum(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]) * (1.f / CFFM_C);

@@ -644,7 +644,7 @@ static int ln_pool_fwd_impl(const cffm_geom* g, const float* x_ref, long ref_bs,
     PoolW pw;
     for (int i = 0; i < 4; ++i) { pb.b[i] = pool_b[i]; pw.w[i] = pool_w ? pool_w[i] : nullptr; }
     CFFM_LAUNCH(k_ln_pool_fwd<false>, (g->nW, 4, g->B), (LNP_THREADS), 0, (hipStream_t)stream, to_geo(g), x_ref, ref_bs, x_tgt, tgt_bs, gamma,
-                beta, pool_w ? nullptr : M, pw, pb, zall, mean, rstd, split);
+                beta, pool_w ? nullptr : M, pw, pb, zall, mean, rstd, split, LnpNoRing());
     CHECK_LAUNCH("ln_pool_fwd");
     return 0;
 }
@@ -2032,7 +2032,7 @@ int cffm_segfuse_fwd(float* y, const float* d, const float* const z[3], const in
     REQUIRE(rows < (1L << 31), "segfuse_fwd: too many output pixels");
     hipStream_t st = (hipStream_t)stream;
     const long patches = (long)N * ((H + 1) / 2) * ((W + 1) / 2);
-    CFFM_LAUNCH(k_segfuse_fwd, ((unsigned)((patches + 3) / 4)), (256), 0, st, y, d, mp, N, H, W);
+    CFFM_LAUNCH(k_segfuse_fwd<false>, ((unsigned)((patches + 3) / 4)), (256), 0, st, y, d, mp, N, H, W, SegfNoPool());
     CHECK_LAUNCH("segfuse_fwd");
     return 0;
 }
@@ -2068,6 +2068,41 @@ int cffm_segfuse_bwd(const float* g, float* const dz[3], const int h[3], const i
     hipStream_t st = (hipStream_t)stream;
     CFFM_LAUNCH(k_segfuse_bwd, ((unsigned)blocks), (256), 0, st, g, mp, N, H, W);
     CHECK_LAUNCH("segfuse_bwd");
+    return 0;
+}
+// [a, a + na) and [b, b + nb) floats share an address
+static bool spans_overlap(const float* a, long na, const float* b, long nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return na > 0 && nb > 0 && a0 < b0 + (uintptr_t)nb * sizeof(float) && b0 < a0 + (uintptr_t)na * sizeof(float);
+}
+// the eval tail of a frame in one pass (k_segfuse_fwd<true>, "k_segfuse_pool_fwd"): y, d and the maps as for cffm_segfuse_fwd, but y is only
+// read; the pooled rows go to slot clamp(slots[which]) of the ring
+int cffm_segfuse_pool_fwd(const float* y, const float* d, const float* const z[3], const int h[3], const int w[3], int nmaps,
+                          const float* scale, const float* shift, float* ring, long slot_floats, int nslots, const int* slots, int which,
+                          int N, int H, int W, void* stream) {
+    REQUIRE(y && d && scale && shift && ring && N >= 0 && (nmaps == 0 || (z && h && w)), "segfuse_pool_fwd: bad arguments (null pointer)");
+    REQUIRE(H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "segfuse_pool_fwd: even map sides expected, got %dx%d", H, W);
+    SegfMaps mp;
+    TRY(segf_maps(mp, h, w, nmaps, H, W, "segfuse_pool_fwd"));
+    for (int m = 0; m < nmaps; ++m) { REQUIRE(z[m], "segfuse_pool_fwd: null map"); mp.z[m] = z[m]; }
+    const long rows = (long)N * H * W, patches = rows / 4, out_floats = patches * SEGF_C;
+    REQUIRE(rows < (1L << 31), "segfuse_pool_fwd: too many output pixels");
+    REQUIRE(nslots >= 1 && slot_floats >= out_floats && slot_floats % 4 == 0, "segfuse_pool_fwd: %d slots of %ld floats for %ld floats of rows",
+            nslots, slot_floats, out_floats);
+    REQUIRE(which >= 0 && (slots ? which < 4 : which == 0), "segfuse_pool_fwd: table index %d", which);
+    bool aligned = !(((uintptr_t)y | (uintptr_t)d | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)ring) & 15) && !((uintptr_t)slots & 3);
+    for (int m = 0; m < nmaps; ++m) aligned = aligned && !((uintptr_t)z[m] & 15);
+    REQUIRE(aligned, "segfuse_pool_fwd: pointers must be 16-byte aligned (the slot table: 4)");
+    // the ring as a whole (any slot may be the one written) must not share memory with anything the launch reads
+    const long ring_floats = (long)(nslots - 1) * slot_floats + out_floats;
+    bool clash = spans_overlap(ring, ring_floats, y, rows * SEGF_C) || spans_overlap(ring, ring_floats, d, SEGF_C) ||
+                 spans_overlap(ring, ring_floats, scale, SEGF_C) || spans_overlap(ring, ring_floats, shift, SEGF_C);
+    for (int m = 0; m < nmaps; ++m) clash = clash || spans_overlap(ring, ring_floats, z[m], (long)N * h[m] * w[m] * SEGF_C);
+    REQUIRE(!clash, "segfuse_pool_fwd: the ring overlaps an input");
+    if (!patches) return 0;
+    const SegfPool pa = {scale, shift, ring, slot_floats, nslots, slots, which};
+    CFFM_LAUNCH(k_segfuse_fwd<true>, ((unsigned)((patches + 3) / 4)), (256), 0, (hipStream_t)stream, const_cast<float*>(y), d, mp, N, H, W, pa);
+    CHECK_LAUNCH("segfuse_pool_fwd");
     return 0;
 }
 
@@ -2586,7 +2621,10 @@ int cffm_layer_prepare(int depth, const cffm_block_params* params, float* prepar
 // the blocks of one call: `stack` = NHWC frames [B,4,HW,256]; the last block's output rows [B,HW,256] go to `y_rows`, or (y_rows NULL) as
 // NCHW images y_bs floats apart to `y_nchw` (k_mlp_fwd's NCHW form)
 static int layer_infer_blocks(const cffm_geom* g, int depth, const cffm_block_params* params, const float* prepared, const float* stack,
-                              float* y_rows, const int* key_src, const int* q_dst, float* ws, void* stream, float* y_nchw = nullptr, long y_bs = 0) {
+                              float* y_rows, const int* key_src, const int* q_dst, float* ws, void* stream, float* y_nchw = nullptr, long y_bs = 0,
+                              const LnpRing* ring = nullptr, long frame_bs = 0) {
+    // ring != NULL: `stack` is a ring of frame buffers and the four frames are those of ring->slots (k_ln_pool_fwd<true, true>); block 0's
+    // residual rows are the copy that launch leaves in the x2 buffer no block touches before block 1 writes it
     REQUIRE(!infer_lds_grant(), "layer_infer: LDS grant failed");
     const PreparedLayout P = prepared_layout();
     const InferWs W = infer_ws_layout(g);
@@ -2598,15 +2636,22 @@ static int layer_infer_blocks(const cffm_geom* g, int depth, const cffm_block_pa
         const cffm_block_params* p = &params[i];
         const float* pre = prepared + (long)i * P.total;
         const float* wf = pre + P.w_frag;
-        const float* tgt = (i == 0) ? stack + 3 * img : ws + W.x2[(i - 1) & 1];
-        const long tgt_bs = (i == 0) ? 4 * img : img;
+        const bool ring0 = ring && i == 0;
+        const float* tgt = ring0 ? ws + W.x2[1] : (i == 0) ? stack + 3 * img : ws + W.x2[(i - 1) & 1];
+        const long tgt_bs = (i == 0 && !ring) ? 4 * img : img;
         float* x2 = (i == depth - 1) ? y_rows : ws + W.x2[i & 1];
         {
             PROF(ST_LN_POOL_FWD);
             PoolB pb;
             for (int q = 0; q < 4; ++q) pb.b[q] = p->pool_b[q];
-            CFFM_LAUNCH(k_ln_pool_fwd<true>, (g->nW, 4, g->B), (LNP_THREADS), 0, st, G, stack, 4 * img, tgt, tgt_bs, p->norm1_w, p->norm1_b, pre + P.M,
-                        PoolW(), pb, ws + W.zall, nullptr, nullptr, 1);
+            if (ring) {
+                LnpRing rg = *ring;
+                rg.tgt_copy = ws + W.x2[1];
+                CFFM_LAUNCH((k_ln_pool_fwd<true, true>), (g->nW, 4, g->B), (LNP_THREADS), 0, st, G, stack, frame_bs, ring0 ? nullptr : tgt, tgt_bs,
+                            p->norm1_w, p->norm1_b, pre + P.M, PoolW(), pb, ws + W.zall, nullptr, nullptr, 1, rg);
+            } else
+                CFFM_LAUNCH(k_ln_pool_fwd<true>, (g->nW, 4, g->B), (LNP_THREADS), 0, st, G, stack, 4 * img, tgt, tgt_bs, p->norm1_w, p->norm1_b,
+                            pre + P.M, PoolW(), pb, ws + W.zall, nullptr, nullptr, 1, LnpNoRing());
         }
         {
             PROF(ST_GEMM); PROF2(ST_G_QKV_FWD);
@@ -2649,6 +2694,24 @@ int cffm_layer_infer_rows(const cffm_geom* g, int depth, const cffm_block_params
                           const int* key_src, const int* q_dst, float* ws, void* stream) {
     TRY(layer_infer_check(g, depth, params, prepared, x_rows, y_rows, key_src, q_dst, ws, "layer_infer_rows"));
     return layer_infer_blocks(g, depth, params, prepared, x_rows, y_rows, key_src, q_dst, ws, stream);
+}
+// The four frames where a ring of per-frame row buffers holds them: frame t of sample b = ring + clamp(slots[t]) * slot_floats + b * frame_bs
+// (slots: device int[4], the target last; entries may repeat).  No pointer argument depends on the table: a captured call is replayed for
+// other frames by rewriting the 16 bytes of the table.  Otherwise cffm_layer_infer_rows: same workspace, same prepared data, one stream.
+int cffm_layer_infer_rows_ring(const cffm_geom* g, int depth, const cffm_block_params* params, const float* prepared, const float* ring,
+                               long slot_floats, int nslots, const int* slots, long frame_bs, float* y_rows, const int* key_src,
+                               const int* q_dst, float* ws, void* stream) {
+    TRY(layer_infer_check(g, depth, params, prepared, ring, y_rows, key_src, q_dst, ws, "layer_infer_rows_ring"));
+    const long img = (long)g->HW * CFFM_C;
+    REQUIRE(slots && !((uintptr_t)slots & 3) && !((uintptr_t)ring & 15), "layer_infer_rows_ring: null or misaligned slot table / ring");
+    // (a slot may be shorter than a batch of frames: with slot_floats = img and frame_bs = 4 img the ring is the stack of cffm_layer_infer_rows)
+    REQUIRE(nslots >= 1 && frame_bs >= img && frame_bs % 4 == 0 && slot_floats % 4 == 0 && slot_floats >= img,
+            "layer_infer_rows_ring: %d slots of %ld floats, frames %ld apart, for %d frames of %ld floats", nslots, slot_floats, frame_bs, g->B, img);
+    const long ring_floats = (long)(nslots - 1) * slot_floats + (long)(g->B - 1) * frame_bs + img;
+    REQUIRE(!spans_overlap(ring, ring_floats, y_rows, (long)g->B * img), "layer_infer_rows_ring: y_rows lies inside the ring");
+    REQUIRE(!spans_overlap(ring, ring_floats, ws, infer_ws_layout(g).total), "layer_infer_rows_ring: the workspace lies inside the ring");
+    LnpRing rg = {slots, slot_floats, nslots, nullptr};
+    return layer_infer_blocks(g, depth, params, prepared, ring, y_rows, key_src, q_dst, ws, stream, nullptr, 0, &rg, frame_bs);
 }
 // The reference's whole output [B,4,C,H,W].  The NHWC stack the blocks read needs as much room as the output has: it is built IN
 // y_full (so the workspace stays what the rows form needs) and y_full gets its real contents when the last block is done -- frames

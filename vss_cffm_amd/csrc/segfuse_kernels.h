@@ -54,7 +54,40 @@ struct SegfMaps {
 // 2 x 2), which is loaded once for the four pixels -- ~5 row loads per pixel instead of 13 (one wave per pixel was bound by
 // the per-CU L1 rate of those loads: 79 us).  Rows / columns of the neighbourhood no pixel taps are skipped (wave-uniform).
 // grid (ceil(N * ceil(H/2) * ceil(W/2) / 4)); every XCD (workgroup b runs on XCD b % 8) owns a contiguous run of patches.
-__global__ void __launch_bounds__(256) k_segfuse_fwd(float* __restrict__ y, const float* __restrict__ d, SegfMaps mp, int N, int H, int W) {
+//
+// POOL = true (a new instantiation, "k_segfuse_pool_fwd"; <false> is the kernel it was, instruction for instruction): the eval tail of a
+// frame in the same pass (H, W even).  y is only read, and instead of the sums the wave writes one row of the 1/8 clip stack,
+//     out[n, patch, :] = 0.25 * ((r00 + r01) + (r10 + r11)),   r = max(acc * scale + shift, 0)
+// -- the eval BatchNorm, the ReLU and the 1/4 -> 1/8 average of k_bn_relu_pool_fwd on the patch (its wave w is pixel (w >> 1, w & 1): the
+// same parenthesisation; its `y * sc + sh` is fed the rounded sum, as here), so the rows have the bits of that pair's `stack` while neither
+// the pre-BN map nor `fused` is written.  The patch arithmetic is ONE text for both forms -- selected by a template parameter, not a
+// run-time branch and not a helper function (a helper changed k_segfuse_fwd's registers: 96 -> 98 / 100 VGPRs, five waves -> four).
+// out = ring + slot * slot_floats: the slot comes from a device table (slots[which], NULL: 0), so that a captured launch can be replayed
+// for another slot, and is clamped into [0, nslots) -- whatever the table holds, the rows land inside the ring.  No LDS, no atomics.
+struct SegfNoPool {};
+struct SegfPool { const float* scale; const float* shift; float* ring; long slot_floats; int nslots; const int* slots; int which; };
+template <bool POOL> struct SegfPoolArg { typedef SegfNoPool type; };
+template <> struct SegfPoolArg<true> { typedef SegfPool type; };
+__device__ __forceinline__ void segf_pool_store(const SegfPool& pa, const f32x4 (&acc)[2][2], long patch, int lane) {
+    const f32x4 sc = ((const f32x4*)pa.scale)[lane], sh = ((const f32x4*)pa.shift)[lane];
+    f32x4 r[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            f32x4 v = acc[a][b] * sc + sh;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+            r[a][b] = v;
+        }
+    int slot = pa.slots ? pa.slots[pa.which] : 0;
+    slot = slot < 0 ? 0 : (slot > pa.nslots - 1 ? pa.nslots - 1 : slot);
+    ((f32x4*)(pa.ring + (long)slot * pa.slot_floats + patch * SEGF_C))[lane] = ((r[0][0] + r[0][1]) + (r[1][0] + r[1][1])) * 0.25f;
+}
+__device__ __forceinline__ void segf_pool_store(const SegfNoPool&, const f32x4 (&)[2][2], long, int) {}
+template <bool POOL = false>
+__global__ void __launch_bounds__(256) k_segfuse_fwd(float* __restrict__ y, const float* __restrict__ d, SegfMaps mp, int N, int H, int W,
+                                                     typename SegfPoolArg<POOL>::type pa) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ph = (H + 1) / 2, pw = (W + 1) / 2;
     const long patch = (long)xcd_linear_id() * 4 + wave;
@@ -114,6 +147,10 @@ __global__ void __launch_bounds__(256) k_segfuse_fwd(float* __restrict__ y, cons
                 }
                 acc[a][b] += sum;
             }
+    }
+    if (POOL) {           // (H, W even: the patch is whole, and its index is the output row)
+        segf_pool_store(pa, acc, patch, lane);
+        return;
     }
     ((f32x4*)yb)[lane] = acc[0][0];
     if (vx) ((f32x4*)(yb + SEGF_C))[lane] = acc[0][1];

@@ -25,7 +25,8 @@ import torch.nn.functional as F
 from .modules import BasicLayer3d3, BasicLayer_cluster
 from . import _lib
 from .cluster import kmeans
-from .ops import bn_relu_pool, cat_into, cat_room, conv1x1, frame_logits_cat, late_params, head_cross_entropy, resize_cross_entropy, rows_resize, segformer_fuse
+from .ops import (bn_relu_pool, cat_into, cat_room, conv1x1, frame_logits_cat, late_params, head_cross_entropy, resize_cross_entropy, rows_resize,
+                  segformer_fuse, segformer_fuse_pool)
 from .registry import HEADS, LOSSES, build_loss
 
 
@@ -349,9 +350,52 @@ class _CffmHeadBase(BaseDecodeHead_clips_flow):
             return rows.permute(0, 1, 4, 2, 3)
         return torch.cat([x, x2], 1)
 
+    # ------------------------------------------------------------------ streaming inference (stream.ClipStream): a frame at a time
+    # In eval mode everything in front of the layer acts on each frame alone, and all the layer needs of a frame is its 1/8 stack rows.
+    # So a frame is encoded ONCE, into its slot of a ring [R,B,h/2*w/2,256] on the device (stream_rows), and the tail of `_forward_rows`
+    # reads its four frames where they lie (forward_stream).  The slot numbers come from a device table: no launch argument changes
+    # from frame to frame.
+    can_stream = False      # the heads with a forward_stream set it
+
+    def stream_rows(self, inputs, ring, slots, which):
+        """One frame's backbone features -> its stack rows in ``ring[slots[which]]`` (ops.segformer_fuse_pool: one pass from the embeddings
+        to the rows; the pre-BatchNorm map, `fused` and the frame logits of the clip path are not computed)."""
+        if self.training:
+            raise RuntimeError('stream_rows is the eval path of the head: call head.eval() first')
+        c1, c2, c3, c4 = self._transform_inputs(inputs)
+        lins = (self.linear_c1, self.linear_c2, self.linear_c3, self.linear_c4)
+        return segformer_fuse_pool([c1, c2, c3, c4], [l.proj.weight for l in lins], [l.proj.bias for l in lins], self.linear_fuse.conv.weight,
+                                   self.linear_fuse.bn, ring, slots, which)
+
+    def _stream_clip(self, ring, slots, h, w):
+        """-> (the target frame's rows [B,h2*w2,256] -- gathered on the device: no host read of the table --, the clip-level logits x2)"""
+        if self.training:
+            raise RuntimeError('forward_stream is the eval path of the head: call head.eval() first')
+        b, (h2, w2) = ring.shape[1], (h // 2, w // 2)
+        with torch.no_grad():
+            tgt = ring.index_select(0, slots[3:].long().clamp(0, ring.shape[0] - 1))[0]
+            mined = self.decoder_focal.forward_rows_ring(ring, slots, h2, w2)                    # [B, h2*w2, 256]
+            x2 = self._rows_logits(self.linear_pred2, torch.cat([tgt, mined], dim=-1).view(b, h2, w2, -1), self.dropout, (h, w))
+        return tgt, x2
+
+    def forward_stream(self, ring, slots, h, w, img_metas=None):
+        """[B,K,h,w] logits of the frame in ``ring[slots[3]]`` from the clip ``ring[slots[0..3]]`` (h, w: the 1/4-scale map's size):
+        the eval tail of `_forward_rows`."""
+        raise NotImplementedError('%s has no streaming forward' % type(self).__name__)
+
+    def _stream_tail_torch(self, stack, size, img_metas=None):
+        """the same tail in stock ops on cached per-frame maps: stack [B,4,256,h/2,w/2] -> [B,K,h,w] (the A/B partner of forward_stream)"""
+        x2 = self._clip_logits(stack, self.decoder_focal(stack), size)
+        return x2.squeeze(1)
+
 
 @HEADS.register_module()
 class CFFMHead_clips_resize1_8(_CffmHeadBase):
+    can_stream = True
+
+    def forward_stream(self, ring, slots, h, w, img_metas=None):
+        return self._stream_clip(ring, slots, h, w)[1].squeeze(1)
+
     def _forward_rows(self, inputs, batch_size, num_clips):
         # (the frame classifier's parameters as they will be used at the END of the forward, through a node created FIRST: its backward runs
         #  late and joins the deferred branch before autograd accumulates their gradients -- ops._LateGradFn)
@@ -421,6 +465,12 @@ class CFFMHead_clips_resize1_8_gene_prototype(_CffmHeadBase):
         video = img_metas[0]['filename'].split('/')[-3]
         os.makedirs(self.save_path + video, exist_ok=True)
         torch.save(centers, self.save_path + video + '/centers.pt')
+
+    def stream_rows(self, inputs, ring, slots, which):
+        raise NotImplementedError('the prototype-generating head clusters whole clips: it has no streaming forward')
+
+    def _stream_tail_torch(self, stack, size, img_metas=None):
+        raise NotImplementedError('the prototype-generating head clusters whole clips: it has no streaming forward')
 
     def _forward_rows(self, inputs, batch_size, num_clips, img_metas):
         """Eval on token rows: the clip stack `_rows_front` leaves as [B*T, h2*w2, 256] rows IS the [T*h2*w2, 256] point matrix of a clip
@@ -519,6 +569,28 @@ class CFFMHead_clips_resize1_8_finetune_w_prototype3(_CffmHeadBase):
         if not self.training:
             return x2.squeeze(1) + 0.5 * x3.squeeze(1)
         return self._rows_cat(x, x3)
+
+    can_stream = True
+
+    def forward_stream(self, ring, slots, h, w, img_metas=None):
+        """`_forward_rows`'s eval tail: the clip-level logits plus half the prototype layer's on the target frame's rows"""
+        b, (h2, w2) = ring.shape[1], (h // 2, w // 2)
+        assert b == len(img_metas)
+        centers = self._load_centers(img_metas, ring.device)
+        tgt, x2 = self._stream_clip(ring, slots, h, w)
+        with torch.no_grad():
+            ctx = self.decoder_swin(tgt.contiguous(), h2, w2, centers)[0]                       # [B, h2*w2, C]
+            x3 = self._rows_logits(self.linear_pred3, ctx.reshape(b, h2, w2, -1), self.dropout3, (h, w))
+        return x2.squeeze(1) + 0.5 * x3.squeeze(1)
+
+    def _stream_tail_torch(self, stack, size, img_metas=None):
+        centers = self._load_centers(img_metas, stack.device)
+        x2 = self._clip_logits(stack, self.decoder_focal(stack), size)
+        b, _, c, h2, w2 = stack.shape
+        ctx = self.decoder_swin(stack[:, -1].permute(0, 2, 3, 1).reshape(b, h2 * w2, c), h2, w2, centers)[0]
+        ctx = ctx.reshape(b, h2, w2, c).permute(0, 3, 1, 2)
+        x3 = resize(self._classify(self.linear_pred3, self.dropout3(ctx)), size=size, mode='bilinear', align_corners=False)
+        return x2.squeeze(1) + 0.5 * x3
 
     def forward(self, inputs, batch_size=None, num_clips=None, imgs=None, img_metas=None):
         assert batch_size == len(img_metas)

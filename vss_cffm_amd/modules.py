@@ -186,6 +186,14 @@ class BasicLayer3d3(nn.Module):
             return ops.cffm_layer_rows_infer(x_rows, h, w, self.depth, params, self._prepared(params))
         return ops.cffm_layer_rows(x_rows, h, w, self.depth, params)
 
+    def forward_rows_ring(self, ring, slots, h, w):
+        """forward_rows on four frames where a ring of per-frame rows holds them (streaming inference): ring [R, B, h*w, 256], frame t of
+        the clip (the target last) = ring[slots[t]], slots a device int32 [4] -> the new target frame [B, h*w, 256].  Inference only."""
+        params = [p for blk in self.blocks for p in blk.param_list()]
+        if not self._records_nothing(ring, params):
+            raise RuntimeError('forward_rows_ring is inference only: call it under torch.no_grad()')
+        return ops.cffm_layer_rows_ring(ring, slots, h, w, self.depth, params, self._prepared(params))
+
 
 # ------------------------------------------------------------------------------------------- CFFM++
 class WindowAttention_cluster(nn.Module):

@@ -315,6 +315,40 @@ def _to_rows(lib, x):
 
 
 # ---------------------------------------------------------------------------------------------- SegFormer embedding
+def _segfuse_chains(lib, d, ca):
+    """What _SegFuseFn.forward and segformer_fuse_pool share: operands checked, every scale embedded at its own resolution with its composed
+    matrix -> (d, feats, mats, toks, zs, the three small maps' (pointers, heights, widths) as the C ABI takes them)."""
+    k = len(ca) // 2
+    feats, mats = ca[:k], [a.contiguous() for a in ca[k:]]
+    if not 1 <= k <= 4:
+        raise _lib.CffmError('segformer_fuse: 1..4 feature maps expected, got %d' % k)
+    for c in feats + tuple(mats) + (d,):
+        _require_device(c, 'segformer_fuse operand')
+    n = feats[0].shape[0]
+    st, dev = _stream(feats[0]), feats[0].device
+    for c, a in zip(feats, mats):
+        if c.dim() != 4 or c.shape[0] != n or a.shape != (256, c.shape[1]):
+            raise _lib.CffmError('segformer_fuse: feature %s does not fit matrix %s' % (tuple(c.shape), tuple(a.shape)))
+    # prepare: plain-NCHW copies of strided features (on the caller's stream: in front of the mark), token rows [N*h*w, C_i], products
+    cs, d = [c.contiguous() for c in feats], d.contiguous()
+    pix = [c.shape[2] * c.shape[3] for c in cs]
+    toks = [torch.empty(n * p, c.shape[1], dtype=torch.float32, device=dev) for c, p in zip(cs, pix)]
+    zs = [torch.empty(n * p, 256, dtype=torch.float32, device=dev) for p in pix]
+    hs = (C.c_int * 3)(*([c.shape[2] for c in feats[1:]] + [1] * (4 - k)))
+    ws = (C.c_int * 3)(*([c.shape[3] for c in feats[1:]] + [1] * (4 - k)))
+    zp = (C.c_void_p * 3)(*([z.data_ptr() for z in zs[1:]] + [None] * (4 - k)))
+    # every scale is an independent chain NCHW -> token rows -> Linear: the 1/4-scale one (three quarters of the bytes) on the caller's
+    # stream, the others on branches beside it (one stream: 107 us of a replayed head step for 64 us of the largest chain)
+    with _branches(lib, st) as take:
+        for i, (c, a, t, z, p) in enumerate(zip(cs, mats, toks, zs, pix)):
+            if n * p:
+                ci = c.shape[1]
+                s = take(i) if i else st
+                _lib.check(lib.cffm_transpose(_ptr(c), _ptr(t), n, ci, p, ci * p, ci * p, s), lib)
+                _lib.check(lib.cffm_linear_fwd(_ptr(t), _ptr(a), _ptr(z), n * p, 256, ci, s), lib)
+    return d, feats, mats, toks, zs, (zp, hs, ws)
+
+
 class _SegFuseFn(torch.autograd.Function):
     """sum_i resize_i(A_i c_i) + d on token rows: features c_i [N,C_i,h_i,w_i] (c_0 at the output resolution), composed
     matrices A_i [256,C_i], constant d [256] -> [N,256,H,W] (channels-last memory).  See csrc/segfuse_kernels.h."""
@@ -322,34 +356,10 @@ class _SegFuseFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, d, *ca):
         lib = _lib.get()
-        k = len(ca) // 2
-        feats, mats = ca[:k], [a.contiguous() for a in ca[k:]]
-        if not 1 <= k <= 4:
-            raise _lib.CffmError('segformer_fuse: 1..4 feature maps expected, got %d' % k)
-        for c in feats + tuple(mats) + (d,):
-            _require_device(c, 'segformer_fuse operand')
+        d, feats, mats, toks, zs, (zp, hs, ws) = _segfuse_chains(lib, d, ca)
+        k = len(feats)
         n, _, H, W = feats[0].shape
-        st, dev = _stream(feats[0]), feats[0].device
-        for c, a in zip(feats, mats):
-            if c.dim() != 4 or c.shape[0] != n or a.shape != (256, c.shape[1]):
-                raise _lib.CffmError('segformer_fuse: feature %s does not fit matrix %s' % (tuple(c.shape), tuple(a.shape)))
-        # prepare: plain-NCHW copies of strided features (on the caller's stream: in front of the mark), token rows [N*h*w, C_i], products
-        cs, d = [c.contiguous() for c in feats], d.contiguous()
-        pix = [c.shape[2] * c.shape[3] for c in cs]
-        toks = [torch.empty(n * p, c.shape[1], dtype=torch.float32, device=dev) for c, p in zip(cs, pix)]
-        zs = [torch.empty(n * p, 256, dtype=torch.float32, device=dev) for p in pix]
-        hs = (C.c_int * 3)(*([c.shape[2] for c in feats[1:]] + [1] * (4 - k)))
-        ws = (C.c_int * 3)(*([c.shape[3] for c in feats[1:]] + [1] * (4 - k)))
-        zp = (C.c_void_p * 3)(*([z.data_ptr() for z in zs[1:]] + [None] * (4 - k)))
-        # every scale is an independent chain NCHW -> token rows -> Linear: the 1/4-scale one (three quarters of the bytes) on the caller's
-        # stream, the others on branches beside it (one stream: 107 us of a replayed head step for 64 us of the largest chain)
-        with _branches(lib, st) as take:
-            for i, (c, a, t, z, p) in enumerate(zip(cs, mats, toks, zs, pix)):
-                if n * p:
-                    ci = c.shape[1]
-                    s = take(i) if i else st
-                    _lib.check(lib.cffm_transpose(_ptr(c), _ptr(t), n, ci, p, ci * p, ci * p, s), lib)
-                    _lib.check(lib.cffm_linear_fwd(_ptr(t), _ptr(a), _ptr(z), n * p, 256, ci, s), lib)
+        st = _stream(feats[0])
         y = zs[0]                                                             # updated in place: nothing else needs it
         if n * H * W:
             _lib.check(lib.cffm_segfuse_fwd(_ptr(y), _ptr(d), zp, hs, ws, k - 1, n, H, W, st), lib)
@@ -487,6 +497,51 @@ def segformer_fuse(feats, lin_w, lin_b, fuse_w):
             raise _lib.CffmError('segformer_fuse: embedding bias %s, [%d] expected' % (tuple(b_.shape), e))
     *mats, d = _ComposeFn.apply(fuse_w.reshape(e, k * e), *lin_w, *lin_b)
     return _SegFuseFn.apply(d, *feats, *mats)
+
+
+def _check_ring(ring, slots, what):
+    """a frame ring [R,B,rows,256] (fp32, contiguous) and its slot table (int32 [4], same device)"""
+    _require_device(ring, what + ' ring')
+    if ring.dim() != 4 or ring.shape[3] != 256 or ring.shape[0] < 1 or not ring.is_contiguous():
+        raise _lib.CffmError('%s: a contiguous ring [R,B,rows,256] with R >= 1 expected, got %s' % (what, tuple(ring.shape)))
+    if slots.dtype != torch.int32 or tuple(slots.shape) != (4,) or slots.device != ring.device or not slots.is_contiguous():
+        raise _lib.CffmError('%s: the slot table is a contiguous int32 [4] on %s, got %s %s on %s'
+                             % (what, ring.device, slots.dtype, tuple(slots.shape), slots.device))
+
+
+def segformer_fuse_pool(feats, lin_w, lin_b, fuse_w, bn, ring, slots, which):
+    """The eval tail of one frame (or of a batch of single frames) in one pass over the 1/4-scale map: what
+    ``bn_relu_pool(segformer_fuse(feats, ...), bn)[1]`` returns -- the [B, H/2*W/2, 256] rows the CFFM layer reads, bit for bit -- written
+    into ``ring[slots[which]]`` without the pre-BatchNorm map or ``fused`` ever existing (``cffm_segfuse_pool_fwd``).
+
+    feats, lin_w, lin_b, fuse_w as for ``segformer_fuse``; ``bn`` must be in eval mode with running statistics; ``ring`` [R,B,H/2*W/2,256];
+    ``slots`` a device int32 [4] the kernel reads (an entry outside 0..R-1 is clamped on the device); ``which`` in 0..3.  Inference only."""
+    lib = _lib.get()
+    if bn.training or bn.running_mean is None or bn.running_var is None:
+        raise _lib.CffmError('segformer_fuse_pool is the eval tail: the BatchNorm must be in eval mode and have running statistics')
+    _infer_only(list(feats) + list(lin_w) + list(lin_b) + [fuse_w, bn.weight, bn.bias], 'segformer_fuse_pool')
+    _check_ring(ring, slots, 'segformer_fuse_pool')
+    if not 0 <= int(which) < 4:
+        raise _lib.CffmError('segformer_fuse_pool: `which` indexes the 4-entry slot table, got %r' % (which,))
+    k, e = len(feats), fuse_w.shape[0]
+    if e != 256 or fuse_w.shape[1] != k * e:
+        raise _lib.CffmError('segformer_fuse_pool: fuse weight %s does not fit %d embeddings of 256' % (tuple(fuse_w.shape), k))
+    n, _, H, W = feats[0].shape
+    if H % 2 or W % 2 or tuple(ring.shape[1:]) != (n, (H // 2) * (W // 2), 256):
+        raise _lib.CffmError('segformer_fuse_pool: a [%d,*,%d,%d] map (even sides) does not fit ring slots %s'
+                             % (n, H, W, tuple(ring.shape[1:])))
+    with torch.no_grad():
+        *mats, d = _ComposeFn.apply(fuse_w.detach().reshape(e, k * e), *[w.detach() for w in lin_w], *[b_.detach() for b_ in lin_b])
+        d, feats, mats, _toks, zs, (zp, hs, ws) = _segfuse_chains(lib, d, tuple(f.detach() for f in feats) + tuple(mats))
+        st, dev = _stream(ring), ring.device
+        coef = torch.empty(4, 256, dtype=torch.float32, device=dev)
+        w_, b_ = bn.weight.detach().contiguous(), bn.bias.detach().contiguous()
+        _lib.check(lib.cffm_bn_finalize_fwd(None, 0, float(n * H * W), _ptr(w_), _ptr(b_), _ptr(bn.running_mean), _ptr(bn.running_var), 0.0,
+                                            float(bn.eps), _ptr(coef), st), lib)
+        slot_floats = ring.shape[1] * ring.shape[2] * 256
+        _lib.check(lib.cffm_segfuse_pool_fwd(_ptr(zs[0]), _ptr(d), zp, hs, ws, k - 1, _ptr(coef[0]), _ptr(coef[1]), _ptr(ring), slot_floats,
+                                             ring.shape[0], _ptr(slots), int(which), n, H, W, st), lib)
+    return ring
 
 
 # ---------------------------------------------------------------------------------------------- 1x1 classifiers
@@ -884,6 +939,27 @@ def cffm_layer_rows_infer(x_rows, h0, w0, depth, params, prepared, ws=None, out=
     ws, out = _infer_buffers(lib, g, depth, prepared, ws, out, (b, h0 * w0, 256), x_rows.device)
     _lib.check(lib.cffm_layer_infer_rows(C.byref(g), depth, block_structs(params, depth), _ptr(prepared), _ptr(x_rows), _ptr(out), _ptr(key_src),
                                          _ptr(q_dst), _ptr(ws), _stream(x_rows)), lib)
+    return out
+
+
+def cffm_layer_rows_ring(ring, slots, h0, w0, depth, params, prepared, ws=None, out=None):
+    """cffm_layer_rows_infer on four frames where a ring holds them: ring [R,B,h0*w0,256], frame t (the target last) = ring[slots[t]],
+    slots a device int32 [4] the kernels read (entries may repeat; one outside 0..R-1 is clamped on the device) -> the new target frame
+    [B,h0*w0,256].  Equal, bit for bit, to cffm_layer_rows_infer on ``ring.index_select(0, slots).transpose(0, 1)``.  No argument of the
+    library call depends on the table's contents: captured once, the call serves every frame of a video."""
+    lib = _lib.get()
+    _check_ring(ring, slots, 'cffm_layer_rows_ring')
+    if ring.shape[2] != h0 * w0:
+        raise _lib.CffmError('cffm_layer_rows_ring: ring slots [B,%d,256] expected, got %s' % (h0 * w0, tuple(ring.shape[1:])))
+    if len(params) != NPB * depth:
+        raise _lib.CffmError('expected %d parameter tensors for depth %d, got %d' % (NPB * depth, depth, len(params)))
+    ring = ring.detach()
+    r, b = ring.shape[0], ring.shape[1]
+    g, (key_src, q_dst, *_) = _layer_geom(lib, b, h0, w0, ring.device)
+    ws, out = _infer_buffers(lib, g, depth, prepared, ws, out, (b, h0 * w0, 256), ring.device)
+    img = h0 * w0 * 256
+    _lib.check(lib.cffm_layer_infer_rows_ring(C.byref(g), depth, block_structs(params, depth), _ptr(prepared), _ptr(ring), b * img, r, _ptr(slots),
+                                              img, _ptr(out), _ptr(key_src), _ptr(q_dst), _ptr(ws), _stream(ring)), lib)
     return out
 
 
