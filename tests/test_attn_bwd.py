@@ -26,13 +26,11 @@ def bias_buffer(bias):
     return b320.view(8, 4, 16, 10, 4, 8).permute(0, 1, 3, 4, 2, 5).contiguous().reshape(-1)
 
 
-def run_attn_bwd_stage(lib, device, b, h0, w0, grad_scale=1e-3, zero_window=False, raw=False):
+def stage_inputs(b, h0, w0, grad_scale=1e-3, zero_window=False):
+    """the stage's seeded inputs: the f16 q|k|v rows, the dense bias and the upstream gradient of the attention output"""
     torch.manual_seed(b * 1000 + h0 * 31 + w0)
-    g = ops.make_geom(lib, b, h0, w0)
-    nw, rc, hw = g.nW, g.RC, g.HW
-    ks_t, qd_t, ip_t, ii_t = ops.device_tables(h0, w0, device)
-    ks_c, qd_c = ks_t.cpu(), qd_t.cpu()
-    qkv = (torch.randn(b * rc, 768) * 0.7).half()
+    nw, hw = ((h0 + 6) // 7) * ((w0 + 6) // 7), h0 * w0
+    qkv = (torch.randn(b * 64 * nw, 768) * 0.7).half()
     bias = torch.randn(8, 64, 304) * 0.5
     bias[:, 49:] = 0
     bias[:, :, 289:] = 0
@@ -40,6 +38,18 @@ def run_attn_bwd_stage(lib, device, b, h0, w0, grad_scale=1e-3, zero_window=Fals
     dao[: hw // 3] *= 1e-3                       # windows whose gradients are three decades smaller (the common-scale staging)
     if zero_window:
         dao[:] = 0
+    return qkv, bias, dao
+
+
+def run_attn_bwd_stage(lib, device, b, h0, w0, grad_scale=1e-3, zero_window=False, raw=False, ao=None, lse=None):
+    """ao [b * HW, 256] / lse [b, nW, 8, 64] (fp32, on `device`): what the backward is handed in place of the reference's own
+    attention output and log-sum-exp -- tests/test_attn_fwd.py passes the forward kernel's; the gradients are judged the same way"""
+    g = ops.make_geom(lib, b, h0, w0)
+    nw, rc, hw = g.nW, g.RC, g.HW
+    assert rc == 64 * nw and nw == ((h0 + 6) // 7) * ((w0 + 6) // 7)
+    ks_t, qd_t, ip_t, ii_t = ops.device_tables(h0, w0, device)
+    ks_c, qd_c = ks_t.cpu(), qd_t.cpu()
+    qkv, bias, dao = stage_inputs(b, h0, w0, grad_scale, zero_window)
     # ---- reference: torch autograd on the float values of the same f16 rows
     x = qkv.float().clone().requires_grad_(True)
     xq = x.view(b, rc, 768)
@@ -56,19 +66,19 @@ def run_attn_bwd_stage(lib, device, b, h0, w0, grad_scale=1e-3, zero_window=Fals
     qdf = qd_c.view(-1)
     sel = torch.nonzero(qdf >= 0).view(-1)
     (o_rows[:, sel] * dao.view(b, hw, 256)[:, qdf[sel].long()]).sum().backward()
-    ao = torch.zeros(b, hw, 256)
-    ao[:, qdf[sel].long()] = o_rows[:, sel].detach()
+    ao_ref = torch.zeros(b, hw, 256)
+    ao_ref[:, qdf[sel].long()] = o_rows[:, sel].detach()
     dref = x.grad.view(b, rc, 768)
     dbias_ref = s.grad.sum((0, 1))
     # ---- library
-    lse = torch.zeros(b, nw, 8, 64)
-    lse[..., :49] = lse_ref.detach()
+    lse_in = torch.zeros(b, nw, 8, 64)
+    lse_in[..., :49] = lse_ref.detach()
     dev = lambda t: t.contiguous().to(device)
     dqkv = torch.full((b * rc, 768), float('nan'), device=device)
     dbias_t = torch.zeros(8, 304, 64, device=device)
     ws = torch.zeros(b * nw * (304 * 256 + 8), device=device)      # f16 partial rows + their scales
     stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream) if device.type == 'cuda' else None
-    args = [dev(t) for t in (qkv, bias_buffer(bias), ao.view(b * hw, 256), dao, lse)]
+    args = [dev(t) for t in (qkv, bias_buffer(bias), ao_ref.view(b * hw, 256) if ao is None else ao, dao, lse_in if lse is None else lse)]
     _lib.check(lib.cffm_attn_bwd(C.byref(g), P(args[0]), P(ks_t), P(qd_t), P(ip_t), P(ii_t), P(args[1]), P(args[2]), P(args[3]),
                                  P(args[4]), P(dqkv), P(dbias_t), P(ws), stream), lib)
     if raw:
