@@ -335,6 +335,16 @@ int cffm_segfuse_bwd(const float* g, float* const dz[3], const int h[3], const i
 int cffm_segfuse_pool_fwd(const float* y, const float* d, const float* const z[3], const int h[3], const int w[3], int nmaps,
                           const float* scale, const float* shift, float* ring, long slot_floats, int nslots, const int* slots, int which,
                           int N, int H, int W, void* stream);
+/* added under ABI 13, additive: the same with ONE SLOT PER FRAME (a chunk of a video in one call).  Frame n's H/2 * W/2 rows go to
+ * ring + clamp(slots[n], 0, nslots - 1) * slot_floats; slots is a DEVICE int[N] read by the kernel, so a captured launch serves any slots;
+ * slot_floats >= H/2 * W/2 * 256 (one frame), a multiple of 4.  Arithmetic and parenthesisation are cffm_segfuse_pool_fwd's: the rows have
+ * the bits of N calls of it at N = 1 on the frames' slices of the inputs.  Two frames that name the same slot are the caller's mistake: that
+ * slot then holds an unspecified mix of their rows; nothing is written outside the ring (the clamp).  Refused before anything is enqueued:
+ * odd H or W, null or misaligned pointers (16 bytes; the table 4, and it must not be NULL), a ring that overlaps y, d, scale, shift, the
+ * table or a map.  One launch on `stream`, no LDS, no atomics. */
+int cffm_segfuse_pool_fwd_frames(const float* y, const float* d, const float* const z[3], const int h[3], const int w[3], int nmaps,
+                                 const float* scale, const float* shift, float* ring, long slot_floats, int nslots, const int* slots, int N,
+                                 int H, int W, void* stream);
 
 /* ---- the head's training loss without full-resolution logits ----
  * Replaces decode_head.py:744-835's resize(seg_logit, size=label size, 'bilinear', align_corners=False) followed by
@@ -453,6 +463,15 @@ int cffm_layer_infer_full(const cffm_geom* g, int depth, const cffm_block_params
 int cffm_layer_infer_rows_ring(const cffm_geom* g, int depth, const cffm_block_params* params, const float* prepared, const float* ring,
                                long slot_floats, int nslots, const int* slots, long frame_bs, float* y_rows, const int* key_src,
                                const int* q_dst, float* ws, void* stream);
+/* added under ABI 13, additive: the same with ONE TABLE PER SAMPLE (the g->B targets of a chunk of one video, each with its own clip, in one
+ * call).  Frame t of sample b is ring + clamp(slots[4 * b + t], 0, nslots - 1) * slot_floats, [HW,256] floats; slots is a DEVICE int[B * 4].
+ * There is no frame_bs: every sample reads whole slots of the one ring, and entries may repeat within a sample and across samples.  Block
+ * 0's residual is sample b's own target (slots[4 * b + 3]).  Same prepared data, same workspace (cffm_layer_infer_ws_floats at g->B), every
+ * launch on `stream`; the ring is only read.  y_rows or ws inside the ring is an error, as is a null or misaligned table.  With B = 1 the
+ * call is cffm_layer_infer_rows_ring; with B > 1 sample b's rows have the bits of a B = 1 call of it with that sample's four entries. */
+int cffm_layer_infer_rows_ring_tables(const cffm_geom* g, int depth, const cffm_block_params* params, const float* prepared, const float* ring,
+                                      long slot_floats, int nslots, const int* slots, float* y_rows, const int* key_src, const int* q_dst,
+                                      float* ws, void* stream);
 
 /* ---- `linear_fuse`'s BatchNorm + ReLU and the 1/4 -> 1/8 resize that builds the clip stack (cffm_head.py:119, :131-135), on token
  * rows [pixels,256].  With even H, W the bilinear 1/2 resize (align_corners=False) is exactly a 2x2 average.

@@ -228,6 +228,8 @@ SIGNATURES = {
     'cffm_mit_blocks_train_bwd': (ci, [MCP, MBP, MSC, MBP, vp, vp, vp, vp, vp, vp]),
     'cffm_segfuse_pool_fwd': (ci, [vp, vp, vp * 3, ci * 3, ci * 3, ci, vp, vp, vp, cl, ci, vp, ci, ci, ci, ci, vp]),
     'cffm_layer_infer_rows_ring': (ci, [GP, ci, BP, vp, vp, cl, ci, vp, cl, vp, vp, vp, vp, vp]),
+    'cffm_segfuse_pool_fwd_frames': (ci, [vp, vp, vp * 3, ci * 3, ci * 3, ci, vp, vp, vp, cl, ci, vp, ci, ci, ci, vp]),
+    'cffm_layer_infer_rows_ring_tables': (ci, [GP, ci, BP, vp, vp, cl, ci, vp, vp, vp, vp, vp, vp]),
 }
 
 

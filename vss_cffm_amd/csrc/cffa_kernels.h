@@ -204,26 +204,38 @@ __device__ __forceinline__ int frame_group(int frame) { return frame == 3 ? 0 : 
 // x_tgt == NULL: the target is frame 3 of the table (block 0); otherwise the block before's rows, as in the other forms.  In block 0 the
 // target's rows, each read exactly once by the launch, are also copied to rg.tgt_copy [B,HW,256]: the residual k_mlp_fwd adds sits at an
 // address its arguments can name, so that kernel is not touched and no host pointer depends on the table.
+// TABLES = true (RING = true only; a new instantiation, the three forms above are the kernels they were): one 4-entry table PER SAMPLE --
+// frame t of sample b at x_ref + clamp(rg.slots[4 * b + t]) * rg.slot_floats, whole slots of the one ring (ref_bs is not used); entries
+// may repeat within a sample and across samples.  The third template parameter is defaulted and the form is chosen by the TYPE of the
+// trailing argument (LnpRingTables wraps LnpRing).
 struct LnpNoRing {};
 struct LnpRing { const int* slots; long slot_floats; int nslots; float* tgt_copy; };
-template <bool RING> struct LnpRingArg { typedef LnpNoRing type; };
-template <> struct LnpRingArg<true> { typedef LnpRing type; };
+struct LnpRingTables { LnpRing r; };
+template <bool RING, bool TABLES = false> struct LnpRingArg { typedef LnpNoRing type; };
+template <> struct LnpRingArg<true, false> { typedef LnpRing type; };
+template <> struct LnpRingArg<true, true> { typedef LnpRingTables type; };
 __device__ __forceinline__ const float* lnp_ring_frame(const float* ring, const LnpRing& rg, int frame, long b, long frame_bs) {
     int s = rg.slots[frame];
     s = s < 0 ? 0 : (s > rg.nslots - 1 ? rg.nslots - 1 : s);
     return ring + (long)s * rg.slot_floats + b * frame_bs;
 }
+__device__ __forceinline__ const float* lnp_ring_frame(const float* ring, const LnpRingTables& rg, int frame, long b, long) {
+    int s = rg.r.slots[4 * b + frame];
+    s = s < 0 ? 0 : (s > rg.r.nslots - 1 ? rg.r.nslots - 1 : s);
+    return ring + (long)s * rg.r.slot_floats;
+}
 __device__ __forceinline__ const float* lnp_ring_frame(const float*, const LnpNoRing&, int, long, long) { return nullptr; }
 __device__ __forceinline__ void lnp_ring_keep(const LnpRing& rg, long row, int lane, const f32x4& v) { *(f32x4*)(rg.tgt_copy + row * CFFM_C + 4 * lane) = v; }
+__device__ __forceinline__ void lnp_ring_keep(const LnpRingTables& rg, long row, int lane, const f32x4& v) { lnp_ring_keep(rg.r, row, lane, v); }
 __device__ __forceinline__ void lnp_ring_keep(const LnpNoRing&, long, int, const f32x4&) {}
-template <bool INFER, bool RING = false>
+template <bool INFER, bool RING = false, bool TABLES = false>
 __global__ void __launch_bounds__(LNP_THREADS, 6) k_ln_pool_fwd(Geo G, const float* __restrict__ x_ref, long ref_bs,
                                                       const float* __restrict__ x_tgt, long tgt_bs,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
                                                       const float* __restrict__ M /* or NULL: built here from pw */, PoolW pw, PoolB pb,
                                                       float* __restrict__ zall, float* __restrict__ mean_out,
                                                       float* __restrict__ rstd_out, int split /* zall rows in split-4 storage */,
-                                                      typename LnpRingArg<RING>::type rg) {
+                                                      typename LnpRingArg<RING, TABLES>::type rg) {
     __shared__ float sM[9 * CFFM_WA];
     __shared__ float red[4][9][CFFM_C];              // (eight waves: the upper four add into the lower four's rows)
     const int w = blockIdx.x, frame = blockIdx.y, b = blockIdx.z;

@@ -2105,6 +2105,36 @@ int cffm_segfuse_pool_fwd(const float* y, const float* d, const float* const z[3
     CHECK_LAUNCH("segfuse_pool_fwd");
     return 0;
 }
+// the same with one slot per frame (k_segfuse_fwd<true, true>): frame n's rows go to slot clamp(slots[n]) of the ring, slots a device int[N]
+int cffm_segfuse_pool_fwd_frames(const float* y, const float* d, const float* const z[3], const int h[3], const int w[3], int nmaps,
+                                 const float* scale, const float* shift, float* ring, long slot_floats, int nslots, const int* slots, int N,
+                                 int H, int W, void* stream) {
+    REQUIRE(y && d && scale && shift && ring && slots && N >= 0 && (nmaps == 0 || (z && h && w)),
+            "segfuse_pool_fwd_frames: bad arguments (null pointer)");
+    REQUIRE(H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "segfuse_pool_fwd_frames: even map sides expected, got %dx%d", H, W);
+    SegfMaps mp;
+    TRY(segf_maps(mp, h, w, nmaps, H, W, "segfuse_pool_fwd_frames"));
+    for (int m = 0; m < nmaps; ++m) { REQUIRE(z[m], "segfuse_pool_fwd_frames: null map"); mp.z[m] = z[m]; }
+    const long rows = (long)N * H * W, patches = rows / 4, frame_floats = (long)(H / 2) * (W / 2) * SEGF_C;
+    REQUIRE(rows < (1L << 31), "segfuse_pool_fwd_frames: too many output pixels");
+    REQUIRE(nslots >= 1 && slot_floats >= frame_floats && slot_floats % 4 == 0,
+            "segfuse_pool_fwd_frames: %d slots of %ld floats for frames of %ld floats of rows", nslots, slot_floats, frame_floats);
+    bool aligned = !(((uintptr_t)y | (uintptr_t)d | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)ring) & 15) && !((uintptr_t)slots & 3);
+    for (int m = 0; m < nmaps; ++m) aligned = aligned && !((uintptr_t)z[m] & 15);
+    REQUIRE(aligned, "segfuse_pool_fwd_frames: pointers must be 16-byte aligned (the slot table: 4)");
+    // the ring as a whole (any slot may be written) must not share memory with anything the launch reads
+    const long ring_floats = (long)(nslots - 1) * slot_floats + frame_floats;
+    bool clash = spans_overlap(ring, ring_floats, y, rows * SEGF_C) || spans_overlap(ring, ring_floats, d, SEGF_C) ||
+                 spans_overlap(ring, ring_floats, scale, SEGF_C) || spans_overlap(ring, ring_floats, shift, SEGF_C) ||
+                 spans_overlap(ring, ring_floats, (const float*)slots, N);
+    for (int m = 0; m < nmaps; ++m) clash = clash || spans_overlap(ring, ring_floats, z[m], (long)N * h[m] * w[m] * SEGF_C);
+    REQUIRE(!clash, "segfuse_pool_fwd_frames: the ring overlaps an input");
+    if (!patches) return 0;
+    const SegfPoolFrames pa = {{scale, shift, ring, slot_floats, nslots, slots, 0}};
+    CFFM_LAUNCH((k_segfuse_fwd<true, true>), ((unsigned)((patches + 3) / 4)), (256), 0, (hipStream_t)stream, const_cast<float*>(y), d, mp, N, H, W, pa);
+    CHECK_LAUNCH("segfuse_pool_fwd_frames");
+    return 0;
+}
 
 // ------------------------------------------------------------------------------------------- resize + cross entropy
 static int upce_geom(UpceGeom& G, int M, int K, int h, int w, int H, int W, int ignore, const char* who) {
@@ -2622,9 +2652,10 @@ int cffm_layer_prepare(int depth, const cffm_block_params* params, float* prepar
 // NCHW images y_bs floats apart to `y_nchw` (k_mlp_fwd's NCHW form)
 static int layer_infer_blocks(const cffm_geom* g, int depth, const cffm_block_params* params, const float* prepared, const float* stack,
                               float* y_rows, const int* key_src, const int* q_dst, float* ws, void* stream, float* y_nchw = nullptr, long y_bs = 0,
-                              const LnpRing* ring = nullptr, long frame_bs = 0) {
+                              const LnpRing* ring = nullptr, long frame_bs = 0, bool tables = false) {
     // ring != NULL: `stack` is a ring of frame buffers and the four frames are those of ring->slots (k_ln_pool_fwd<true, true>); block 0's
-    // residual rows are the copy that launch leaves in the x2 buffer no block touches before block 1 writes it
+    // residual rows are the copy that launch leaves in the x2 buffer no block touches before block 1 writes it.  tables: ring->slots holds
+    // one 4-entry table per sample and every sample reads whole slots (k_ln_pool_fwd<true, true, true>; frame_bs is not used)
     REQUIRE(!infer_lds_grant(), "layer_infer: LDS grant failed");
     const PreparedLayout P = prepared_layout();
     const InferWs W = infer_ws_layout(g);
@@ -2647,8 +2678,13 @@ static int layer_infer_blocks(const cffm_geom* g, int depth, const cffm_block_pa
             if (ring) {
                 LnpRing rg = *ring;
                 rg.tgt_copy = ws + W.x2[1];
-                CFFM_LAUNCH((k_ln_pool_fwd<true, true>), (g->nW, 4, g->B), (LNP_THREADS), 0, st, G, stack, frame_bs, ring0 ? nullptr : tgt, tgt_bs,
-                            p->norm1_w, p->norm1_b, pre + P.M, PoolW(), pb, ws + W.zall, nullptr, nullptr, 1, rg);
+                if (tables) {
+                    const LnpRingTables rt = {rg};
+                    CFFM_LAUNCH((k_ln_pool_fwd<true, true, true>), (g->nW, 4, g->B), (LNP_THREADS), 0, st, G, stack, 0L, ring0 ? nullptr : tgt, tgt_bs,
+                                p->norm1_w, p->norm1_b, pre + P.M, PoolW(), pb, ws + W.zall, nullptr, nullptr, 1, rt);
+                } else
+                    CFFM_LAUNCH((k_ln_pool_fwd<true, true>), (g->nW, 4, g->B), (LNP_THREADS), 0, st, G, stack, frame_bs, ring0 ? nullptr : tgt, tgt_bs,
+                                p->norm1_w, p->norm1_b, pre + P.M, PoolW(), pb, ws + W.zall, nullptr, nullptr, 1, rg);
             } else
                 CFFM_LAUNCH(k_ln_pool_fwd<true>, (g->nW, 4, g->B), (LNP_THREADS), 0, st, G, stack, 4 * img, tgt, tgt_bs, p->norm1_w, p->norm1_b,
                             pre + P.M, PoolW(), pb, ws + W.zall, nullptr, nullptr, 1, LnpNoRing());
@@ -2712,6 +2748,22 @@ int cffm_layer_infer_rows_ring(const cffm_geom* g, int depth, const cffm_block_p
     REQUIRE(!spans_overlap(ring, ring_floats, ws, infer_ws_layout(g).total), "layer_infer_rows_ring: the workspace lies inside the ring");
     LnpRing rg = {slots, slot_floats, nslots, nullptr};
     return layer_infer_blocks(g, depth, params, prepared, ring, y_rows, key_src, q_dst, ws, stream, nullptr, 0, &rg, frame_bs);
+}
+// The same with one table per sample: frame t of sample b = ring + clamp(slots[4 * b + t]) * slot_floats (slots: device int[B * 4]), whole
+// slots of the one ring -- the B targets of a chunk of one video, each with its own clip, in one call.
+int cffm_layer_infer_rows_ring_tables(const cffm_geom* g, int depth, const cffm_block_params* params, const float* prepared, const float* ring,
+                                      long slot_floats, int nslots, const int* slots, float* y_rows, const int* key_src, const int* q_dst,
+                                      float* ws, void* stream) {
+    TRY(layer_infer_check(g, depth, params, prepared, ring, y_rows, key_src, q_dst, ws, "layer_infer_rows_ring_tables"));
+    const long img = (long)g->HW * CFFM_C;
+    REQUIRE(slots && !((uintptr_t)slots & 3) && !((uintptr_t)ring & 15), "layer_infer_rows_ring_tables: null or misaligned slot tables / ring");
+    REQUIRE(nslots >= 1 && slot_floats % 4 == 0 && slot_floats >= img, "layer_infer_rows_ring_tables: %d slots of %ld floats for frames of %ld floats",
+            nslots, slot_floats, img);
+    const long ring_floats = (long)(nslots - 1) * slot_floats + img;
+    REQUIRE(!spans_overlap(ring, ring_floats, y_rows, (long)g->B * img), "layer_infer_rows_ring_tables: y_rows lies inside the ring");
+    REQUIRE(!spans_overlap(ring, ring_floats, ws, infer_ws_layout(g).total), "layer_infer_rows_ring_tables: the workspace lies inside the ring");
+    LnpRing rg = {slots, slot_floats, nslots, nullptr};
+    return layer_infer_blocks(g, depth, params, prepared, ring, y_rows, key_src, q_dst, ws, stream, nullptr, 0, &rg, 0, true);
 }
 // The reference's whole output [B,4,C,H,W].  The NHWC stack the blocks read needs as much room as the output has: it is built IN
 // y_full (so the workspace stays what the rows form needs) and y_full gets its real contents when the last block is done -- frames

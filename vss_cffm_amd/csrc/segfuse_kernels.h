@@ -64,11 +64,20 @@ struct SegfMaps {
 // run-time branch and not a helper function (a helper changed k_segfuse_fwd's registers: 96 -> 98 / 100 VGPRs, five waves -> four).
 // out = ring + slot * slot_floats: the slot comes from a device table (slots[which], NULL: 0), so that a captured launch can be replayed
 // for another slot, and is clamped into [0, nslots) -- whatever the table holds, the rows land inside the ring.  No LDS, no atomics.
+//
+// FRAMES = true (POOL = true only; a new instantiation, the two forms above are the kernels they were): one slot PER FRAME instead of one
+// for the batch -- frame n's H/2 * W/2 rows go to ring + clamp(slots[n]) * slot_floats, slots a device int[N].  The second template
+// parameter is defaulted and the form is chosen by the TYPE of the trailing argument (SegfPoolFrames wraps SegfPool; `which` is unused),
+// so the arithmetic in front of the store is the one text it was.  Two frames that name one slot race on its rows (the caller's mistake;
+// the slot then holds an unspecified mix of the two); nothing is written outside the ring.
 struct SegfNoPool {};
 struct SegfPool { const float* scale; const float* shift; float* ring; long slot_floats; int nslots; const int* slots; int which; };
-template <bool POOL> struct SegfPoolArg { typedef SegfNoPool type; };
-template <> struct SegfPoolArg<true> { typedef SegfPool type; };
-__device__ __forceinline__ void segf_pool_store(const SegfPool& pa, const f32x4 (&acc)[2][2], long patch, int lane) {
+struct SegfPoolFrames { SegfPool p; };
+template <bool POOL, bool FRAMES = false> struct SegfPoolArg { typedef SegfNoPool type; };
+template <> struct SegfPoolArg<true, false> { typedef SegfPool type; };
+template <> struct SegfPoolArg<true, true> { typedef SegfPoolFrames type; };
+// (entry: the table entry that names the slot, NULL: slot 0; row: the output row inside the slot)
+__device__ __forceinline__ void segf_pool_rows(const SegfPool& pa, const f32x4 (&acc)[2][2], const int* entry, long row, int lane) {
     const f32x4 sc = ((const f32x4*)pa.scale)[lane], sh = ((const f32x4*)pa.shift)[lane];
     f32x4 r[2][2];
 #pragma unroll
@@ -80,14 +89,21 @@ __device__ __forceinline__ void segf_pool_store(const SegfPool& pa, const f32x4 
             for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
             r[a][b] = v;
         }
-    int slot = pa.slots ? pa.slots[pa.which] : 0;
+    int slot = entry ? *entry : 0;
     slot = slot < 0 ? 0 : (slot > pa.nslots - 1 ? pa.nslots - 1 : slot);
-    ((f32x4*)(pa.ring + (long)slot * pa.slot_floats + patch * SEGF_C))[lane] = ((r[0][0] + r[0][1]) + (r[1][0] + r[1][1])) * 0.25f;
+    ((f32x4*)(pa.ring + (long)slot * pa.slot_floats + row * SEGF_C))[lane] = ((r[0][0] + r[0][1]) + (r[1][0] + r[1][1])) * 0.25f;
 }
-__device__ __forceinline__ void segf_pool_store(const SegfNoPool&, const f32x4 (&)[2][2], long, int) {}
-template <bool POOL = false>
+// (n, pr: the patch's frame and its index inside the frame -- the per-frame form's table entry and output row)
+__device__ __forceinline__ void segf_pool_store(const SegfPool& pa, const f32x4 (&acc)[2][2], long patch, int lane, int, int) {
+    segf_pool_rows(pa, acc, pa.slots ? pa.slots + pa.which : nullptr, patch, lane);
+}
+__device__ __forceinline__ void segf_pool_store(const SegfPoolFrames& pa, const f32x4 (&acc)[2][2], long, int lane, int n, int pr) {
+    segf_pool_rows(pa.p, acc, pa.p.slots + n, pr, lane);
+}
+__device__ __forceinline__ void segf_pool_store(const SegfNoPool&, const f32x4 (&)[2][2], long, int, int, int) {}
+template <bool POOL = false, bool FRAMES = false>
 __global__ void __launch_bounds__(256) k_segfuse_fwd(float* __restrict__ y, const float* __restrict__ d, SegfMaps mp, int N, int H, int W,
-                                                     typename SegfPoolArg<POOL>::type pa) {
+                                                     typename SegfPoolArg<POOL, FRAMES>::type pa) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ph = (H + 1) / 2, pw = (W + 1) / 2;
     const long patch = (long)xcd_linear_id() * 4 + wave;
@@ -149,7 +165,7 @@ __global__ void __launch_bounds__(256) k_segfuse_fwd(float* __restrict__ y, cons
             }
     }
     if (POOL) {           // (H, W even: the patch is whole, and its index is the output row)
-        segf_pool_store(pa, acc, patch, lane);
+        segf_pool_store(pa, acc, patch, lane, n, pr);
         return;
     }
     ((f32x4*)yb)[lane] = acc[0][0];

@@ -26,7 +26,7 @@ from .modules import BasicLayer3d3, BasicLayer_cluster
 from . import _lib
 from .cluster import kmeans
 from .ops import (bn_relu_pool, cat_into, cat_room, conv1x1, frame_logits_cat, late_params, head_cross_entropy, resize_cross_entropy, rows_resize,
-                  segformer_fuse, segformer_fuse_pool)
+                  segformer_fuse, segformer_fuse_pool, segformer_fuse_pool_frames)
 from .registry import HEADS, LOSSES, build_loss
 
 
@@ -388,6 +388,33 @@ class _CffmHeadBase(BaseDecodeHead_clips_flow):
         x2 = self._clip_logits(stack, self.decoder_focal(stack), size)
         return x2.squeeze(1)
 
+    # ---- a chunk of ONE video at a time: M frames encoded in one call, a slot each (ring [R,h/2*w/2,256]); M targets, a clip table each
+    def stream_rows_many(self, inputs, ring, slots):
+        """The backbone features of M frames of one video -> frame n's stack rows in ``ring[slots[n]]`` (ops.segformer_fuse_pool_frames:
+        one pass; slots a device int32 [M]).  The per-frame-slot counterpart of `stream_rows`."""
+        if self.training:
+            raise RuntimeError('stream_rows_many is the eval path of the head: call head.eval() first')
+        c1, c2, c3, c4 = self._transform_inputs(inputs)
+        lins = (self.linear_c1, self.linear_c2, self.linear_c3, self.linear_c4)
+        return segformer_fuse_pool_frames([c1, c2, c3, c4], [l.proj.weight for l in lins], [l.proj.bias for l in lins],
+                                          self.linear_fuse.conv.weight, self.linear_fuse.bn, ring, slots)
+
+    def _stream_clip_many(self, ring, tables, h, w):
+        """-> (the M targets' rows [M,h2*w2,256] -- gathered on the device: no host read of the tables --, the clip-level logits x2)"""
+        if self.training:
+            raise RuntimeError('forward_stream_many is the eval path of the head: call head.eval() first')
+        m, (h2, w2) = tables.shape[0], (h // 2, w // 2)
+        with torch.no_grad():
+            tgt = ring.index_select(0, tables[:, 3].long().clamp(0, ring.shape[0] - 1))
+            mined = self.decoder_focal.forward_rows_ring_tables(ring, tables, h2, w2)           # [M, h2*w2, 256]
+            x2 = self._rows_logits(self.linear_pred2, torch.cat([tgt, mined], dim=-1).view(m, h2, w2, -1), self.dropout, (h, w))
+        return tgt, x2
+
+    def forward_stream_many(self, ring, tables, h, w, img_metas=None):
+        """[M,K,h,w] logits of the M frames ``ring[tables[:, 3]]`` of one video, frame b from the clip ``ring[tables[b]]`` (tables: device
+        int32 [M,4]; h, w: the 1/4-scale map's size): `forward_stream` at B = M."""
+        raise NotImplementedError('%s has no streaming forward' % type(self).__name__)
+
 
 @HEADS.register_module()
 class CFFMHead_clips_resize1_8(_CffmHeadBase):
@@ -395,6 +422,9 @@ class CFFMHead_clips_resize1_8(_CffmHeadBase):
 
     def forward_stream(self, ring, slots, h, w, img_metas=None):
         return self._stream_clip(ring, slots, h, w)[1].squeeze(1)
+
+    def forward_stream_many(self, ring, tables, h, w, img_metas=None):
+        return self._stream_clip_many(ring, tables, h, w)[1].squeeze(1)
 
     def _forward_rows(self, inputs, batch_size, num_clips):
         # (the frame classifier's parameters as they will be used at the END of the forward, through a node created FIRST: its backward runs
@@ -467,6 +497,9 @@ class CFFMHead_clips_resize1_8_gene_prototype(_CffmHeadBase):
         torch.save(centers, self.save_path + video + '/centers.pt')
 
     def stream_rows(self, inputs, ring, slots, which):
+        raise NotImplementedError('the prototype-generating head clusters whole clips: it has no streaming forward')
+
+    def stream_rows_many(self, inputs, ring, slots):
         raise NotImplementedError('the prototype-generating head clusters whole clips: it has no streaming forward')
 
     def _stream_tail_torch(self, stack, size, img_metas=None):
@@ -581,6 +614,17 @@ class CFFMHead_clips_resize1_8_finetune_w_prototype3(_CffmHeadBase):
         with torch.no_grad():
             ctx = self.decoder_swin(tgt.contiguous(), h2, w2, centers)[0]                       # [B, h2*w2, C]
             x3 = self._rows_logits(self.linear_pred3, ctx.reshape(b, h2, w2, -1), self.dropout3, (h, w))
+        return x2.squeeze(1) + 0.5 * x3.squeeze(1)
+
+    def forward_stream_many(self, ring, tables, h, w, img_metas=None):
+        """`forward_stream` on M targets of ONE video: `decoder_swin` runs on the M targets' rows with the video's centers (loaded once
+        from the first meta)"""
+        m, (h2, w2) = tables.shape[0], (h // 2, w // 2)
+        centers = self._load_centers(img_metas[:1], ring.device).expand(m, -1, -1).contiguous()
+        tgt, x2 = self._stream_clip_many(ring, tables, h, w)
+        with torch.no_grad():
+            ctx = self.decoder_swin(tgt.contiguous(), h2, w2, centers)[0]                       # [M, h2*w2, C]
+            x3 = self._rows_logits(self.linear_pred3, ctx.reshape(m, h2, w2, -1), self.dropout3, (h, w))
         return x2.squeeze(1) + 0.5 * x3.squeeze(1)
 
     def _stream_tail_torch(self, stack, size, img_metas=None):

@@ -194,6 +194,14 @@ class BasicLayer3d3(nn.Module):
             raise RuntimeError('forward_rows_ring is inference only: call it under torch.no_grad()')
         return ops.cffm_layer_rows_ring(ring, slots, h, w, self.depth, params, self._prepared(params))
 
+    def forward_rows_ring_tables(self, ring, tables, h, w):
+        """forward_rows_ring on B targets with a clip each: ring [R, h*w, 256] holds single frames, frame t of sample b (the target last) =
+        ring[tables[b, t]], tables a device int32 [B, 4] -> the B new target frames [B, h*w, 256].  Inference only."""
+        params = [p for blk in self.blocks for p in blk.param_list()]
+        if not self._records_nothing(ring, params):
+            raise RuntimeError('forward_rows_ring_tables is inference only: call it under torch.no_grad()')
+        return ops.cffm_layer_rows_ring_tables(ring, tables, h, w, self.depth, params, self._prepared(params))
+
 
 # ------------------------------------------------------------------------------------------- CFFM++
 class WindowAttention_cluster(nn.Module):

@@ -544,6 +544,50 @@ def segformer_fuse_pool(feats, lin_w, lin_b, fuse_w, bn, ring, slots, which):
     return ring
 
 
+def _check_frame_ring(ring, table, shape, what):
+    """a ring of single frames [R,rows,256] (fp32, contiguous) and a device table of slot numbers (int32, contiguous, `shape` with None =
+    any size >= 1, same device)"""
+    _require_device(ring, what + ' ring')
+    if ring.dim() != 3 or ring.shape[2] != 256 or ring.shape[0] < 1 or not ring.is_contiguous():
+        raise _lib.CffmError('%s: a contiguous ring [R,rows,256] with R >= 1 expected, got %s' % (what, tuple(ring.shape)))
+    fits = table.dim() == len(shape) and table.shape[0] >= 1 and all(s is None or s == t for s, t in zip(shape, table.shape))
+    if table.dtype != torch.int32 or not fits or table.device != ring.device or not table.is_contiguous():
+        raise _lib.CffmError('%s: the slot table is a contiguous int32 %s on %s, got %s %s on %s'
+                             % (what, list(shape), ring.device, table.dtype, tuple(table.shape), table.device))
+
+
+def segformer_fuse_pool_frames(feats, lin_w, lin_b, fuse_w, bn, ring, slots):
+    """``segformer_fuse_pool`` on N frames of ONE video with a slot per frame: frame n's [H/2*W/2, 256] rows are written into
+    ``ring[slots[n]]`` (``cffm_segfuse_pool_fwd_frames``, one launch), with the bits N calls of ``segformer_fuse_pool`` at N = 1 leave.
+
+    feats, lin_w, lin_b, fuse_w as for ``segformer_fuse``; ``bn`` in eval mode with running statistics; ``ring`` [R,H/2*W/2,256];
+    ``slots`` a device int32 [N] the kernel reads (an entry outside 0..R-1 is clamped on the device; two frames naming one slot leave an
+    unspecified mix there).  Inference only."""
+    lib = _lib.get()
+    if bn.training or bn.running_mean is None or bn.running_var is None:
+        raise _lib.CffmError('segformer_fuse_pool_frames is the eval tail: the BatchNorm must be in eval mode and have running statistics')
+    _infer_only(list(feats) + list(lin_w) + list(lin_b) + [fuse_w, bn.weight, bn.bias], 'segformer_fuse_pool_frames')
+    n, _, H, W = feats[0].shape
+    _check_frame_ring(ring, slots, (n,), 'segformer_fuse_pool_frames')
+    k, e = len(feats), fuse_w.shape[0]
+    if e != 256 or fuse_w.shape[1] != k * e:
+        raise _lib.CffmError('segformer_fuse_pool_frames: fuse weight %s does not fit %d embeddings of 256' % (tuple(fuse_w.shape), k))
+    if H % 2 or W % 2 or tuple(ring.shape[1:]) != ((H // 2) * (W // 2), 256):
+        raise _lib.CffmError('segformer_fuse_pool_frames: a [%d,*,%d,%d] map (even sides) does not fit ring slots %s'
+                             % (n, H, W, tuple(ring.shape[1:])))
+    with torch.no_grad():
+        *mats, d = _ComposeFn.apply(fuse_w.detach().reshape(e, k * e), *[w.detach() for w in lin_w], *[b_.detach() for b_ in lin_b])
+        d, feats, mats, _toks, zs, (zp, hs, ws) = _segfuse_chains(lib, d, tuple(f.detach() for f in feats) + tuple(mats))
+        st, dev = _stream(ring), ring.device
+        coef = torch.empty(4, 256, dtype=torch.float32, device=dev)
+        w_, b_ = bn.weight.detach().contiguous(), bn.bias.detach().contiguous()
+        _lib.check(lib.cffm_bn_finalize_fwd(None, 0, float(n * H * W), _ptr(w_), _ptr(b_), _ptr(bn.running_mean), _ptr(bn.running_var), 0.0,
+                                            float(bn.eps), _ptr(coef), st), lib)
+        _lib.check(lib.cffm_segfuse_pool_fwd_frames(_ptr(zs[0]), _ptr(d), zp, hs, ws, k - 1, _ptr(coef[0]), _ptr(coef[1]), _ptr(ring),
+                                                    ring.shape[1] * 256, ring.shape[0], _ptr(slots), n, H, W, st), lib)
+    return ring
+
+
 # ---------------------------------------------------------------------------------------------- 1x1 classifiers
 class _Conv1x1Fn(torch.autograd.Function):
     """A 1x1 convolution as a Linear GEMM on channels-last token rows: x [N,C,H,W] (any strides; channels-last costs no copy),
@@ -960,6 +1004,26 @@ def cffm_layer_rows_ring(ring, slots, h0, w0, depth, params, prepared, ws=None, 
     img = h0 * w0 * 256
     _lib.check(lib.cffm_layer_infer_rows_ring(C.byref(g), depth, block_structs(params, depth), _ptr(prepared), _ptr(ring), b * img, r, _ptr(slots),
                                               img, _ptr(out), _ptr(key_src), _ptr(q_dst), _ptr(ws), _stream(ring)), lib)
+    return out
+
+
+def cffm_layer_rows_ring_tables(ring, tables, h0, w0, depth, params, prepared, ws=None, out=None):
+    """cffm_layer_rows_ring with a clip table per sample: ring [R,h0*w0,256] holds single frames, frame t (the target last) of sample b =
+    ring[tables[b, t]], tables a device int32 [B,4] the kernels read (entries may repeat within a sample and across samples; one outside
+    0..R-1 is clamped on the device) -> the B new target frames [B,h0*w0,256].  Sample b's rows equal, bit for bit, cffm_layer_rows_ring
+    on ``ring.unsqueeze(1)`` with ``tables[b]``.  No argument of the library call depends on the tables' contents."""
+    lib = _lib.get()
+    _check_frame_ring(ring, tables, (None, 4), 'cffm_layer_rows_ring_tables')
+    if ring.shape[1] != h0 * w0:
+        raise _lib.CffmError('cffm_layer_rows_ring_tables: ring slots [%d,256] expected, got %s' % (h0 * w0, tuple(ring.shape[1:])))
+    if len(params) != NPB * depth:
+        raise _lib.CffmError('expected %d parameter tensors for depth %d, got %d' % (NPB * depth, depth, len(params)))
+    ring = ring.detach()
+    r, b = ring.shape[0], tables.shape[0]
+    g, (key_src, q_dst, *_) = _layer_geom(lib, b, h0, w0, ring.device)
+    ws, out = _infer_buffers(lib, g, depth, prepared, ws, out, (b, h0 * w0, 256), ring.device)
+    _lib.check(lib.cffm_layer_infer_rows_ring_tables(C.byref(g), depth, block_structs(params, depth), _ptr(prepared), _ptr(ring), h0 * w0 * 256, r,
+                                                     _ptr(tables), _ptr(out), _ptr(key_src), _ptr(q_dst), _ptr(ws), _stream(ring)), lib)
     return out
 
 
